@@ -1,18 +1,24 @@
 #!/usr/bin/env python
 """Headline benchmark: PSMF filter timesteps/s at d=100k, r=32 (BASELINE.json `metric`).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 One "step" of this harness = one pass of the hot path (T filter timesteps, full PSMF filter:
 predict / y_hat = C mu_bar / innovation / r x r solve / low-rank updates of C, mu, P, V) over a
 synthetic series that is already resident in HBM.  value = K * T / elapsed  (timesteps per
-second of the whole job).  For N > 1 the d rows of C and y are sharded over the ranks
+second of the whole job).  A plain run does only what `value` needs: it uploads the series, runs
+untimed passes (runtime pools, then one pass from the initial state, so that the timed passes start
+from the same state as with --full), W warm-up passes and the K timed ones, and prints the line.
+--dump-outputs DIR then writes what the last timed pass computed (see dump_outputs).
+Everything else below -- the CPU baselines, the in-run parity against the oracle, the cold pass,
+the roofline and per-kernel figures, other_configs -- runs only with --full.
+For N > 1 the d rows of C and y are sharded over the ranks
 (strong scaling; blocked engine: one RCCL all-reduce of a 128 x 64 cross-Gram per block of 64 - r
 timesteps, off the critical path; per-step engine: r+1 doubles per timestep); launch with
 `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` -- torch is used
 only as rendezvous plumbing (gloo: id broadcast, barrier, max over ranks), never for compute.
 
-Extra objects on the JSON line (rank 0; the N = 1 run carries all of them):
+Extra objects on the JSON line with --full (rank 0; the N = 1 run carries all of them):
   roofline      dominant kernel (SURVEY 8(d) definition): algorithmic bytes 8 d (r+1) per timestep x timesteps per
                 launch / its average duration measured with HIP events on the stream it runs on, vs 8 TB/s HBM --
                 kept as the contract defines it, and labelled for what it is: the blocked engine REMOVES that
@@ -64,11 +70,16 @@ def parse():
     ap.add_argument("--T", "--timesteps", type=int, default=10_000, dest="T")
     ap.add_argument("--robust", type=int, default=0)
     ap.add_argument("--storage", default="f32")
-    ap.add_argument("--cpu-steps", type=int, default=300, help="timesteps of the CPU baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: CPU baselines and in-run parity against the oracle, "
+                         "the cold pass, roofline and per-kernel figures, other_configs (off by default)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed passes write what the last one computed to DIR/<name>.npy (float64 state, y_hat sample)")
+    ap.add_argument("--cpu-steps", type=int, default=300, help="with --full: timesteps of the CPU baseline sample (0 = skip)")
     ap.add_argument("--no-y-pred", action="store_true")
     ap.add_argument("--workgroups", type=int, default=0)
     ap.add_argument("--engine", default="auto", choices=["auto", "step", "block"])
-    ap.add_argument("--no-extras", action="store_true", help="skip other_configs / literal baseline / copy peak (profiling runs)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip other_configs / literal baseline / copy peak (profiling runs)")
     ap.add_argument("--comm", default="rccl", choices=["rccl", "gloo"],
                     help="N > 1: RCCL all-reduce on the device streams (default), or the host-mediated communicator over gloo "
                          "(psmf_comm_init_host) -- the transport for rehearsing the N > 1 path with all ranks on ONE GPU")
@@ -80,7 +91,10 @@ def parse():
     ap.add_argument("--parity-fixture", default=None,
                     help="stored oracle answers of this workload (format of tests/golden/make_golden_fullsize.py) for the in-run parity of a "
                          "sharded run; default: tests/golden/fullsize_E_{psmf,rpsmf}.npz when the workload is BASELINE config E")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 class Series:
@@ -538,6 +552,47 @@ def load_pmc(name):
     return json.load(open(p)) if os.path.exists(p) else None
 
 
+DUMP_BUDGET = 64_000_000      # bytes over all files of --dump-outputs
+DUMP_SEED = 20240607
+
+
+def dump_outputs(f, out_dir, T, world, rank, dist):
+    """--dump-outputs: what the last timed pass computed, as a caller of DeviceFilter.run receives it -- the filter state
+    (get_state: C, V, P, Q, mu and the scalars rho, lam, s, eta, N, phi, omega) in float64, and y_hat of that pass in the storage
+    type.  Within DUMP_BUDGET: y_hat at a fixed, seeded sample of at most 64 timesteps (y_hat_timesteps.npy), and C and y_hat at a
+    fixed, seeded sample of rows (rows.npy) when C would take more than half of it.  Ranks > 1 send their row shards to rank 0,
+    which writes the files (d = 100 000, r = 32: C 25.6 MB, y_hat 25.6 MB)."""
+    from rpsmf_amd._capi import F32
+
+    d, r = f.d, f.r
+    yp_type = np.float32 if f.storage == F32 else np.float64
+    rng = np.random.default_rng(DUMP_SEED)
+    n_rows = min(d, (DUMP_BUDGET // 2) // (8 * (r + 1)))          # C and rows.npy: half the budget
+    rows = np.arange(d) if n_rows == d else np.sort(rng.choice(d, n_rows, replace=False))
+    ts = np.sort(rng.choice(T, max(1, min(64, T, (DUMP_BUDGET // 2 - 1_000_000) // (np.dtype(yp_type).itemsize * n_rows))), replace=False))
+    s = f.get_state()
+    C = s["C"]
+    Y = np.concatenate([f.y_pred(int(t), 1, dtype=yp_type) for t in ts]) if f.store_y_pred else None
+    if dist is not None:        # row shards in rank order (shard_rows): concatenated they are the whole filter's rows
+        parts = [None] * world
+        dist.all_gather_object(parts, (C, Y))
+        C = np.concatenate([p[0] for p in parts])
+        Y = np.concatenate([p[1] for p in parts], axis=1) if Y is not None else None
+    if rank != 0:
+        return
+    out = {"C": C[rows], "V": s["V"], "P": s["P"], "Q": s["Q"], "mu": s["mu"]}
+    out.update({k: np.float64(s[k]) for k in ("rho", "lam", "s", "eta", "N", "phi", "omega")})
+    out.update({k: s[k] for k in ("theta", "gradsum") if s[k].size})
+    if Y is not None:
+        out["y_hat"] = Y[:, rows]
+        out["y_hat_timesteps"] = ts.astype(np.float64)
+    if n_rows < d:
+        out["rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=yp_type if name == "y_hat" else np.float64))
+
+
 def main():
     args = parse()
     # The contract is ONE JSON line on stdout.  Libraries underneath write there too (gloo's "Rank 0 is connected to ..." line, RCCL's
@@ -661,15 +716,15 @@ def main():
         dist.all_reduce(te, op=dist.ReduceOp.MAX)
         return float(te.item())
 
-    # ---- CPU baseline + in-run parity of the GPU path against it (rank 0, N = 1 only)
+    # ---- --full: CPU baseline + in-run parity of the GPU path against it (rank 0, N = 1 only)
     cpu = None
     parity = None
-    if world == 1 and args.cpu_steps > 0:
+    if args.full and world == 1 and args.cpu_steps > 0:
         cpu, st_cpu, n_cpu = cpu_baseline(args, series, st0)
         reset()
         f.run(0, n_cpu)
         parity = parity_of(f, st_cpu, n_cpu)
-    elif world > 1 and args.cpu_steps > 0:
+    elif args.full and world > 1 and args.cpu_steps > 0:
         fixture = args.parity_fixture
         if fixture is None and (d, r, T, args.scaling) == (100_000, 32, 10_000, "strong"):
             fixture = os.path.join(ROOT, "tests", "golden", f"fullsize_E_{'rpsmf' if args.robust else 'psmf'}.npz")
@@ -685,9 +740,10 @@ def main():
         f.run(0, T, sync=False)
     f.sync()
     # ---- config E as literally stated: ONE pass of T timesteps from the initial state, timed on its own
-    # (twice, each from the initial state: a single 40 ms measurement is at the mercy of one host hiccup; both are reported)
+    # (--full: twice, each from the initial state: a single 40 ms measurement is at the mercy of one host hiccup; both are reported.
+    # A plain run makes the pass once and reports nothing of it: the timed passes start from the state they do under --full)
     cold_runs = []
-    for _ in range(2):
+    for _ in range(2 if args.full else 1):
         reset()
         f.sync()
         barrier()
@@ -701,7 +757,8 @@ def main():
     for _ in range(args.warmup):
         f.run(0, T, sync=False)
     f.sync()
-    if geo_engine_block(f):
+    in_kernel_times = args.full and geo_engine_block(f)      # the library records them always; --full reads them
+    if in_kernel_times:
         f.counters(reset=True)
         f.filter_kernel_time(reset=True)
     barrier()
@@ -713,10 +770,12 @@ def main():
     f.sync()
     barrier()
     elapsed = time.perf_counter() - t0
-    insitu = f.counters() if geo_engine_block(f) else None      # device-timer durations of the filter kernels of the timed region
-    chained = f.filter_kernel_time() if geo_engine_block(f) else (0, 0.0)   # HIP events around the chained filter launches of the timed region
+    insitu = f.counters() if in_kernel_times else None      # device-timer durations of the filter kernels of the timed region
+    chained = f.filter_kernel_time() if in_kernel_times else (0, 0.0)   # HIP events around the chained filter launches of the timed region
     elapsed = max_over_ranks(elapsed)
     value = args.steps * T / elapsed
+    if args.dump_outputs:
+        dump_outputs(f, args.dump_outputs, T, world, rank, dist)
     # ---- what the exchange really was: the communicator as RCCL reports it, which GPU every rank drives, and per rank the time
     # between consecutive blocks of the chained filter launch (an all-reduce that landed on the critical path shows there)
     cinfo = f.comm_info()
@@ -729,91 +788,92 @@ def main():
         dist.all_gather_object(per_rank, mine)
 
     # ---- roofline of the dominant kernel, HIP events on the library's stream (psmf_time_kernel)
-    es = 4.0 if args.storage == "f32" else 8.0
-    bytes_per_step = 2.0 * es * d_local * (r + 1)   # read C, write C, read y, write y_hat
     geo = f.geometry()
-    traffic = None
-    if geo["engine"] == "block":
-        # one launch of the coefficient-space filter kernel = every block of a pass (chained); the two d-sized
-        # products of each block (cross-Gram, apply) run concurrently on a second stream
-        B = geo["block_steps"]
-        t_filter = f.time_kernel(0, 20)
-        t_gram = f.time_kernel(1, 50)
-        t_apply = f.time_kernel(2, 50)
-        t_block_insitu = insitu["filter_us_mean"] if insitu and insitu["filter_launches"] > 0 else t_filter
-        if chained[0] > 0:
-            # HIP events around every chained launch of the timed region, on the stream it runs on: reported as measured (the host
-            # wall time of a pass is beside it as ms_per_step; the two clocks differ by ~0.2 %)
-            kernel, kernel_us, steps_per_launch = geo.get("filter_kernel", "psmf_blk_filter3"), 1e3 * chained[1] / chained[0], float(T)
+    if args.full:
+        es = 4.0 if args.storage == "f32" else 8.0
+        bytes_per_step = 2.0 * es * d_local * (r + 1)   # read C, write C, read y, write y_hat
+        traffic = None
+        if geo["engine"] == "block":
+            # one launch of the coefficient-space filter kernel = every block of a pass (chained); the two d-sized
+            # products of each block (cross-Gram, apply) run concurrently on a second stream
+            B = geo["block_steps"]
+            t_filter = f.time_kernel(0, 20)
+            t_gram = f.time_kernel(1, 50)
+            t_apply = f.time_kernel(2, 50)
+            t_block_insitu = insitu["filter_us_mean"] if insitu and insitu["filter_launches"] > 0 else t_filter
+            if chained[0] > 0:
+                # HIP events around every chained launch of the timed region, on the stream it runs on: reported as measured (the host
+                # wall time of a pass is beside it as ms_per_step; the two clocks differ by ~0.2 %)
+                kernel, kernel_us, steps_per_launch = geo.get("filter_kernel", "psmf_blk_filter3"), 1e3 * chained[1] / chained[0], float(T)
+            else:
+                full_blocks_only = (T % B == 0)
+                kernel, kernel_us = geo.get("filter_kernel", "psmf_blk_filter3"), t_block_insitu
+                steps_per_launch = B if full_blocks_only else T / (insitu["filter_launches"] / args.steps)
+            zbytes = es * d_local * 64
+            nb1 = min(B, 64)
+            xg_bytes = es * d_local * (r + B + nb1)          # cross-Gram reads C, the current and the next series block
+            ap_bytes = 2.0 * es * d_local * (r + B)          # apply reads C, Y_cur and writes C, Y_hat
+            pmc_name = next((n for n in ("r4_pmc_traffic_block_engine.json", "r3_pmc_traffic_block_engine.json", "r2_pmc_traffic_block_engine.json", "r1_pmc_traffic_block_engine.json")
+                             if os.path.exists(os.path.join(ROOT, "profiles", n))), None)
+            pmc = load_pmc(pmc_name) if pmc_name else None
+            real_hbm = None
+            traffic_source = None
+            if (d, r, args.storage, world) == (100_000, 32, "f32", 1) and pmc:
+                # rocprofv3 --pmc passes of this workload (counter collection serialises the kernels; the library then runs
+                # one filter launch per block): bytes per block of B timesteps, scaled to the blocks one launch advances
+                traffic = pmc["traffic_bytes_per_launch"] * (steps_per_launch / B)
+                traffic_source = (f"profiles/{pmc_name} (rocprofv3 --pmc passes of this workload, committed; NOT measured in this run; counter "
+                                  "collection serialises kernels, so those passes ran the per-block schedule -- one filter launch per block, event "
+                                  "hand-off -- not the chained launch timed here: same kernels and bytes per block, different launch structure)")
+                if "all_kernels_bytes_per_block" in pmc:
+                    real_hbm = pmc["all_kernels_bytes_per_block"] * (T / B) / (elapsed / args.steps) / 1e9
+            steps_timed = max(1, (insitu["ns_steps"] + insitu["sweep_steps"])) if insitu else 1
+            iters_per_step = insitu["ns_iterations"] / steps_timed if insitu else None
+            step_us = t_block_insitu / B
+            extra = {"steps_per_launch": steps_per_launch,
+                     "blocks_per_launch": steps_per_launch / B,
+                     "block_us_in_kernel": t_block_insitu,
+                     "one_block_us_hip_events_standalone": t_filter,
+                     "gap_between_blocks_us": insitu["filter_gap_us_mean"] if insitu else None,
+                     "gap_between_blocks_us_per_rank": [p["gap_between_blocks_us"] for p in per_rank],
+                     "block_us_in_kernel_per_rank": [p["block_us_in_kernel"] for p in per_rank],
+                     "real_hbm_GBps": real_hbm,
+                     "traffic_source": traffic_source,
+                     # the blocked formulation's own minimum per block of B timesteps: cross-Gram reads C, Y_cur, Y_next; apply reads
+                     # C, Y_cur and writes C, Y_hat (f32) -- against what the counters say the kernels of a block move
+                     "blocked_min_bytes_per_block": xg_bytes + ap_bytes,
+                     "blocked_traffic_over_min": (pmc["all_kernels_bytes_per_block"] / (xg_bytes + ap_bytes))
+                                                 if (traffic_source and pmc and "all_kernels_bytes_per_block" in pmc) else None,
+                     "filter_chain_frac": (iters_per_step * NS_ITER_ISSUE_US / step_us) if iters_per_step else None,
+                     "filter_chain": {"newton_schulz_iterations_per_timestep": iters_per_step, "mfma_issue_us_per_iteration": NS_ITER_ISSUE_US,
+                                      "us_per_timestep_in_kernel": step_us,
+                                      "timesteps_by_direct_sweep": insitu["sweep_steps"] if insitu else None},
+                     "kernels_us": {"psmf_blk_filter3": t_filter, "psmf_blk_xgram2+xreduce2": t_gram, "psmf_blk_apply2": t_apply},
+                     "bulk_kernels": {"psmf_blk_xgram2+xreduce2": {"bytes": xg_bytes, "us": t_gram, "GBps": xg_bytes / (t_gram * 1e-6) / 1e9,
+                                                                  "frac_of_hbm_peak": xg_bytes / (t_gram * 1e-6) / 1e9 / HBM_PEAK_GBS},
+                                      "psmf_blk_apply2": {"bytes": ap_bytes, "us": t_apply, "GBps": ap_bytes / (t_apply * 1e-6) / 1e9,
+                                                          "frac_of_hbm_peak": ap_bytes / (t_apply * 1e-6) / 1e9 / HBM_PEAK_GBS}},
+                     "note": "filter_chain_frac is the distance of the timed kernel to ITS bound: matrix-core issue time of the Newton-Schulz products of a "
+                             "timestep / measured time per timestep inside the filter kernel (one workgroup, a chain of r x r stages bound by its "
+                             "instruction stream on one CU).  frac = SURVEY 8(d) bookkeeping: step-at-a-time algorithmic bytes of the timesteps one "
+                             "launch advances / its duration / 8 TB/s -- the blocked engine does not move those bytes (traffic, real_hbm_GBps, "
+                             "blocked_min_bytes_per_block); the kernels that do stream the data are under bulk_kernels"}
+        elif geo.get("filter_kernel") == "psmf_pstep_k":
+            # per-step engine as ONE persistent launch per pass (psmf_pstep.hip): HIP events around a pass on the stream it runs on
+            kernel, steps_per_launch = "psmf_pstep_k", float(T)
+            kernel_us = 1e3 * min(f.run_timed(0, T) for _ in range(2))
+            extra = {"steps_per_launch": steps_per_launch, "us_per_timestep_in_kernel": kernel_us / T,
+                     "note": "C stays on chip (float64, in the row workgroups' registers) for the whole launch: the kernel moves y and y_hat only; "
+                             "frac is the SURVEY 8(d) bookkeeping ratio (step-at-a-time bytes / duration / 8 TB/s), not a bandwidth -- what bounds "
+                             "the kernel is the latency of its two hand-offs and of the r x r stage per timestep (docs/MEASUREMENTS.md)"}
         else:
-            full_blocks_only = (T % B == 0)
-            kernel, kernel_us = geo.get("filter_kernel", "psmf_blk_filter3"), t_block_insitu
-            steps_per_launch = B if full_blocks_only else T / (insitu["filter_launches"] / args.steps)
-        zbytes = es * d_local * 64
-        nb1 = min(B, 64)
-        xg_bytes = es * d_local * (r + B + nb1)          # cross-Gram reads C, the current and the next series block
-        ap_bytes = 2.0 * es * d_local * (r + B)          # apply reads C, Y_cur and writes C, Y_hat
-        pmc_name = next((n for n in ("r4_pmc_traffic_block_engine.json", "r3_pmc_traffic_block_engine.json", "r2_pmc_traffic_block_engine.json", "r1_pmc_traffic_block_engine.json")
-                         if os.path.exists(os.path.join(ROOT, "profiles", n))), None)
-        pmc = load_pmc(pmc_name) if pmc_name else None
-        real_hbm = None
-        traffic_source = None
-        if (d, r, args.storage, world) == (100_000, 32, "f32", 1) and pmc:
-            # rocprofv3 --pmc passes of this workload (counter collection serialises the kernels; the library then runs
-            # one filter launch per block): bytes per block of B timesteps, scaled to the blocks one launch advances
-            traffic = pmc["traffic_bytes_per_launch"] * (steps_per_launch / B)
-            traffic_source = (f"profiles/{pmc_name} (rocprofv3 --pmc passes of this workload, committed; NOT measured in this run; counter "
-                              "collection serialises kernels, so those passes ran the per-block schedule -- one filter launch per block, event "
-                              "hand-off -- not the chained launch timed here: same kernels and bytes per block, different launch structure)")
-            if "all_kernels_bytes_per_block" in pmc:
-                real_hbm = pmc["all_kernels_bytes_per_block"] * (T / B) / (elapsed / args.steps) / 1e9
-        steps_timed = max(1, (insitu["ns_steps"] + insitu["sweep_steps"])) if insitu else 1
-        iters_per_step = insitu["ns_iterations"] / steps_timed if insitu else None
-        step_us = t_block_insitu / B
-        extra = {"steps_per_launch": steps_per_launch,
-                 "blocks_per_launch": steps_per_launch / B,
-                 "block_us_in_kernel": t_block_insitu,
-                 "one_block_us_hip_events_standalone": t_filter,
-                 "gap_between_blocks_us": insitu["filter_gap_us_mean"] if insitu else None,
-                 "gap_between_blocks_us_per_rank": [p["gap_between_blocks_us"] for p in per_rank],
-                 "block_us_in_kernel_per_rank": [p["block_us_in_kernel"] for p in per_rank],
-                 "real_hbm_GBps": real_hbm,
-                 "traffic_source": traffic_source,
-                 # the blocked formulation's own minimum per block of B timesteps: cross-Gram reads C, Y_cur, Y_next; apply reads
-                 # C, Y_cur and writes C, Y_hat (f32) -- against what the counters say the kernels of a block move
-                 "blocked_min_bytes_per_block": xg_bytes + ap_bytes,
-                 "blocked_traffic_over_min": (pmc["all_kernels_bytes_per_block"] / (xg_bytes + ap_bytes))
-                                             if (traffic_source and pmc and "all_kernels_bytes_per_block" in pmc) else None,
-                 "filter_chain_frac": (iters_per_step * NS_ITER_ISSUE_US / step_us) if iters_per_step else None,
-                 "filter_chain": {"newton_schulz_iterations_per_timestep": iters_per_step, "mfma_issue_us_per_iteration": NS_ITER_ISSUE_US,
-                                  "us_per_timestep_in_kernel": step_us,
-                                  "timesteps_by_direct_sweep": insitu["sweep_steps"] if insitu else None},
-                 "kernels_us": {"psmf_blk_filter3": t_filter, "psmf_blk_xgram2+xreduce2": t_gram, "psmf_blk_apply2": t_apply},
-                 "bulk_kernels": {"psmf_blk_xgram2+xreduce2": {"bytes": xg_bytes, "us": t_gram, "GBps": xg_bytes / (t_gram * 1e-6) / 1e9,
-                                                              "frac_of_hbm_peak": xg_bytes / (t_gram * 1e-6) / 1e9 / HBM_PEAK_GBS},
-                                  "psmf_blk_apply2": {"bytes": ap_bytes, "us": t_apply, "GBps": ap_bytes / (t_apply * 1e-6) / 1e9,
-                                                      "frac_of_hbm_peak": ap_bytes / (t_apply * 1e-6) / 1e9 / HBM_PEAK_GBS}},
-                 "note": "filter_chain_frac is the distance of the timed kernel to ITS bound: matrix-core issue time of the Newton-Schulz products of a "
-                         "timestep / measured time per timestep inside the filter kernel (one workgroup, a chain of r x r stages bound by its "
-                         "instruction stream on one CU).  frac = SURVEY 8(d) bookkeeping: step-at-a-time algorithmic bytes of the timesteps one "
-                         "launch advances / its duration / 8 TB/s -- the blocked engine does not move those bytes (traffic, real_hbm_GBps, "
-                         "blocked_min_bytes_per_block); the kernels that do stream the data are under bulk_kernels"}
-    elif geo.get("filter_kernel") == "psmf_pstep_k":
-        # per-step engine as ONE persistent launch per pass (psmf_pstep.hip): HIP events around a pass on the stream it runs on
-        kernel, steps_per_launch = "psmf_pstep_k", float(T)
-        kernel_us = 1e3 * min(f.run_timed(0, T) for _ in range(2))
-        extra = {"steps_per_launch": steps_per_launch, "us_per_timestep_in_kernel": kernel_us / T,
-                 "note": "C stays on chip (float64, in the row workgroups' registers) for the whole launch: the kernel moves y and y_hat only; "
-                         "frac is the SURVEY 8(d) bookkeeping ratio (step-at-a-time bytes / duration / 8 TB/s), not a bandwidth -- what bounds "
-                         "the kernel is the latency of its two hand-offs and of the r x r stage per timestep (docs/MEASUREMENTS.md)"}
-    else:
-        kernel, kernel_us, steps_per_launch = "psmf_sweep_solve", f.time_kernel(0, 300), 1
-        extra = {"steps_per_launch": 1, "kernels_us": {"psmf_sweep_solve": kernel_us, "psmf_serial": f.time_kernel(1, 300)}}
-        pmc = load_pmc("r1_pmc_traffic.json")
-        if (d, r, args.storage, world) == (100_000, 32, "f32", 1) and pmc:
-            traffic = pmc["traffic_bytes_per_launch"]   # rocprofv3 --pmc passes of this workload
-    alg_bytes = bytes_per_step * steps_per_launch
-    achieved = alg_bytes / (kernel_us * 1e-6) / 1e9
+            kernel, kernel_us, steps_per_launch = "psmf_sweep_solve", f.time_kernel(0, 300), 1
+            extra = {"steps_per_launch": 1, "kernels_us": {"psmf_sweep_solve": kernel_us, "psmf_serial": f.time_kernel(1, 300)}}
+            pmc = load_pmc("r1_pmc_traffic.json")
+            if (d, r, args.storage, world) == (100_000, 32, "f32", 1) and pmc:
+                traffic = pmc["traffic_bytes_per_launch"]   # rocprofv3 --pmc passes of this workload
+        alg_bytes = bytes_per_step * steps_per_launch
+        achieved = alg_bytes / (kernel_us * 1e-6) / 1e9
     f.close()
 
     if rank == 0:
@@ -837,16 +897,19 @@ def main():
                        "d": d, "d_per_gpu": d_local, "r": r, "T": T, "timesteps_per_pass": T, "store_y_pred": not args.no_y_pred,
                        "exchange": exchange_info(world, args, per_rank, geo, r),
                        "us_per_timestep": 1e6 * elapsed / (args.steps * T), "engine": geo["engine"], "geometry": geo},
-            # BASELINE config E as literally stated -- ONE pass of T timesteps from the initial state -- next to `value`, which is
-            # the steady state of carried-state passes (epochs 2, 3, ... of PSMFIter.run)
-            "value_config_E_literal": T / cold_elapsed,
-            "cold_pass_steps_per_s": T / cold_elapsed,
-            "cold_pass_runs_steps_per_s": [T / c for c in cold_runs],
-            "roofline": dict({"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                              "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "kernel": kernel, "kernel_us": kernel_us,
-                              "algorithmic_bytes_per_launch": alg_bytes,
-                              "whole_job_frac": value * 2.0 * es * d * (r + 1) / (world * HBM_PEAK_GBS * 1e9)}, **extra),
         }
+        if args.full:
+            line.update({
+                # BASELINE config E as literally stated -- ONE pass of T timesteps from the initial state -- next to `value`, which is
+                # the steady state of carried-state passes (epochs 2, 3, ... of PSMFIter.run)
+                "value_config_E_literal": T / cold_elapsed,
+                "cold_pass_steps_per_s": T / cold_elapsed,
+                "cold_pass_runs_steps_per_s": [T / c for c in cold_runs],
+                "roofline": dict({"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                  "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "kernel": kernel, "kernel_us": kernel_us,
+                                  "algorithmic_bytes_per_launch": alg_bytes,
+                                  "whole_job_frac": value * 2.0 * es * d * (r + 1) / (world * HBM_PEAK_GBS * 1e9)}, **extra),
+            })
         if world > 1:
             # an N-GPU number carried over the host path must not be mistaken for an RCCL number
             line["transport_fallback"] = bool(per_rank[0].get("rccl_error")) or args.comm != "rccl"
@@ -858,7 +921,7 @@ def main():
             line["cpu_baseline"] = cpu
         if parity is not None:
             line["parity_vs_cpu_oracle"] = parity
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             try:
                 line["roofline"]["hbm_peak_measured"] = {"GBps": _capi.measure_copy_bandwidth(local_rank, 1 << 32, 10),
                                                          "what": "copy kernel, 4 GiB read + 4 GiB written per launch, 16-byte accesses"}

@@ -18,13 +18,14 @@ pytestmark = [pytest.mark.gpu, pytest.mark.timeout(300)]
 
 
 @pytest.mark.parametrize("engine,d,r", [("block", 8000, 32), ("step", 3000, 12)])
-def test_bench_two_ranks_one_gpu(engine, d, r):
+def test_bench_two_ranks_one_gpu(engine, d, r, tmp_path):
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--rows", str(d),
-           "--latent-rank", str(r), "--timesteps", "400", "--cpu-steps", "150", "--no-extras", "--comm", "gloo", "--one-device", "--engine", engine]
+           "--latent-rank", str(r), "--timesteps", "400", "--cpu-steps", "150", "--no-extras", "--full", "--comm", "gloo", "--one-device", "--engine", engine,
+           "--dump-outputs", str(tmp_path / "out")]
     env = dict(os.environ, OMP_NUM_THREADS="4")
     pr = subprocess.run(cmd, capture_output=True, text=True, timeout=280, env=env, cwd=ROOT)
     assert pr.returncode == 0, pr.stdout[-2000:] + pr.stderr[-3000:]
@@ -48,6 +49,19 @@ def test_bench_two_ranks_one_gpu(engine, d, r):
         assert len(gaps) == 2 and all(g is not None and g >= 0.0 for g in gaps)
     else:
         assert ex["messages"]["per_timestep_bytes"] == (r + 1) * 8
+    # --dump-outputs: rank 0 writes the whole filter's rows, the shards of both ranks in order -- what the unsharded run computes
+    import numpy as np
+
+    from conftest import relerr
+
+    cmd1 = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--rows", str(d), "--latent-rank", str(r),
+            "--timesteps", "400", "--engine", engine, "--dump-outputs", str(tmp_path / "one")]
+    pr1 = subprocess.run(cmd1, capture_output=True, text=True, timeout=280, env=env, cwd=ROOT)
+    assert pr1.returncode == 0, pr1.stdout[-2000:] + pr1.stderr[-3000:]
+    for name in ("C", "V", "P", "mu", "y_hat"):
+        two, one = np.load(tmp_path / "out" / f"{name}.npy"), np.load(tmp_path / "one" / f"{name}.npy")
+        # (2 000 timesteps of float32 storage, sums over the rows in another order: apart by far less than this; rows out of place, by O(1))
+        assert two.shape == one.shape and relerr(two, one) < 1e-3, (name, two.shape, one.shape, relerr(two, one))
 
 
 def test_bench_four_ranks_one_gpu_uneven_rows():
@@ -60,7 +74,7 @@ def test_bench_four_ranks_one_gpu_uneven_rows():
     d, r = 10_002, 32
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1", "--rows", str(d),
-           "--latent-rank", str(r), "--timesteps", "400", "--cpu-steps", "150", "--no-extras", "--comm", "gloo", "--one-device"]
+           "--latent-rank", str(r), "--timesteps", "400", "--cpu-steps", "150", "--no-extras", "--full", "--comm", "gloo", "--one-device"]
     pr = subprocess.run(cmd, capture_output=True, text=True, timeout=280, env=dict(os.environ, OMP_NUM_THREADS="2"), cwd=ROOT)
     assert pr.returncode == 0, pr.stdout[-2000:] + pr.stderr[-3000:]
     lines = [ln for ln in pr.stdout.splitlines() if ln.startswith("{")]
@@ -85,7 +99,7 @@ def test_bench_falls_back_to_gloo_when_rccl_does_not_come_up():
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--rows", "8000",
-           "--latent-rank", "32", "--timesteps", "400", "--cpu-steps", "150", "--no-extras", "--one-device"]
+           "--latent-rank", "32", "--timesteps", "400", "--cpu-steps", "150", "--no-extras", "--full", "--one-device"]
     env = dict(os.environ, OMP_NUM_THREADS="4")
     pr = subprocess.run(cmd, capture_output=True, text=True, timeout=280, env=env, cwd=ROOT)
     assert pr.returncode == 0, pr.stdout[-2000:] + pr.stderr[-3000:]
@@ -115,7 +129,7 @@ def test_bench_two_ranks_parity_against_stored_answers(tmp_path):
     np.savez_compressed(path, **fx)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--rows", str(d),
-           "--latent-rank", str(r), "--timesteps", str(T), "--cpu-steps", "150", "--no-extras", "--comm", "gloo", "--one-device",
+           "--latent-rank", str(r), "--timesteps", str(T), "--cpu-steps", "150", "--no-extras", "--full", "--comm", "gloo", "--one-device",
            "--parity-fixture", path]
     pr = subprocess.run(cmd, capture_output=True, text=True, timeout=280, env=dict(os.environ, OMP_NUM_THREADS="4"), cwd=ROOT)
     assert pr.returncode == 0, pr.stdout[-2000:] + pr.stderr[-3000:]
@@ -135,7 +149,7 @@ def test_bench_weak_scaling_two_ranks_one_gpu():
     """`--scaling weak`: every rank holds --rows rows, the filter has N x as many; the line says so."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--rows", "4000",
-           "--latent-rank", "32", "--timesteps", "400", "--cpu-steps", "150", "--no-extras", "--comm", "gloo", "--one-device", "--scaling", "weak"]
+           "--latent-rank", "32", "--timesteps", "400", "--cpu-steps", "150", "--no-extras", "--full", "--comm", "gloo", "--one-device", "--scaling", "weak"]
     pr = subprocess.run(cmd, capture_output=True, text=True, timeout=280, env=dict(os.environ, OMP_NUM_THREADS="4"), cwd=ROOT)
     assert pr.returncode == 0, pr.stdout[-2000:] + pr.stderr[-3000:]
     out = json.loads([ln for ln in pr.stdout.splitlines() if ln.startswith("{")][0])
@@ -155,7 +169,7 @@ def test_forced_collective_single_rank_bench_costs_nothing():
         env.pop("PSMF_FORCE_COLLECTIVE", None)
         if forced:
             env["PSMF_FORCE_COLLECTIVE"] = "1"
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "8", "--warmup", "2", "--timesteps", "3200", "--cpu-steps", "0", "--no-extras"]
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "8", "--warmup", "2", "--timesteps", "3200", "--cpu-steps", "0", "--no-extras", "--full"]
         pr = subprocess.run(cmd, capture_output=True, text=True, timeout=280, env=env, cwd=ROOT)
         assert pr.returncode == 0, pr.stdout[-2000:] + pr.stderr[-3000:]
         out = json.loads([ln for ln in pr.stdout.splitlines() if ln.startswith("{")][0])

@@ -6,10 +6,10 @@ O=gpurun_out/r4p
 mkdir -p $O
 if [ "$1" = "a" ]; then
   # the bench line of the final build
-  python bench.py > $O/bench_n1.json 2> $O/bench_n1.err
+  python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err
   # kernel trace + stats of the default workload (whole-pass launches of the chained filter kernel)
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 bench.py --steps 5 --warmup 1 --cpu-steps 0 --no-extras > $O/bench_under_rocprof.json 2> $O/kt.err
-  python tools/trace_summary.py $O/kt "rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 5 --warmup 1 --cpu-steps 0 --no-extras; whole-pass launches = 2 pre-warm + 2 cold + 1 warm-up + 5 timed (T = 10 000 each); the short launches are psmf_time_kernel stand-alone blocks" > $O/kernel_trace_chain_summary.json
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 bench.py --steps 5 --warmup 1 --cpu-steps 0 --no-extras --full > $O/bench_under_rocprof.json 2> $O/kt.err
+  python tools/trace_summary.py $O/kt "rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 5 --warmup 1 --cpu-steps 0 --no-extras --full; whole-pass launches = 2 pre-warm + 2 cold + 1 warm-up + 5 timed (T = 10 000 each); the short launches are psmf_time_kernel stand-alone blocks" > $O/kernel_trace_chain_summary.json
   find $O/kt -name "*kernel_stats.csv" -exec cp {} $O/kernel_stats_chain.csv \;
   find $O -name "*kernel_trace.csv" -size +10M -delete || true
   # per-step and masked engines under the profiler (few steps: rocprofv3's CSV writer crashes on long traces on this image)
@@ -19,11 +19,11 @@ if [ "$1" = "a" ]; then
   python tools/probe_modes.py > $O/modes.txt 2>&1
 else
   # HBM traffic of the blocked engine's kernels (separate --pmc passes; FETCH_SIZE x 2 on gfx950)
-  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/pmc_f -- python3 bench.py --steps 1 --warmup 1 --cpu-steps 0 --T 1000 --no-extras > $O/bench_pmc_f.json 2> $O/pmc_f.err
-  rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/pmc_w -- python3 bench.py --steps 1 --warmup 1 --cpu-steps 0 --T 1000 --no-extras > $O/bench_pmc_w.json 2> $O/pmc_w.err
+  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/pmc_f -- python3 bench.py --steps 1 --warmup 1 --cpu-steps 0 --T 1000 --no-extras --full > $O/bench_pmc_f.json 2> $O/pmc_f.err
+  rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/pmc_w -- python3 bench.py --steps 1 --warmup 1 --cpu-steps 0 --T 1000 --no-extras --full > $O/bench_pmc_w.json 2> $O/pmc_w.err
   (cd tools && python pmc_block_engine.py ../$O/pmc.json ../$O/pmc_f ../$O/pmc_w > ../$O/pmc_summary.txt)
   # instruction mix of the filter kernel
-  rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_MFMA --output-format csv -d $O/pmc_sq -- python3 bench.py --steps 1 --warmup 1 --cpu-steps 0 --T 1000 --no-extras > $O/bench_pmc_sq.json 2> $O/pmc_sq.err
+  rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_MFMA --output-format csv -d $O/pmc_sq -- python3 bench.py --steps 1 --warmup 1 --cpu-steps 0 --T 1000 --no-extras --full > $O/bench_pmc_sq.json 2> $O/pmc_sq.err
   python - <<'PY' > $O/pmc_filter3_sq.json
 import csv, glob, json, collections
 f = glob.glob("gpurun_out/r4p/pmc_sq/**/*counter_collection.csv", recursive=True)[0]

@@ -6,10 +6,10 @@ O=gpurun_out/r5p
 mkdir -p $O
 if [ "$1" = "a" ]; then
   # the bench line of the final build
-  python bench.py > $O/bench_n1.json 2> $O/bench_n1.err
+  python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err
   # kernel trace + stats of the default workload (whole-pass launches of the chained filter kernel)
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 bench.py --steps 5 --warmup 1 --cpu-steps 0 --no-extras > $O/bench_under_rocprof.json 2> $O/kt.err
-  python tools/trace_summary.py $O/kt "rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 5 --warmup 1 --cpu-steps 0 --no-extras; whole-pass launches = 2 pre-warm + 2 cold + 1 warm-up + 5 timed (T = 10 000 each); the short launches are psmf_time_kernel stand-alone blocks" > $O/kernel_trace_chain_summary.json
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 bench.py --steps 5 --warmup 1 --cpu-steps 0 --no-extras --full > $O/bench_under_rocprof.json 2> $O/kt.err
+  python tools/trace_summary.py $O/kt "rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 5 --warmup 1 --cpu-steps 0 --no-extras --full; whole-pass launches = 2 pre-warm + 2 cold + 1 warm-up + 5 timed (T = 10 000 each); the short launches are psmf_time_kernel stand-alone blocks" > $O/kernel_trace_chain_summary.json
   find $O/kt -name "*kernel_stats.csv" -exec cp {} $O/kernel_stats_chain.csv \;
   find $O -name "*kernel_trace.csv" -size +10M -delete || true
   # the persistent per-step kernel under the profiler: config E's shape, unmasked and masked
