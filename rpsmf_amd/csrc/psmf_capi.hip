@@ -23,6 +23,7 @@
 #include <limits>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 using psmf::DevState;
@@ -46,29 +47,50 @@ constexpr int kGramWG = 128;
 
 }  // namespace
 
-// Environment switches ("Switches"): read ONCE per handle, at psmf_create -- tests flip them between
-// handles of one process; nothing on the per-block host path calls getenv.
+// Environment switches: one row each, and this struct is the library's only reader of the environment.  The rows
+// are read when a Switches is constructed: ONCE per handle, with the handle at psmf_create -- tests flip them between handles of one
+// process, and nothing on the per-block host path looks at the environment; the entry points without a handle (psmf_impute_*,
+// psmf_measure_copy_bandwidth) construct one at entry, on every call.
 struct Switches {
-  bool bulk2 = true, filter3 = true, filter4 = true, filter6 = true, filter7 = true, filter6_dual = true, block_dual = true, block_flags = true, block_chain = true, block_pipe = true;
-  bool force_collective = false;
-  bool host_comm_flags = false;     // PSMF_HOST_COMM_FLAGS=1: device-flag hand-off (and chained filter launches) under a host-mediated communicator too
-  bool serial_wide = true, step_dual = true, tail_reduce = true, wgram_mfma = true, pstep_big = true;
-  int sweep_threads = 512;
-  double ns_far4 = 0.6;            // filter4 / filter4s: residual at which a Newton-Schulz start is given up (PSMF_NS_FAR4; PSMF_NS_FAR, when set, rules both)
-  bool ns_far_set = false;
-  bool step_persistent = true;      // per-step engine: one persistent launch per run (psmf_pstep.hip) where it applies; PSMF_STEP_PERSISTENT=0: two launches per timestep
-  static bool off(const char* name) { const char* e = getenv(name); return e && atoi(e) == 0; }
-  void read() {
-    bulk2 = !off("PSMF_BULK2"); filter3 = !off("PSMF_FILTER3"); filter4 = !off("PSMF_FILTER4"); filter6 = !off("PSMF_FILTER6"); filter7 = !off("PSMF_FILTER7"); filter6_dual = !off("PSMF_FILTER6_DUAL"); block_dual = !off("PSMF_BLOCK_DUAL");
-    block_flags = !off("PSMF_BLOCK_FLAGS"); block_chain = !off("PSMF_BLOCK_CHAIN"); block_pipe = !off("PSMF_BLOCK_PIPE");
-    force_collective = getenv("PSMF_FORCE_COLLECTIVE") != nullptr;
-    { const char* e = getenv("PSMF_HOST_COMM_FLAGS"); host_comm_flags = e && atoi(e) != 0; }
-    step_persistent = !off("PSMF_STEP_PERSISTENT");
-    serial_wide = !off("PSMF_SERIAL_WIDE"); step_dual = !off("PSMF_STEP_DUAL"); tail_reduce = !off("PSMF_TAIL_REDUCE"); wgram_mfma = !off("PSMF_WGRAM_MFMA"); pstep_big = !off("PSMF_PSTEP_BIG");
-    { const char* e = getenv("PSMF_SWEEP_THREADS"); sweep_threads = (e && atoi(e) == 256) ? 256 : 512; }
-    if (const char* e = getenv("PSMF_NS_FAR4")) ns_far4 = atof(e);
-    ns_far_set = getenv("PSMF_NS_FAR") != nullptr;
-  }
+  static bool set(const char* name) { return getenv(name) != nullptr; }                                  // present at all
+  static bool on(const char* name) { const char* e = getenv(name); return e && atoi(e) != 0; }           // set and non-zero
+  static bool off(const char* name) { const char* e = getenv(name); return e && atoi(e) == 0; }          // set to zero
+  static int as_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+  static double as_double(const char* name, double dflt) { const char* e = getenv(name); return e ? atof(e) : dflt; }
+
+  int engine_env = as_int("PSMF_ENGINE", 0);             // 1 | 2: force the per-step / blocked engine (2 only where the blocked engine applies)
+  // blocked engine; "=0" puts the older / more general kernel in the place of the role-specialised one
+  bool bulk2 = !off("PSMF_BULK2");                       // streaming cross-Gram / apply kernels (psmf_bulk.hip)
+  bool filter3 = !off("PSMF_FILTER3"), filter4 = !off("PSMF_FILTER4"), filter6 = !off("PSMF_FILTER6"), filter7 = !off("PSMF_FILTER7");
+  bool filter6_dual = !off("PSMF_FILTER6_DUAL"), block_dual = !off("PSMF_BLOCK_DUAL");      // the two inversions side by side
+  bool block_pipe = !off("PSMF_BLOCK_PIPE");             // =0: blocks one after the other
+  bool block_chain = !off("PSMF_BLOCK_CHAIN");           // =0: one filter launch per block
+  bool block_flags = !off("PSMF_BLOCK_FLAGS");           // =0: event hand-off instead of device flags
+  int reserved_cus = as_int("PSMF_RESERVED_CUS", 8);     // CUs that the filter chain's stream owns
+  int bulk_wgs_env = as_int("PSMF_BULK_WGS", 0);         // workgroups of the streaming bulk kernels (8..256, rounded down to a multiple of 8 where it is used)
+  bool host_comm_flags = on("PSMF_HOST_COMM_FLAGS");     // device-flag hand-off (and chained filter launches) under a host-mediated communicator too
+  bool force_collective = set("PSMF_FORCE_COLLECTIVE");  // the RCCL path with one rank
+  // per-step engine
+  bool step_persistent = !off("PSMF_STEP_PERSISTENT");   // one persistent launch per run (psmf_pstep.hip) where it applies; =0: two launches per timestep
+  bool pstep_big = !off("PSMF_PSTEP_BIG");               // =0: the persistent kernel for r <= 32 only
+  bool pstep_prof = set("PSMF_PSTEP_PROF");              // diagnostic (-DPSTEP_PROF builds): per-phase clock sums, printed at psmf_destroy
+  bool wave_solve = !off("PSMF_STEP_WAVE_SOLVE"), wave_big = !off("PSMF_STEP_WAVE_BIG");      // =0: LDS-and-barrier sweeps in the solve block, for every r / for r > 32
+  bool step_dual = !off("PSMF_STEP_DUAL"), serial_wide = !off("PSMF_SERIAL_WIDE"), wgram_mfma = !off("PSMF_WGRAM_MFMA");
+  int sweep_threads = as_int("PSMF_SWEEP_THREADS", 512) == 256 ? 256 : 512;
+  int tail_reduce = as_int("PSMF_TAIL_REDUCE", -1);      // 0 | 1: the serial stage / the last row workgroup sums the partial rows (unset: by shape)
+  // Newton-Schulz starts of the inversions; the *_set ones have defaults that depend on the handle (fill_step_params, update_ns_policy)
+  bool ns = !off("PSMF_NS");                             // =0: direct sweeps only
+  int ns_predict = as_int("PSMF_NS_PREDICT", 7);         // bits: 1 a / b (phase F), 2 core (wave 7), 4 applied
+  bool ns_tol_set = set("PSMF_NS_TOL"); double ns_tol = as_double("PSMF_NS_TOL", 0.0);      // diagnostic: acceptance tolerance
+  bool ns_far_set = set("PSMF_NS_FAR"); double ns_far = as_double("PSMF_NS_FAR", 0.3);      // diagnostic: residual at which a start is given up
+  bool ns_skip_set = set("PSMF_NS_SKIP"); int ns_skip = as_int("PSMF_NS_SKIP", 3);          // diagnostic: timesteps that then sweep unasked
+  double ns_far4 = as_double("PSMF_NS_FAR4", 0.6);       // filter4 / filter4s: their give-up residual (PSMF_NS_FAR, when set, rules both)
+  // small-shape masked engine (psmf_impute.hip)
+  bool impute_v3 = !off("PSMF_IMPUTE_V3"), impute_par = !off("PSMF_IMPUTE_PAR");      // =0: round 2's loop for the small shapes too; inversions one after the other
+  // diagnostics
+  bool dbg_breakdown = set("PSMF_DBG_BREAKDOWN");        // psmf_counters prints the in-situ breakdown of a filter3 launch
+  bool host_timing = on("PSMF_HOST_TIMING");             // report slow host-side enqueues and waits
+  int copy_grid = as_int("PSMF_COPY_GRID", 0);           // grid of the copy-bandwidth probe (0, unset: sized from the buffer)
 };
 
 struct psmf_filter {
@@ -117,7 +139,6 @@ struct psmf_filter {
   int block_steps = 0;         // B = RB - r
   bool q_iso = false;          // Q = q I with q > 0 as last uploaded (two-group block filter applies)
   double q_last = 0.0, p_diag_max = 0.0;      // Q[0][0] and max_i P[i][i] as last uploaded: the give-up policy of the Newton-Schulz starts (update_ns_policy)
-  bool ns_far_env = false, ns_skip_env = false;
   double* Kpart = nullptr;
   double* Kmat = nullptr;
   double* Acoef = nullptr;     // 2 x RB x RM   (ping-pong across pipelined blocks)
@@ -182,6 +203,15 @@ int fail(psmf_handle h, int code, const std::string& msg) {
 
 int next_pow2(int x) { int p = 1; while (p < x) p <<= 1; return p; }
 
+// The one dispatch on the storage type: f(T()) with T = double or float (the argument only carries the type: decltype(t)).
+template <typename F>
+auto by_storage(const psmf_filter* h, F&& f) { return h->cfg.storage == PSMF_F64 ? f(double()) : f(float()); }
+
+// A kernel whose dynamic LDS may need the opt-in (hipFuncAttributeMaxDynamicSharedMemorySize): psmf_create sets it for the
+// kernels the handle can launch (opt_in_lds), on the handle's device; the launchers only launch.
+template <typename Fn>
+struct LdsKernel { Fn fn; int threads; size_t lds; };
+
 // Completion waits by polling: hipStreamSynchronize / hipEventSynchronize fall back to an interrupt wait that, on this
 // stack, now and then returns ~70 ms after the work is done (seen as wall time without matching event time).
 hipError_t spin_stream(hipStream_t s) {
@@ -238,9 +268,7 @@ sweep_fn_t sweep_for_gs(int gs) {
 // per-workgroup partial rows the serial stage has to read at the same number of waves per CU
 sweep_fn_t sweep_kernel(const psmf_filter* h) {
   const int gs = h->geo.gs;
-  if (h->geo.nt == 512)
-    return h->cfg.storage == PSMF_F64 ? sweep_for_gs<double, 512>(gs) : sweep_for_gs<float, 512>(gs);
-  return h->cfg.storage == PSMF_F64 ? sweep_for_gs<double, 256>(gs) : sweep_for_gs<float, 256>(gs);
+  return by_storage(h, [&](auto t) { return h->geo.nt == 512 ? sweep_for_gs<decltype(t), 512>(gs) : sweep_for_gs<decltype(t), 256>(gs); });
 }
 
 bool serial_wide(const psmf_filter* h) { return h->geo.rpad >= 64 && h->sw.serial_wide; }
@@ -299,10 +327,7 @@ void fill_block_params(psmf_filter* h, psmf::BlockParams& b, int64_t k0, int nb,
 
 void launch_blk_gram(psmf_filter* h, const psmf::BlockParams& b, hipStream_t stream = nullptr) {
   if (!stream) stream = h->stream;
-  if (h->cfg.storage == PSMF_F64)
-    hipLaunchKernelGGL(psmf::psmf_blk_gram_mfma<double>, dim3(psmf::BLK_GRAM_WG), dim3(psmf::WG), 0, stream, b);
-  else
-    hipLaunchKernelGGL(psmf::psmf_blk_gram_mfma<float>, dim3(psmf::BLK_GRAM_WG), dim3(psmf::WG), 0, stream, b);
+  by_storage(h, [&](auto t) { hipLaunchKernelGGL(psmf::psmf_blk_gram_mfma<decltype(t)>, dim3(psmf::BLK_GRAM_WG), dim3(psmf::WG), 0, stream, b); });
   hipLaunchKernelGGL(psmf::psmf_blk_reduce, dim3(psmf::RB * psmf::RB / 128), dim3(128), 0, stream, b, (int)psmf::BLK_GRAM_WG);
 }
 
@@ -325,10 +350,7 @@ void launch_blk_xgram(psmf_filter* h, const psmf::BlockParams& x, double* xg, hi
     }
     return;
   }
-  if (h->cfg.storage == PSMF_F64)
-    hipLaunchKernelGGL(psmf::psmf_blk_xgram_mfma<double>, dim3(psmf::BLK_GRAM_WG), dim3(psmf::WG), 0, stream, x);
-  else
-    hipLaunchKernelGGL(psmf::psmf_blk_xgram_mfma<float>, dim3(psmf::BLK_GRAM_WG), dim3(psmf::WG), 0, stream, x);
+  by_storage(h, [&](auto t) { hipLaunchKernelGGL(psmf::psmf_blk_xgram_mfma<decltype(t)>, dim3(psmf::BLK_GRAM_WG), dim3(psmf::WG), 0, stream, x); });
   hipLaunchKernelGGL(psmf::psmf_blk_xreduce, dim3((int)(xg_elems / 128)), dim3(128), 0, stream, x, xg, (int)psmf::BLK_GRAM_WG);
 }
 
@@ -456,10 +478,7 @@ void launch_blk_apply(psmf_filter* h, const psmf::BlockParams& b, hipStream_t st
   int g = (nslab + 3) / 4;
   if (g > 1024) g = 1024;
   const size_t lds = psmf::blk_apply_lds_bytes();
-  if (h->cfg.storage == PSMF_F64)
-    hipLaunchKernelGGL(psmf::psmf_blk_apply_mfma<double>, dim3(g), dim3(psmf::WG), lds, stream, b);
-  else
-    hipLaunchKernelGGL(psmf::psmf_blk_apply_mfma<float>, dim3(g), dim3(psmf::WG), lds, stream, b);
+  by_storage(h, [&](auto t) { hipLaunchKernelGGL(psmf::psmf_blk_apply_mfma<decltype(t)>, dim3(g), dim3(psmf::WG), lds, stream, b); });
 }
 
 int enqueue_block(psmf_filter* h, int64_t k0, int nb) {
@@ -482,11 +501,10 @@ double host_now_ms() {
   using namespace std::chrono;
   return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
 }
-const bool g_host_timing = getenv("PSMF_HOST_TIMING") && atoi(getenv("PSMF_HOST_TIMING")) != 0;
 
 int enqueue_blocks_pipelined(psmf_filter* h, int64_t k_begin, int64_t k_end) {
   const int B = h->block_steps;
-  const double t_enq0 = g_host_timing ? host_now_ms() : 0.0;
+  const double t_enq0 = h->sw.host_timing ? host_now_ms() : 0.0;
   double t_prev = t_enq0, t_worst = 0.0;
   long long worst_blk = -1;
   const int64_t nblk = (k_end - k_begin + B - 1) / B;
@@ -573,9 +591,9 @@ int enqueue_blocks_pipelined(psmf_filter* h, int64_t k_begin, int64_t k_end) {
     // bulk: apply of block bi
     launch_blk_apply(h, b, h->bulk);
     HIP_TRY(h, hipEventRecord(h->evA[bi & 3], h->bulk));
-    if (g_host_timing) { const double t = host_now_ms(); if (t - t_prev > t_worst) { t_worst = t - t_prev; worst_blk = bi; } t_prev = t; }
+    if (h->sw.host_timing) { const double t = host_now_ms(); if (t - t_prev > t_worst) { t_worst = t - t_prev; worst_blk = bi; } t_prev = t; }
   }
-  if (g_host_timing) {
+  if (h->sw.host_timing) {
     const double t = host_now_ms();
     if (t - t_enq0 > 20.0 || t_worst > 5.0)
       fprintf(stderr, "[psmf host timing] enqueue of %lld blocks took %.1f ms, slowest block's calls %.1f ms (block %lld)\n", (long long)nblk, t - t_enq0, t_worst, worst_blk);
@@ -591,12 +609,10 @@ int enqueue_blocks_pipelined(psmf_filter* h, int64_t k_begin, int64_t k_end) {
 int enqueue_gram_into(psmf_filter* h, double* Gout, const DevState* wst, const double* rho_rows) {
   const int r = h->cfg.r;
   const int rows = (h->cfg.d_local + kGramWG - 1) / kGramWG;
-  if (h->cfg.storage == PSMF_F64)
-    hipLaunchKernelGGL(psmf::psmf_gram_partial<double>, dim3(kGramWG), dim3(psmf::WG), 0, h->stream,
-                       (const double*)h->C, h->cfg.d_local, r, h->geo.rp, rows, h->gpart, wst, rho_rows);
-  else
-    hipLaunchKernelGGL(psmf::psmf_gram_partial<float>, dim3(kGramWG), dim3(psmf::WG), 0, h->stream,
-                       (const float*)h->C, h->cfg.d_local, r, h->geo.rp, rows, h->gpart, wst, rho_rows);
+  by_storage(h, [&](auto t) {
+    hipLaunchKernelGGL(psmf::psmf_gram_partial<decltype(t)>, dim3(kGramWG), dim3(psmf::WG), 0, h->stream,
+                       (const decltype(t)*)h->C, h->cfg.d_local, r, h->geo.rp, rows, h->gpart, wst, rho_rows);
+  });
   hipLaunchKernelGGL(psmf::psmf_gram_reduce, dim3((r * r + 255) / 256), dim3(256), 0, h->stream,
                      (const double*)h->gpart, kGramWG, r * r, Gout);
   if (h->use_coll) { const int rc = all_reduce_sum(h, Gout, (size_t)r * r, h->stream); if (rc) return rc; }
@@ -605,33 +621,23 @@ int enqueue_gram_into(psmf_filter* h, double* Gout, const DevState* wst, const d
 constexpr int kMGramWG = 256;      // workgroups of the masked Gram (one partial each)
 
 // psmf_serial_mgram: block 0 = the serial stage, blocks 1 .. kMGramWG = the masked Gram of the next step (psmf_masked.hip)
+typedef LdsKernel<void (*)(StepParams, int, double*)> serial_mgram_t;
+template <int RPAD, typename T, int NT, int NW>
+serial_mgram_t serial_mgram_inst() { return {psmf::psmf_serial_mgram<RPAD, T, NT, NW>, NW * 64, (size_t)psmf::mgram_lds_doubles(NT, NW) * sizeof(double)}; }
+
 template <typename T>
-int launch_serial_mgram_t(psmf_filter* h, int first) {
-  const int r = h->cfg.r, rpad = h->geo.rpad;
-  const dim3 grid(1 + kMGramWG);
-#define PSMF_SM_LAUNCH(RPAD_, NT_, NW_)                                                                                     \
-  do {                                                                                                                      \
-    const size_t lds_ = (size_t)psmf::mgram_lds_doubles(NT_, NW_) * sizeof(double);                                         \
-    static bool attr_[2] = {false, false};                                                                                  \
-    if (!attr_[sizeof(T) == 8]) {                                                                                           \
-      HIP_TRY(h, hipFuncSetAttribute((const void*)psmf::psmf_serial_mgram<RPAD_, T, NT_, NW_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_)); \
-      attr_[sizeof(T) == 8] = true;                                                                                         \
-    }                                                                                                                       \
-    hipLaunchKernelGGL((psmf::psmf_serial_mgram<RPAD_, T, NT_, NW_>), grid, dim3(NW_ * 64), lds_, h->stream, h->sp, first, h->gpart); \
-  } while (0)
-  if (rpad == 8) PSMF_SM_LAUNCH(8, 1, 16);
-  else if (rpad == 16) PSMF_SM_LAUNCH(16, 1, 16);
-  else if (rpad == 32) PSMF_SM_LAUNCH(32, 2, 8);
-  else if (r <= 48) PSMF_SM_LAUNCH(64, 3, 4);
-  else PSMF_SM_LAUNCH(64, 4, 4);
-#undef PSMF_SM_LAUNCH
-  return PSMF_OK;
+serial_mgram_t serial_mgram_for(int rpad, int r) {
+  if (rpad == 8) return serial_mgram_inst<8, T, 1, 16>();
+  if (rpad == 16) return serial_mgram_inst<16, T, 1, 16>();
+  if (rpad == 32) return serial_mgram_inst<32, T, 2, 8>();
+  return r <= 48 ? serial_mgram_inst<64, T, 3, 4>() : serial_mgram_inst<64, T, 4, 4>();
 }
+serial_mgram_t serial_mgram_kernel(const psmf_filter* h) { return by_storage(h, [&](auto t) { return serial_mgram_for<decltype(t)>(h->geo.rpad, h->cfg.r); }); }
 
 // serial stage of the step + masked Gram of the next, then the Gram's fixed-order reduction (and its all-reduce over the shards)
 int enqueue_serial_mgram(psmf_filter* h, int first) {
-  int rc = h->cfg.storage == PSMF_F64 ? launch_serial_mgram_t<double>(h, first) : launch_serial_mgram_t<float>(h, first);
-  if (rc) return rc;
+  const serial_mgram_t k = serial_mgram_kernel(h);
+  hipLaunchKernelGGL(k.fn, dim3(1 + kMGramWG), dim3(k.threads), k.lds, h->stream, h->sp, first, h->gpart);
   const int ne = h->cfg.r * h->cfg.r + 1;
   // the shares of <G_m, Pbar> for the next sweep's eta: by the reduction itself, or -- row shards -- behind the all-reduce of the Gram
   const int ntr = (ne + 63) / 64;
@@ -649,32 +655,23 @@ int enqueue_serial_mgram(psmf_filter* h, int first) {
 int enqueue_gram(psmf_filter* h) { return enqueue_gram_into(h, h->st->G, nullptr, nullptr); }
 
 // the weighted Gram of the current step (non-uniform diagonal R) on the matrix cores: psmf_wgram_mfma + the masked Gram's reduction
+typedef LdsKernel<void (*)(StepParams, double*)> wgram_t;
+template <typename T, int NT>
+wgram_t wgram_inst() { return {psmf::psmf_wgram_mfma<T, NT, 8>, 8 * 64, (size_t)psmf::mgram_lds_doubles(NT, 8) * sizeof(double)}; }
+
 template <typename T>
-int launch_wgram_t(psmf_filter* h) {
-  const int r = h->cfg.r, rpad = h->geo.rpad;
-#define PSMF_WG_LAUNCH(NT_)                                                                                                 \
-  do {                                                                                                                      \
-    const size_t lds_ = (size_t)psmf::mgram_lds_doubles(NT_, 8) * sizeof(double);                                           \
-    static bool attr_[2] = {false, false};                                                                                  \
-    if (!attr_[sizeof(T) == 8]) {                                                                                           \
-      HIP_TRY(h, hipFuncSetAttribute((const void*)psmf::psmf_wgram_mfma<T, NT_, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_)); \
-      attr_[sizeof(T) == 8] = true;                                                                                         \
-    }                                                                                                                       \
-    hipLaunchKernelGGL((psmf::psmf_wgram_mfma<T, NT_, 8>), dim3(kMGramWG), dim3(8 * 64), lds_, h->stream, h->sp, h->gpart);  \
-  } while (0)
-  if (rpad <= 16) PSMF_WG_LAUNCH(1);
-  else if (rpad == 32) PSMF_WG_LAUNCH(2);
-  else if (r <= 48) PSMF_WG_LAUNCH(3);
-  else PSMF_WG_LAUNCH(4);
-#undef PSMF_WG_LAUNCH
-  return PSMF_OK;
+wgram_t wgram_for(int rpad, int r) {
+  if (rpad <= 16) return wgram_inst<T, 1>();
+  if (rpad == 32) return wgram_inst<T, 2>();
+  return r <= 48 ? wgram_inst<T, 3>() : wgram_inst<T, 4>();
 }
+wgram_t wgram_kernel(const psmf_filter* h) { return by_storage(h, [&](auto t) { return wgram_for<decltype(t)>(h->geo.rpad, h->cfg.r); }); }
 
 int enqueue_weighted_gram(psmf_filter* h) {
   if (!h->sw.wgram_mfma) return enqueue_gram_into(h, h->st->GR, h->st, h->sp.rho_rows);      // PSMF_WGRAM_MFMA=0: the vector-unit Gram
   const int r = h->cfg.r;
-  const int rc = h->cfg.storage == PSMF_F64 ? launch_wgram_t<double>(h) : launch_wgram_t<float>(h);
-  if (rc) return rc;
+  const wgram_t k = wgram_kernel(h);
+  hipLaunchKernelGGL(k.fn, dim3(kMGramWG), dim3(k.threads), k.lds, h->stream, h->sp, h->gpart);
   hipLaunchKernelGGL(psmf::psmf_mgram_reduce, dim3((r * r + 63) / 64), dim3(512), 0, h->stream, (const double*)h->gpart, (int)kMGramWG, r * r,
                      h->st->GR, (const double*)nullptr, r, (double*)nullptr);
   if (h->use_coll) { const int rc2 = all_reduce_sum(h, h->st->GR, (size_t)r * r, h->stream); if (rc2) return rc2; }
@@ -738,16 +735,14 @@ int rot_gemm(psmf_filter* h, const TA* A, long long a_i, long long a_k, const TB
 int rot_rows(psmf_filter* h, const void* src, void* dst, long long n, bool fwd) {
   const long long d = h->cfg.d_local;
   const long long bk = fwd ? d : 1, bj = fwd ? 1 : d;
-  if (h->cfg.storage == PSMF_F64) return rot_gemm(h, (const double*)src, d, 1LL, (const double*)h->rotU, bk, bj, (double*)dst, d, n, d, d);
-  return rot_gemm(h, (const float*)src, d, 1LL, (const double*)h->rotU, bk, bj, (float*)dst, d, n, d, d);
+  return by_storage(h, [&](auto t) { return rot_gemm(h, (const decltype(t)*)src, d, 1LL, (const double*)h->rotU, bk, bj, (decltype(t)*)dst, d, n, d, d); });
 }
 
 // the dictionary (d x rp, storage type): dst = U^T src (fwd) or U src (back)
 int rot_dict(psmf_filter* h, const void* src, void* dst, bool fwd) {
   const long long d = h->cfg.d_local, rp = h->geo.rp, r = h->cfg.r;
   const long long ai = fwd ? 1 : d, ak = fwd ? d : 1;
-  if (h->cfg.storage == PSMF_F64) return rot_gemm(h, (const double*)h->rotU, ai, ak, (const double*)src, rp, 1LL, (double*)dst, rp, d, r, d);
-  return rot_gemm(h, (const double*)h->rotU, ai, ak, (const float*)src, rp, 1LL, (float*)dst, rp, d, r, d);
+  return by_storage(h, [&](auto t) { return rot_gemm(h, (const double*)h->rotU, ai, ak, (const decltype(t)*)src, rp, 1LL, (decltype(t)*)dst, rp, d, r, d); });
 }
 
 void compute_geometry(const psmf_config& c, Geometry& g, const int sweep_nt = 512) {
@@ -843,8 +838,8 @@ int launch_pstep(psmf_filter* h, int64_t k_begin, int64_t n) {
 // PSMF_NS_FAR / PSMF_NS_SKIP override both.
 void update_ns_policy(psmf_filter* h) {
   const bool benign = h->q_iso && h->q_last > 0.0 && h->p_diag_max <= 1e3 * h->q_last;
-  if (!h->ns_far_env) { const double f = benign ? 0.9 : 0.3; h->sp.ns_far2 = f * f; }
-  if (!h->ns_skip_env) h->sp.ns_skip_n = benign ? 1 : 3;
+  if (!h->sw.ns_far_set) { const double f = benign ? 0.9 : 0.3; h->sp.ns_far2 = f * f; }
+  if (!h->sw.ns_skip_set) h->sp.ns_skip_n = benign ? 1 : 3;
 }
 
 int set_device(psmf_handle h) {
@@ -918,205 +913,183 @@ void dyn_f_host(const psmf_config& c, const double* th, const double* x, double 
   }
 }
 
-}  // namespace
-
-extern "C" {
-
-int psmf_device_count(void) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-  return n;
+// psmf_create in stages, in the order it calls them.  The argument checks: the message of the first one that fails, or null
+const char* check_config(const psmf_config* cfg) {
+  if (cfg->abi_version != PSMF_ABI_VERSION) return "psmf_create: ABI version mismatch";
+  if (cfg->r < 1 || cfg->r > PSMF_RMAX) return "psmf_create: need 1 <= r <= 64";
+  if (cfg->d < 1 || cfg->d_local < 1 || cfg->row0 < 0 || cfg->row0 + cfg->d_local > cfg->d) return "psmf_create: bad d / row0 / d_local";
+  if (cfg->storage != PSMF_F32 && cfg->storage != PSMF_F64) return "psmf_create: storage must be f32 or f64";
+  if (cfg->dyn_kind < PSMF_DYN_RANDOM_WALK || cfg->dyn_kind > PSMF_DYN_HOST) return "psmf_create: unknown dyn_kind";
+  if (cfg->dyn_kind == PSMF_DYN_FOURIER && (cfg->dyn_terms < 1 || 2 * cfg->dyn_terms > psmf::DYN_MAX_TERMS)) return "psmf_create: Fourier dynamics need 1 <= dyn_terms <= 4";
+  if (cfg->n_theta != psmf::dyn_n_theta(cfg->dyn_kind, cfg->dyn_flags, cfg->dyn_terms, cfg->r)) return "psmf_create: n_theta does not match dyn_kind / dyn_flags / dyn_terms (see psmf_dyn_kind)";
+  if (cfg->dyn_kind == PSMF_DYN_HOST && cfg->recursive) return "psmf_create: host-stepped dynamics keep theta (and its optimiser) on the host";
+  if (cfg->recursive && cfg->update_every < 1) return "psmf_create: update_every must be >= 1";
+  if (cfg->recursive < 0 || cfg->recursive > 2) return "psmf_create: recursive must be 0, 1 (in-loop Adam) or 2 (in-loop SGD)";
+  if (cfg->masked < 0 || cfg->masked > 3) return "psmf_create: masked must be 0 .. 3";
+  if (cfg->masked >= 2 && (cfg->robust || cfg->dyn_kind != PSMF_DYN_RANDOM_WALK)) return "psmf_create: masked = 2 (MLE-SMF) / 3 (TMF) are random-walk, non-robust filters";
+  if (cfg->masked) {
+    if (cfg->dyn_kind != PSMF_DYN_RANDOM_WALK) return "psmf_create: masked handles are random-walk filters (ExperimentImpute/PSMF.py:65-66: Pbar = P + Q)";
+    if (!cfg->coef_update || !cfg->eta_full || !cfg->pbar_predict || cfg->nonuniform_R || cfg->engine == 2 || !cfg->store_y_pred)
+      return "psmf_create: masked = 1 needs the full filter (coef_update, eta_full, pbar_predict), a uniform diagonal R, "
+             "store_y_pred = 1 and the per-step engine";
+  }
+  return nullptr;
 }
 
-const char* psmf_last_error(psmf_handle h) { return h ? h->err.c_str() : g_create_error.c_str(); }
+int choose_engine(psmf_filter* h) {
+  const psmf_config* cfg = &h->cfg;
+  const bool can_block = cfg->r <= psmf::RM / 2 && cfg->dyn_kind != PSMF_DYN_HOST && !cfg->nonuniform_R && !cfg->masked;
+  if (cfg->engine == 2 && !can_block) return fail(h, PSMF_ERR_ARG, "psmf_create: the blocked engine needs r <= 32, device-evaluated dynamics and a uniform diagonal R");
+  if (cfg->engine < 0 || cfg->engine > 2) return fail(h, PSMF_ERR_ARG, "psmf_create: engine must be 0 (auto), 1 (per-step) or 2 (blocked)");
+  // auto: blocked whenever it applies -- it is exact and removes the per-step launches and row sweeps
+  h->engine = cfg->engine == 0 ? (can_block ? 2 : 1) : cfg->engine;
+  { const int v = h->sw.engine_env; if (v == 1 || (v == 2 && can_block)) h->engine = v; }
+  // (scaled-walk / sinusoid / Fourier dynamics on the per-step engine -- r > 32, a non-uniform R, engine = 1: the launched form's
+  //  serial stage evaluates them through psmf_dyn.hip like the blocked engine's general kernel)
+  return PSMF_OK;
+}
 
-int psmf_create(psmf_handle* out, const psmf_config* cfg) {
-  if (!out || !cfg) return fail(nullptr, PSMF_ERR_ARG, "psmf_create: null argument");
-  *out = nullptr;
-  if (cfg->abi_version != PSMF_ABI_VERSION) return fail(nullptr, PSMF_ERR_ARG, "psmf_create: ABI version mismatch");
-  if (cfg->r < 1 || cfg->r > PSMF_RMAX) return fail(nullptr, PSMF_ERR_ARG, "psmf_create: need 1 <= r <= 64");
-  if (cfg->d < 1 || cfg->d_local < 1 || cfg->row0 < 0 || cfg->row0 + cfg->d_local > cfg->d)
-    return fail(nullptr, PSMF_ERR_ARG, "psmf_create: bad d / row0 / d_local");
-  if (cfg->storage != PSMF_F32 && cfg->storage != PSMF_F64) return fail(nullptr, PSMF_ERR_ARG, "psmf_create: storage must be f32 or f64");
-  if (cfg->dyn_kind < PSMF_DYN_RANDOM_WALK || cfg->dyn_kind > PSMF_DYN_HOST) return fail(nullptr, PSMF_ERR_ARG, "psmf_create: unknown dyn_kind");
-  if (cfg->dyn_kind == PSMF_DYN_FOURIER && (cfg->dyn_terms < 1 || 2 * cfg->dyn_terms > psmf::DYN_MAX_TERMS))
-    return fail(nullptr, PSMF_ERR_ARG, "psmf_create: Fourier dynamics need 1 <= dyn_terms <= 4");
-  if (cfg->n_theta != psmf::dyn_n_theta(cfg->dyn_kind, cfg->dyn_flags, cfg->dyn_terms, cfg->r))
-    return fail(nullptr, PSMF_ERR_ARG, "psmf_create: n_theta does not match dyn_kind / dyn_flags / dyn_terms (see psmf_dyn_kind)");
-  if (cfg->dyn_kind == PSMF_DYN_HOST && cfg->recursive) return fail(nullptr, PSMF_ERR_ARG, "psmf_create: host-stepped dynamics keep theta (and its optimiser) on the host");
-  if (cfg->recursive && cfg->update_every < 1) return fail(nullptr, PSMF_ERR_ARG, "psmf_create: update_every must be >= 1");
-  if (cfg->recursive < 0 || cfg->recursive > 2) return fail(nullptr, PSMF_ERR_ARG, "psmf_create: recursive must be 0, 1 (in-loop Adam) or 2 (in-loop SGD)");
-  if (cfg->masked < 0 || cfg->masked > 3) return fail(nullptr, PSMF_ERR_ARG, "psmf_create: masked must be 0 .. 3");
-  if (cfg->masked >= 2 && (cfg->robust || cfg->dyn_kind != PSMF_DYN_RANDOM_WALK))
-    return fail(nullptr, PSMF_ERR_ARG, "psmf_create: masked = 2 (MLE-SMF) / 3 (TMF) are random-walk, non-robust filters");
-  if (cfg->masked) {
-    if (cfg->dyn_kind != PSMF_DYN_RANDOM_WALK)
-      return fail(nullptr, PSMF_ERR_ARG, "psmf_create: masked handles are random-walk filters (ExperimentImpute/PSMF.py:65-66: Pbar = P + Q)");
-    if (!cfg->coef_update || !cfg->eta_full || !cfg->pbar_predict || cfg->nonuniform_R || cfg->engine == 2 || !cfg->store_y_pred)
-      return fail(nullptr, PSMF_ERR_ARG, "psmf_create: masked = 1 needs the full filter (coef_update, eta_full, pbar_predict), a uniform diagonal R, "
-                                         "store_y_pred = 1 and the per-step engine");
-  }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-    return fail(nullptr, PSMF_ERR_NO_DEVICE, "psmf_create: no HIP device visible (the MI355X path has no CPU fallback)");
-  if (cfg->device < 0 || cfg->device >= ndev) return fail(nullptr, PSMF_ERR_ARG, "psmf_create: bad device ordinal");
-
-  psmf_filter* h = new psmf_filter();
-  h->cfg = *cfg;
-  h->sw.read();
-  compute_geometry(h->cfg, h->geo, h->sw.sweep_threads);
-  auto bail = [&](int code) { g_create_error = h->err; psmf_destroy(h); return code; };
-#define CREATE_TRY(expr)                                                                  \
-  do {                                                                                    \
-    hipError_t e_ = (expr);                                                               \
-    if (e_ != hipSuccess) { h->err = std::string(#expr) + ": " + hipGetErrorString(e_); return bail(PSMF_ERR_HIP); } \
-  } while (0)
-  CREATE_TRY(hipSetDevice(cfg->device));
-  CREATE_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-  CREATE_TRY(hipEventCreate(&h->ev0));
-  CREATE_TRY(hipEventCreate(&h->ev1));
-  CREATE_TRY(hipHostMalloc((void**)&h->err_host, sizeof(int), hipHostMallocMapped));
-  CREATE_TRY(hipHostGetDevicePointer((void**)&h->err_host_dev, h->err_host, 0));
-  CREATE_TRY(hipMalloc((void**)&h->st, sizeof(DevState)));
-  CREATE_TRY(hipMemset(h->st, 0, sizeof(DevState)));
-  CREATE_TRY(hipMalloc(&h->C, (size_t)cfg->d_local * h->geo.rp * h->elem()));
-  CREATE_TRY(hipMalloc((void**)&h->partials, (size_t)h->geo.n_sweep_wg * h->geo.ps * sizeof(double)));
-  CREATE_TRY(hipMalloc((void**)&h->gpart, (size_t)((cfg->masked || cfg->nonuniform_R) ? 256 : kGramWG) * (cfg->r * cfg->r + 1) * sizeof(double)));
-  if (cfg->masked) CREATE_TRY(hipMalloc((void**)&h->mg, (size_t)(cfg->r * cfg->r + 2 + (cfg->r * cfg->r + 64) / 64 + 1) * sizeof(double)));     // Gram, count | trace shares
-  {
-    const bool can_block = cfg->r <= psmf::RM / 2 && cfg->dyn_kind != PSMF_DYN_HOST && !cfg->nonuniform_R && !cfg->masked;
-    if (cfg->engine == 2 && !can_block) { h->err = "psmf_create: the blocked engine needs r <= 32, device-evaluated dynamics and a uniform diagonal R"; return bail(PSMF_ERR_ARG); }
-    if (cfg->engine < 0 || cfg->engine > 2) { h->err = "psmf_create: engine must be 0 (auto), 1 (per-step) or 2 (blocked)"; return bail(PSMF_ERR_ARG); }
-    // auto: blocked whenever it applies -- it is exact and removes the per-step launches and row sweeps
-    h->engine = cfg->engine == 0 ? (can_block ? 2 : 1) : cfg->engine;
-    if (const char* e = getenv("PSMF_ENGINE")) { const int v = atoi(e); if (v == 1 || (v == 2 && can_block)) h->engine = v; }
-    // (scaled-walk / sinusoid / Fourier dynamics on the per-step engine -- r > 32, a non-uniform R, engine = 1: the launched form's
-    //  serial stage evaluates them through psmf_dyn.hip like the blocked engine's general kernel)
-  }
+// the device, the handle's stream and events, and the buffers of every engine
+int alloc_common(psmf_filter* h) {
+  const psmf_config* cfg = &h->cfg;
+  HIP_TRY(h, hipSetDevice(cfg->device));
+  HIP_TRY(h, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+  HIP_TRY(h, hipEventCreate(&h->ev0));
+  HIP_TRY(h, hipEventCreate(&h->ev1));
+  HIP_TRY(h, hipHostMalloc((void**)&h->err_host, sizeof(int), hipHostMallocMapped));
+  HIP_TRY(h, hipHostGetDevicePointer((void**)&h->err_host_dev, h->err_host, 0));
+  HIP_TRY(h, hipMalloc((void**)&h->st, sizeof(DevState)));
+  HIP_TRY(h, hipMemset(h->st, 0, sizeof(DevState)));
+  HIP_TRY(h, hipMalloc(&h->C, (size_t)cfg->d_local * h->geo.rp * h->elem()));
+  HIP_TRY(h, hipMalloc((void**)&h->partials, (size_t)h->geo.n_sweep_wg * h->geo.ps * sizeof(double)));
+  HIP_TRY(h, hipMalloc((void**)&h->gpart, (size_t)((cfg->masked || cfg->nonuniform_R) ? 256 : kGramWG) * (cfg->r * cfg->r + 1) * sizeof(double)));
+  if (cfg->masked) HIP_TRY(h, hipMalloc((void**)&h->mg, (size_t)(cfg->r * cfg->r + 2 + (cfg->r * cfg->r + 64) / 64 + 1) * sizeof(double)));     // Gram, count | trace shares
   h->th_cap = (size_t)(cfg->n_theta > psmf::RM ? cfg->n_theta : psmf::RM);
-  CREATE_TRY(hipMalloc((void**)&h->thbuf, 4 * h->th_cap * sizeof(double)));
-  CREATE_TRY(hipMemset(h->thbuf, 0, 4 * h->th_cap * sizeof(double)));
-  if (h->engine == 2) {
-    // B = 64 - r timesteps per block, at most 48: the role-specialised filter kernel and the streaming bulk kernels stage
-    // up to three 16-column tiles of a series block (r < 16 would otherwise give blocks of 49..63)
-    h->block_steps = psmf::RB - cfg->r < 48 ? psmf::RB - cfg->r : 48;
-    CREATE_TRY(hipMalloc((void**)&h->Kpart, (size_t)psmf::BLK_GRAM_WG * psmf::RB * psmf::RB * sizeof(double)));
-    CREATE_TRY(hipMalloc((void**)&h->Kmat, (size_t)psmf::RB * psmf::RB * sizeof(double)));
-    CREATE_TRY(hipMalloc((void**)&h->Acoef, (size_t)2 * psmf::RB * psmf::RM * sizeof(double)));
-    CREATE_TRY(hipMalloc((void**)&h->Bcoef, (size_t)2 * psmf::RB * psmf::RB * sizeof(double)));
-    CREATE_TRY(hipMemset(h->Bcoef, 0, (size_t)2 * psmf::RB * psmf::RB * sizeof(double)));
-    CREATE_TRY(hipMalloc((void**)&h->XGpart, (size_t)psmf::BLK_GRAM_WG * (psmf::RB + psmf::XGB) * psmf::XGB * sizeof(double)));
-    CREATE_TRY(hipMalloc((void**)&h->XG, (size_t)2 * (psmf::RB + psmf::XGB) * psmf::XGB * sizeof(double)));
-    CREATE_TRY(hipMemset(h->XG, 0, (size_t)2 * (psmf::RB + psmf::XGB) * psmf::XGB * sizeof(double)));   // the all-reduce covers entries no kernel writes
-    CREATE_TRY(hipMalloc((void**)&h->flags, 8 * sizeof(long long)));
-    CREATE_TRY(hipMemset(h->flags, 0, 8 * sizeof(long long)));
-    {
-      // The filter chain is one workgroup on the critical path; the bulk kernels (cross-Gram, apply) run
-      // beside it and would be co-scheduled onto its CU, stretching it by 10-17 % (measured).  Partition the
-      // chip with CU masks: the filter's stream owns `nres` CUs, the bulk stream the others.
-      int nres = 8;
-      if (const char* e = getenv("PSMF_RESERVED_CUS")) nres = atoi(e);
-      hipDeviceProp_t prop;
-      CREATE_TRY(hipGetDeviceProperties(&prop, cfg->device));
-      const int ncu = prop.multiProcessorCount;
-      const int words = (ncu + 31) / 32;
-      // The split below is written for the unpartitioned MI355X: 256 CUs = 8 XCDs x 4 shader engines x 8 CUs, mask bit =
-      // 32 cu + 8 se + xcc (tools/xcc_probe.hip).  On any other device (a CPX / NPS partition, another part) the bit layout and the
-      // engine count are not known here: no CU masks, plain streams -- the filter chain then shares CUs with the bulk kernels
-      // (10-17 % slower, measured), which is a speed matter only.
-      const bool known_layout = ncu == 256;
-      if (known_layout && nres > 0 && nres < ncu / 2 && words <= 16) {
-        uint32_t mf[16] = {0}, mb[16] = {0};
-        for (int i = 0; i < ncu; ++i) (i < nres ? mf : mb)[i >> 5] |= 1u << (i & 31);
-        hipStream_t fs = nullptr, bs = nullptr;
-        if (hipExtStreamCreateWithCUMask(&fs, words, mf) == hipSuccess && hipExtStreamCreateWithCUMask(&bs, words, mb) == hipSuccess) {
-          h->fstream = fs;
-          h->bulk = bs;
-          h->reserved_cus = nres;
-          // The streaming kernels hold one 512-thread workgroup per CU (86-131 KB of LDS), and the dispatcher deals workgroups
-          // to the 32 shader engines (8 XCDs x 4) in equal shares whatever the mask has left each of them.  The filter's
-          // 8 CUs are CU 0 of engine 0 of every XCD (mask bit = 32 cu + 8 se + xcc, tools/xcc_probe.hip): those engines
-          // keep 7 CUs, so with more than 7 workgroups per engine one CU gets a second one and the kernel takes two
-          // rounds -- 231 / 317 us per block at d = 1e6 with 248 or 256 workgroups against 138 / 193 us with 224
-          // (tools/bulk_stream.hip; 124 / 172 us on the unmasked chip).  Hence (CUs per engine - 1) x 32.
-          {
-            const int n_engines = 32, per_engine = ncu / n_engines - (nres + n_engines - 1) / n_engines;
-            h->bulk_wgs = per_engine >= 1 ? per_engine * n_engines : 8;
-            if (h->bulk_wgs > 256) h->bulk_wgs = 256;
-            if (const char* e = getenv("PSMF_BULK_WGS")) { const int v = atoi(e); if (v >= 8 && v <= 256) h->bulk_wgs = (v / 8) * 8; }
-          }
-        } else {
-          (void)hipGetLastError();
-          if (fs) hipStreamDestroy(fs);
-          if (bs) hipStreamDestroy(bs);
-        }
-      }
-      if (!h->bulk) CREATE_TRY(hipStreamCreateWithFlags(&h->bulk, hipStreamNonBlocking));
+  HIP_TRY(h, hipMalloc((void**)&h->thbuf, 4 * h->th_cap * sizeof(double)));
+  HIP_TRY(h, hipMemset(h->thbuf, 0, 4 * h->th_cap * sizeof(double)));
+  return PSMF_OK;
+}
+
+int opt_in_lds(psmf_filter* h, const void* fn, size_t bytes) {
+  HIP_TRY(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  return PSMF_OK;
+}
+
+// blocked engine: buffers, CU-masked streams, events, the concurrency probe, the LDS opt-in of its kernels
+int init_blocked(psmf_filter* h) {
+  const psmf_config* cfg = &h->cfg;
+  // B = 64 - r timesteps per block, at most 48: the role-specialised filter kernel and the streaming bulk kernels stage
+  // up to three 16-column tiles of a series block (r < 16 would otherwise give blocks of 49..63)
+  h->block_steps = psmf::RB - cfg->r < 48 ? psmf::RB - cfg->r : 48;
+  HIP_TRY(h, hipMalloc((void**)&h->Kpart, (size_t)psmf::BLK_GRAM_WG * psmf::RB * psmf::RB * sizeof(double)));
+  HIP_TRY(h, hipMalloc((void**)&h->Kmat, (size_t)psmf::RB * psmf::RB * sizeof(double)));
+  HIP_TRY(h, hipMalloc((void**)&h->Acoef, (size_t)2 * psmf::RB * psmf::RM * sizeof(double)));
+  HIP_TRY(h, hipMalloc((void**)&h->Bcoef, (size_t)2 * psmf::RB * psmf::RB * sizeof(double)));
+  HIP_TRY(h, hipMemset(h->Bcoef, 0, (size_t)2 * psmf::RB * psmf::RB * sizeof(double)));
+  HIP_TRY(h, hipMalloc((void**)&h->XGpart, (size_t)psmf::BLK_GRAM_WG * (psmf::RB + psmf::XGB) * psmf::XGB * sizeof(double)));
+  HIP_TRY(h, hipMalloc((void**)&h->XG, (size_t)2 * (psmf::RB + psmf::XGB) * psmf::XGB * sizeof(double)));
+  HIP_TRY(h, hipMemset(h->XG, 0, (size_t)2 * (psmf::RB + psmf::XGB) * psmf::XGB * sizeof(double)));   // the all-reduce covers entries no kernel writes
+  HIP_TRY(h, hipMalloc((void**)&h->flags, 8 * sizeof(long long)));
+  HIP_TRY(h, hipMemset(h->flags, 0, 8 * sizeof(long long)));
+  // The filter chain is one workgroup on the critical path; the bulk kernels (cross-Gram, apply) run
+  // beside it and would be co-scheduled onto its CU, stretching it by 10-17 % (measured).  Partition the
+  // chip with CU masks: the filter's stream owns `nres` CUs, the bulk stream the others.
+  const int nres = h->sw.reserved_cus;
+  hipDeviceProp_t prop;
+  HIP_TRY(h, hipGetDeviceProperties(&prop, cfg->device));
+  const int ncu = prop.multiProcessorCount;
+  const int words = (ncu + 31) / 32;
+  // The split below is written for the unpartitioned MI355X: 256 CUs = 8 XCDs x 4 shader engines x 8 CUs, mask bit =
+  // 32 cu + 8 se + xcc (tools/xcc_probe.hip).  On any other device (a CPX / NPS partition, another part) the bit layout and the
+  // engine count are not known here: no CU masks, plain streams -- the filter chain then shares CUs with the bulk kernels
+  // (10-17 % slower, measured), which is a speed matter only.
+  const bool known_layout = ncu == 256;
+  if (known_layout && nres > 0 && nres < ncu / 2 && words <= 16) {
+    uint32_t mf[16] = {0}, mb[16] = {0};
+    for (int i = 0; i < ncu; ++i) (i < nres ? mf : mb)[i >> 5] |= 1u << (i & 31);
+    hipStream_t fs = nullptr, bs = nullptr;
+    if (hipExtStreamCreateWithCUMask(&fs, words, mf) == hipSuccess && hipExtStreamCreateWithCUMask(&bs, words, mb) == hipSuccess) {
+      h->fstream = fs;
+      h->bulk = bs;
+      h->reserved_cus = nres;
+      // The streaming kernels hold one 512-thread workgroup per CU (86-131 KB of LDS), and the dispatcher deals workgroups
+      // to the 32 shader engines (8 XCDs x 4) in equal shares whatever the mask has left each of them.  The filter's
+      // 8 CUs are CU 0 of engine 0 of every XCD (mask bit = 32 cu + 8 se + xcc, tools/xcc_probe.hip): those engines
+      // keep 7 CUs, so with more than 7 workgroups per engine one CU gets a second one and the kernel takes two
+      // rounds -- 231 / 317 us per block at d = 1e6 with 248 or 256 workgroups against 138 / 193 us with 224
+      // (tools/bulk_stream.hip; 124 / 172 us on the unmasked chip).  Hence (CUs per engine - 1) x 32.
+      const int n_engines = 32, per_engine = ncu / n_engines - (nres + n_engines - 1) / n_engines;
+      h->bulk_wgs = per_engine >= 1 ? per_engine * n_engines : 8;
+      if (h->bulk_wgs > 256) h->bulk_wgs = 256;
+      { const int v = h->sw.bulk_wgs_env; if (v >= 8 && v <= 256) h->bulk_wgs = (v / 8) * 8; }
+    } else {
+      (void)hipGetLastError();
+      if (fs) hipStreamDestroy(fs);
+      if (bs) hipStreamDestroy(bs);
     }
-    for (int i = 0; i < 4; ++i) {
-      CREATE_TRY(hipEventCreateWithFlags(&h->evF[i], hipEventDisableTiming));
-      CREATE_TRY(hipEventCreateWithFlags(&h->evA[i], hipEventDisableTiming));
-      CREATE_TRY(hipEventCreateWithFlags(&h->evX[i], hipEventDisableTiming));
-    }
-    CREATE_TRY(hipEventCreateWithFlags(&h->evS, hipEventDisableTiming));
-    CREATE_TRY(hipEventCreateWithFlags(&h->evC, hipEventDisableTiming));
-    for (int i = 0; i < psmf_filter::kTimedRuns; ++i) { CREATE_TRY(hipEventCreate(&h->evK0[i])); CREATE_TRY(hipEventCreate(&h->evK1[i])); }
-    if (h->fstream && h->flags) {
-      // the device-flag hand-off and the chained filter launches need the two streams to run concurrently: probe it (a waiter on the filter stream, then the
-      // setter on the bulk stream; the waiter gives up after 50 ms)
-      int* dres = nullptr;
-      struct FreeOnExit { int** p; ~FreeOnExit() { if (*p) { hipFree(*p); *p = nullptr; } } } dres_guard{&dres};      // also on the CREATE_TRY failure paths below
-      CREATE_TRY(hipMalloc((void**)&dres, sizeof(int)));
-      CREATE_TRY(hipMemset(dres, 0, sizeof(int)));
-      CREATE_TRY(hipDeviceSynchronize());      // hipMemset is asynchronous on the null stream, the probe's streams are non-blocking: the zeroes (of dres and of h->flags above) first
-      hipLaunchKernelGGL(psmf::psmf_probe_wait_k, dim3(1), dim3(1), 0, h->fstream, h->flags + 7, 1LL, 5000000LL, dres);
-      hipLaunchKernelGGL(psmf::psmf_flag_set_k, dim3(1), dim3(1), 0, h->bulk, h->flags + 7, 1LL);
-      CREATE_TRY(hipStreamSynchronize(h->fstream));
-      CREATE_TRY(hipStreamSynchronize(h->bulk));
-      int res = 0;
-      CREATE_TRY(hipMemcpy(&res, dres, sizeof(int), hipMemcpyDeviceToHost));
-      h->streams_concurrent = res == 1;
-    }
-    const size_t flds = psmf::blk_filter_lds_bytes();
-    CREATE_TRY(hipFuncSetAttribute((const void*)psmf::psmf_blk_filter6, hipFuncAttributeMaxDynamicSharedMemorySize, (int)flds));
-    CREATE_TRY(hipFuncSetAttribute((const void*)psmf::psmf_blk_filter6d, hipFuncAttributeMaxDynamicSharedMemorySize, (int)flds));
-    CREATE_TRY(hipFuncSetAttribute((const void*)psmf::psmf_blk_filter7, hipFuncAttributeMaxDynamicSharedMemorySize, (int)flds));
-    CREATE_TRY(hipFuncSetAttribute((const void*)psmf::psmf_blk_filter<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)flds));
-    CREATE_TRY(hipFuncSetAttribute((const void*)psmf::psmf_blk_filter<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)flds));
-    CREATE_TRY(hipFuncSetAttribute((const void*)psmf::psmf_blk_filter<32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)flds));
-    const size_t alds = psmf::blk_apply_lds_bytes();
-    CREATE_TRY(hipFuncSetAttribute((const void*)psmf::psmf_blk_apply_mfma<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)alds));
-    CREATE_TRY(hipFuncSetAttribute((const void*)psmf::psmf_blk_apply_mfma<double>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)alds));
-    CREATE_TRY(hipFuncSetAttribute((const void*)psmf::psmf_blk_filter3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)psmf::blk_filter3_lds_bytes()));
-    CREATE_TRY(hipFuncSetAttribute((const void*)psmf::psmf_blk_filter3s, hipFuncAttributeMaxDynamicSharedMemorySize, (int)psmf::blk_filter3_lds_bytes()));
-    CREATE_TRY(hipFuncSetAttribute((const void*)psmf::psmf_blk_filter4, hipFuncAttributeMaxDynamicSharedMemorySize, (int)psmf::blk_filter3_lds_bytes()));
-    CREATE_TRY(hipFuncSetAttribute((const void*)psmf::psmf_blk_filter4s, hipFuncAttributeMaxDynamicSharedMemorySize, (int)psmf::blk_filter3_lds_bytes()));
-    CREATE_TRY(hipFuncSetAttribute((const void*)psmf::psmf_blk_filter5, hipFuncAttributeMaxDynamicSharedMemorySize, (int)psmf::blk_filter3_lds_bytes()));
-    CREATE_TRY(hipFuncSetAttribute((const void*)psmf::psmf_blk_xgram2<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)psmf::blk_xgram2_lds_bytes()));
-    CREATE_TRY(hipFuncSetAttribute((const void*)psmf::psmf_blk_xgram2<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)psmf::blk_xgram2_lds_bytes()));
-    CREATE_TRY(hipFuncSetAttribute((const void*)psmf::psmf_blk_apply2<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)psmf::blk_apply2_lds_bytes()));
-    CREATE_TRY(hipFuncSetAttribute((const void*)psmf::psmf_blk_apply2<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)psmf::blk_apply2_lds_bytes()));
-    const size_t flds2 = psmf::blk_filter2_lds_bytes();
-    CREATE_TRY(hipFuncSetAttribute((const void*)psmf::psmf_blk_filter2<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)flds2));
-    CREATE_TRY(hipFuncSetAttribute((const void*)psmf::psmf_blk_filter2<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)flds2));
-    CREATE_TRY(hipFuncSetAttribute((const void*)psmf::psmf_blk_filter2<32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)flds2));
   }
-  if (h->geo.sweep_lds > 48 * 1024)
-    CREATE_TRY(hipFuncSetAttribute((const void*)sweep_kernel(h), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->geo.sweep_lds));
+  if (!h->bulk) HIP_TRY(h, hipStreamCreateWithFlags(&h->bulk, hipStreamNonBlocking));
+  for (int i = 0; i < 4; ++i) {
+    HIP_TRY(h, hipEventCreateWithFlags(&h->evF[i], hipEventDisableTiming));
+    HIP_TRY(h, hipEventCreateWithFlags(&h->evA[i], hipEventDisableTiming));
+    HIP_TRY(h, hipEventCreateWithFlags(&h->evX[i], hipEventDisableTiming));
+  }
+  HIP_TRY(h, hipEventCreateWithFlags(&h->evS, hipEventDisableTiming));
+  HIP_TRY(h, hipEventCreateWithFlags(&h->evC, hipEventDisableTiming));
+  for (int i = 0; i < psmf_filter::kTimedRuns; ++i) { HIP_TRY(h, hipEventCreate(&h->evK0[i])); HIP_TRY(h, hipEventCreate(&h->evK1[i])); }
+  if (h->fstream && h->flags) {
+    // the device-flag hand-off and the chained filter launches need the two streams to run concurrently: probe it (a waiter on the filter stream, then the
+    // setter on the bulk stream; the waiter gives up after 50 ms)
+    int* dres = nullptr;
+    struct FreeOnExit { int** p; ~FreeOnExit() { if (*p) { hipFree(*p); *p = nullptr; } } } dres_guard{&dres};      // also on the HIP_TRY failure paths below
+    HIP_TRY(h, hipMalloc((void**)&dres, sizeof(int)));
+    HIP_TRY(h, hipMemset(dres, 0, sizeof(int)));
+    HIP_TRY(h, hipDeviceSynchronize());      // hipMemset is asynchronous on the null stream, the probe's streams are non-blocking: the zeroes (of dres and of h->flags above) first
+    hipLaunchKernelGGL(psmf::psmf_probe_wait_k, dim3(1), dim3(1), 0, h->fstream, h->flags + 7, 1LL, 5000000LL, dres);
+    hipLaunchKernelGGL(psmf::psmf_flag_set_k, dim3(1), dim3(1), 0, h->bulk, h->flags + 7, 1LL);
+    HIP_TRY(h, hipStreamSynchronize(h->fstream));
+    HIP_TRY(h, hipStreamSynchronize(h->bulk));
+    int res = 0;
+    HIP_TRY(h, hipMemcpy(&res, dres, sizeof(int), hipMemcpyDeviceToHost));
+    h->streams_concurrent = res == 1;
+  }
+  // function-local: no namespace-scope initialiser takes kernel addresses before the runtime has registered them
+  const size_t flds = psmf::blk_filter_lds_bytes(), flds2 = psmf::blk_filter2_lds_bytes(), flds3 = psmf::blk_filter3_lds_bytes();
+  const size_t alds = psmf::blk_apply_lds_bytes(), alds2 = psmf::blk_apply2_lds_bytes(), xlds2 = psmf::blk_xgram2_lds_bytes();
+  const struct { const void* fn; size_t bytes; } lds_kernels[] = {
+    {(const void*)psmf::psmf_blk_filter6, flds}, {(const void*)psmf::psmf_blk_filter6d, flds}, {(const void*)psmf::psmf_blk_filter7, flds},
+    {(const void*)psmf::psmf_blk_filter<8>, flds}, {(const void*)psmf::psmf_blk_filter<16>, flds}, {(const void*)psmf::psmf_blk_filter<32>, flds},
+    {(const void*)psmf::psmf_blk_apply_mfma<float>, alds}, {(const void*)psmf::psmf_blk_apply_mfma<double>, alds},
+    {(const void*)psmf::psmf_blk_filter3, flds3}, {(const void*)psmf::psmf_blk_filter3s, flds3}, {(const void*)psmf::psmf_blk_filter4, flds3},
+    {(const void*)psmf::psmf_blk_filter4s, flds3}, {(const void*)psmf::psmf_blk_filter5, flds3},
+    {(const void*)psmf::psmf_blk_xgram2<2>, xlds2}, {(const void*)psmf::psmf_blk_xgram2<3>, xlds2},
+    {(const void*)psmf::psmf_blk_apply2<2>, alds2}, {(const void*)psmf::psmf_blk_apply2<3>, alds2},
+    {(const void*)psmf::psmf_blk_filter2<8>, flds2}, {(const void*)psmf::psmf_blk_filter2<16>, flds2}, {(const void*)psmf::psmf_blk_filter2<32>, flds2},
+  };
+  for (const auto& k : lds_kernels) { const int rc = opt_in_lds(h, k.fn, k.bytes); if (rc) return rc; }
+  return PSMF_OK;
+}
+
+// persistent per-step engine (psmf_pstep.hip): the plan of a launch and its communication block, where the kernel applies
+int init_pstep(psmf_filter* h) {
+  const psmf_config* cfg = &h->cfg;
   if (h->engine == 1 && h->sw.step_persistent && (cfg->r <= 32 || (h->sw.pstep_big && cfg->r <= 48 && cfg->masked == 0)) && cfg->masked <= 1 && !cfg->nonuniform_R &&
       cfg->dyn_kind <= PSMF_DYN_COS_PHASE) {
     hipDeviceProp_t prop;
-    CREATE_TRY(hipGetDeviceProperties(&prop, cfg->device));
+    HIP_TRY(h, hipGetDeviceProperties(&prop, cfg->device));
     if (psmf::pstep_plan(cfg->d_local, cfg->r, prop.multiProcessorCount, cfg->storage == PSMF_F64, cfg->masked == 1, &h->ps_plan)) {
-      CREATE_TRY(psmf::pstep_init());
-      CREATE_TRY(hipMalloc(&h->ps_comm, h->ps_plan.total_bytes));
-      CREATE_TRY(hipMemset(h->ps_comm, 0, h->ps_plan.total_bytes));
-      if (getenv("PSMF_PSTEP_PROF")) { CREATE_TRY(hipMalloc((void**)&h->ps_prof, 64 * sizeof(long long))); CREATE_TRY(hipMemset(h->ps_prof, 0, 64 * sizeof(long long))); }
+      HIP_TRY(h, psmf::pstep_init());
+      HIP_TRY(h, hipMalloc(&h->ps_comm, h->ps_plan.total_bytes));
+      HIP_TRY(h, hipMemset(h->ps_comm, 0, h->ps_plan.total_bytes));
+      if (h->sw.pstep_prof) { HIP_TRY(h, hipMalloc((void**)&h->ps_prof, 64 * sizeof(long long))); HIP_TRY(h, hipMemset(h->ps_prof, 0, 64 * sizeof(long long))); }
       h->ps_ok = true;
     }
   }
-#undef CREATE_TRY
+  return PSMF_OK;
+}
 
+void fill_step_params(psmf_filter* h) {
+  const psmf_config* cfg = &h->cfg;
   StepParams& sp = h->sp;
   memset(&sp, 0, sizeof(sp));
   sp.st = h->st;
@@ -1135,7 +1108,7 @@ int psmf_create(psmf_handle* out, const psmf_config* cfg) {
   sp.track_g = ((cfg->eta_full || cfg->coef_update) && !cfg->masked) ? 1 : 0;     // masked: G is this step's masked Gram, recomputed every step
   sp.mask = nullptr; sp.mg = nullptr; sp.mg_tr = nullptr; sp.mg_ntr = 0; sp.sc_hist = nullptr; sp.mask_rows = 0;
   sp.masked_method = cfg->masked >= 2 ? cfg->masked : 0;
-  sp.solve_lds = (Switches::off("PSMF_STEP_WAVE_SOLVE") || (cfg->r > 32 && Switches::off("PSMF_STEP_WAVE_BIG"))) ? 1 : 0;
+  sp.solve_lds = (!h->sw.wave_solve || (cfg->r > 32 && !h->sw.wave_big)) ? 1 : 0;
   {
     // The last row workgroup of a sweep sums the partial rows (tail_reduce_partials) where the solve block outlasts the row blocks
     // by more than that tail -- r > 32 at moderate d_local, small shards: 31.6 -> 30.0 us per timestep at r = 40, d = 2e4, 50.3 ->
@@ -1143,17 +1116,15 @@ int psmf_create(psmf_handle* out, const psmf_config* cfg) {
     // tail; tools/probe_tail.py).  PSMF_TAIL_REDUCE=1 / 0 forces it on / off.
     const double rows_us = 2.0 * (double)cfg->d_local * h->geo.rp * (double)h->elem() / 3.0e6;
     const double solve_us = cfg->r <= 32 ? 0.3 * cfg->r : (cfg->r <= 48 ? 13.0 : 24.0);
-    const char* e = getenv("PSMF_TAIL_REDUCE");
-    const bool forced = e && atoi(e) == 1;
-    sp.tail_reduce = (h->engine == 1 && h->sw.tail_reduce && (forced || (cfg->coef_update && rows_us + 3.0 < solve_us))) ? 1 : 0;
+    sp.tail_reduce = (h->engine == 1 && h->sw.tail_reduce != 0 && (h->sw.tail_reduce == 1 || (cfg->coef_update && rows_us + 3.0 < solve_us))) ? 1 : 0;
   }
   sp.external_reduce = sp.tail_reduce;
-  sp.use_ns = (getenv("PSMF_NS") && atoi(getenv("PSMF_NS")) == 0) ? 0 : 1;
-  sp.ns_predict = getenv("PSMF_NS_PREDICT") ? atoi(getenv("PSMF_NS_PREDICT")) : 7;      // bits: 1 a / b (phase F), 2 core (wave 7), 4 applied
+  sp.use_ns = h->sw.ns ? 1 : 0;
+  sp.ns_predict = h->sw.ns_predict;
   // Newton-Schulz acceptance: ||I - M X||_F below the tolerance BEFORE the last update (which squares it).  float64
   // storage: 3e-7 (-> 1e-13).  float32 storage: 3e-4 (-> ~1e-7, of the order of the rounding of C and y to float32; errors
   // against the float64 oracle measured at 1e-4 / 3e-4 / 1e-3 in DESIGN section 5: unchanged up to 3e-4).  PSMF_NS_TOL overrides.
-  const double ns_tol = getenv("PSMF_NS_TOL") ? atof(getenv("PSMF_NS_TOL")) : (cfg->storage == PSMF_F64 ? 3e-7 : 3e-4);
+  const double ns_tol = h->sw.ns_tol_set ? h->sw.ns_tol : (cfg->storage == PSMF_F64 ? 3e-7 : 3e-4);
   sp.ns_tol2 = ns_tol * ns_tol;
   // A start with ||I - M X0||_F >= 0.3 is given up for the direct sweep, and the next three steps sweep unasked (PSMF_NS_FAR,
   // PSMF_NS_SKIP).  Below 1 the iteration would converge -- from 0.9 in seven iterations of 0.9 us against a 15 us sweep -- and
@@ -1161,14 +1132,48 @@ int psmf_create(psmf_handle* out, const psmf_config* cfg) {
   // NOT taken: the iteration stops at a residual (1e-7), the sweep is pivot-exact, and where Lbar' = (I / q - W / q^2) / omega
   // cancels (q = 1e-8, tests/adversarial_cases.py:tiny_Q) every early step iterated instead of swept costs accuracy -- y_hat error
   // 6.4e-7 (0.3 / 3), 4.0e-6 (0.3 / 0), 9.2e-6 (0.6 / 1), 1.26e-5 (0.6 / 0) against the 1e-5 bar (profiles/r4_adversarial_ns_far.txt).
-  const double ns_far = getenv("PSMF_NS_FAR") ? atof(getenv("PSMF_NS_FAR")) : 0.3;
-  sp.ns_far2 = ns_far * ns_far;
-  sp.ns_skip_n = getenv("PSMF_NS_SKIP") ? atoi(getenv("PSMF_NS_SKIP")) : 3;
-  h->ns_far_env = getenv("PSMF_NS_FAR") != nullptr;          // (otherwise psmf_set_state picks 0.9 / 1 where nothing cancels: update_ns_policy)
-  h->ns_skip_env = getenv("PSMF_NS_SKIP") != nullptr;
+  sp.ns_far2 = h->sw.ns_far * h->sw.ns_far;      // (unset: psmf_set_state picks 0.9 / 1 where nothing cancels, update_ns_policy)
+  sp.ns_skip_n = h->sw.ns_skip;
   sp.alpha = cfg->alpha; sp.beta = cfg->beta;
   sp.lr = cfg->adam_lr; sp.lr_end = cfg->adam_lr_end; sp.lr_steps = cfg->adam_lr_steps;
   sp.b1 = cfg->adam_b1; sp.b2 = cfg->adam_b2;
+}
+
+}  // namespace
+
+extern "C" {
+
+int psmf_device_count(void) {
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess) return 0;
+  return n;
+}
+
+const char* psmf_last_error(psmf_handle h) { return h ? h->err.c_str() : g_create_error.c_str(); }
+
+int psmf_create(psmf_handle* out, const psmf_config* cfg) {
+  if (!out || !cfg) return fail(nullptr, PSMF_ERR_ARG, "psmf_create: null argument");
+  *out = nullptr;
+  if (const char* msg = check_config(cfg)) return fail(nullptr, PSMF_ERR_ARG, msg);
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+    return fail(nullptr, PSMF_ERR_NO_DEVICE, "psmf_create: no HIP device visible (the MI355X path has no CPU fallback)");
+  if (cfg->device < 0 || cfg->device >= ndev) return fail(nullptr, PSMF_ERR_ARG, "psmf_create: bad device ordinal");
+
+  psmf_filter* h = new psmf_filter();
+  h->cfg = *cfg;
+  compute_geometry(h->cfg, h->geo, h->sw.sweep_threads);
+  auto bail = [&](int code) { g_create_error = h->err; psmf_destroy(h); return code; };
+  int rc = choose_engine(h);
+  if (!rc) rc = alloc_common(h);
+  if (!rc && h->engine == 2) rc = init_blocked(h);
+  // dynamic LDS beyond the default limit: opted in here, per handle and so on the handle's device, for the kernels it can launch
+  if (!rc && h->geo.sweep_lds > 48 * 1024) rc = opt_in_lds(h, (const void*)sweep_kernel(h), h->geo.sweep_lds);
+  if (!rc && cfg->masked) { const serial_mgram_t k = serial_mgram_kernel(h); rc = opt_in_lds(h, (const void*)k.fn, k.lds); }
+  if (!rc && cfg->nonuniform_R) { const wgram_t k = wgram_kernel(h); rc = opt_in_lds(h, (const void*)k.fn, k.lds); }
+  if (!rc) rc = init_pstep(h);
+  if (rc) return bail(rc);
+  fill_step_params(h);
   // the zero-fills above ran on the null stream; the handle's own streams are non-blocking
   if (hipDeviceSynchronize() != hipSuccess) { h->err = "hipDeviceSynchronize at the end of psmf_create failed"; return bail(PSMF_ERR_HIP); }
   *out = h;
@@ -1243,15 +1248,13 @@ int psmf_set_state(psmf_handle h, const double* C, const double* V, const double
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   const int r = h->cfg.r, dl = h->cfg.d_local, rp = h->geo.rp;
   if (C) {
-    if (h->cfg.storage == PSMF_F64) {
-      std::vector<double> buf((size_t)dl * rp);
-      pack_rows<double>(C, buf.data(), dl, r, rp);
-      HIP_TRY(h, hipMemcpy(h->C, buf.data(), buf.size() * 8, hipMemcpyHostToDevice));
-    } else {
-      std::vector<float> buf((size_t)dl * rp);
-      pack_rows<float>(C, buf.data(), dl, r, rp);
-      HIP_TRY(h, hipMemcpy(h->C, buf.data(), buf.size() * 4, hipMemcpyHostToDevice));
-    }
+    rc = by_storage(h, [&](auto t) {
+      std::vector<decltype(t)> buf((size_t)dl * rp);
+      pack_rows(C, buf.data(), dl, r, rp);
+      HIP_TRY(h, hipMemcpy(h->C, buf.data(), buf.size() * sizeof(t), hipMemcpyHostToDevice));
+      return (int)PSMF_OK;
+    });
+    if (rc) return rc;
     if (h->rotU) {                       // non-diagonal R: the handle keeps U^T C
       const size_t cb = (size_t)dl * rp * h->elem();
       rc = ensure_rot_tmp(h, cb);
@@ -1331,15 +1334,13 @@ int psmf_get_state(psmf_handle h, double* C, double* V, double* P, double* Q, do
       HIP_TRY(h, hipStreamSynchronize(h->stream));
       Csrc = h->rot_tmp;
     }
-    if (h->cfg.storage == PSMF_F64) {
-      std::vector<double> buf((size_t)dl * rp);
-      HIP_TRY(h, hipMemcpy(buf.data(), Csrc, buf.size() * 8, hipMemcpyDeviceToHost));
-      for (int i = 0; i < dl; ++i) for (int c = 0; c < r; ++c) C[(size_t)i * r + c] = buf[(size_t)i * rp + c];
-    } else {
-      std::vector<float> buf((size_t)dl * rp);
-      HIP_TRY(h, hipMemcpy(buf.data(), Csrc, buf.size() * 4, hipMemcpyDeviceToHost));
+    rc = by_storage(h, [&](auto t) {
+      std::vector<decltype(t)> buf((size_t)dl * rp);
+      HIP_TRY(h, hipMemcpy(buf.data(), Csrc, buf.size() * sizeof(t), hipMemcpyDeviceToHost));
       for (int i = 0; i < dl; ++i) for (int c = 0; c < r; ++c) C[(size_t)i * r + c] = (double)buf[(size_t)i * rp + c];
-    }
+      return (int)PSMF_OK;
+    });
+    if (rc) return rc;
   }
   const size_t rr = (size_t)r * r * sizeof(double);
   if (V) HIP_TRY(h, hipMemcpy(V, h->st->V, rr, hipMemcpyDeviceToHost));
@@ -1406,23 +1407,19 @@ int psmf_upload_series(psmf_handle h, const void* Y, int dtype, int64_t t0, int6
     HIP_TRY(h, hipMemcpy(dst, Y, n * es, hipMemcpyHostToDevice));
   } else {
     const size_t blk = (size_t)1 << 24;
-    if (h->cfg.storage == PSMF_F32) {
-      std::vector<float> buf(n < blk ? n : blk);
-      const double* src = (const double*)Y;
+    rc = by_storage(h, [&](auto t) {      // t: the storage type; the caller's array is of the other one
+      using TD = decltype(t);
+      using TS = std::conditional_t<sizeof(TD) == 8, float, double>;
+      std::vector<TD> buf(n < blk ? n : blk);
+      const TS* src = (const TS*)Y;
       for (size_t a = 0; a < n; a += blk) {
         const size_t m = n - a < blk ? n - a : blk;
-        for (size_t i = 0; i < m; ++i) buf[i] = (float)src[a + i];
-        HIP_TRY(h, hipMemcpy(dst + a * 4, buf.data(), m * 4, hipMemcpyHostToDevice));
+        for (size_t i = 0; i < m; ++i) buf[i] = (TD)src[a + i];
+        HIP_TRY(h, hipMemcpy(dst + a * sizeof(TD), buf.data(), m * sizeof(TD), hipMemcpyHostToDevice));
       }
-    } else {
-      std::vector<double> buf(n < blk ? n : blk);
-      const float* src = (const float*)Y;
-      for (size_t a = 0; a < n; a += blk) {
-        const size_t m = n - a < blk ? n - a : blk;
-        for (size_t i = 0; i < m; ++i) buf[i] = (double)src[a + i];
-        HIP_TRY(h, hipMemcpy(dst + a * 8, buf.data(), m * 8, hipMemcpyHostToDevice));
-      }
-    }
+      return (int)PSMF_OK;
+    });
+    if (rc) return rc;
   }
   if (h->rotU && n) {                    // non-diagonal R: the handle keeps the rows y^T U
     rc = ensure_rot_tmp(h, n * es);
@@ -1515,11 +1512,11 @@ int psmf_sync(psmf_handle h) {
   if (!h) return PSMF_ERR_ARG;
   int rc = set_device(h);
   if (rc) return rc;
-  const double t_s0 = g_host_timing ? host_now_ms() : 0.0;
+  const double t_s0 = h->sw.host_timing ? host_now_ms() : 0.0;
   // (a 4-byte device-to-host hipMemcpy[Async] here now and then took 20-70 ms on this stack -- the copy engine waking
   //  up -- which is half a pass of the headline workload; a store from a kernel to mapped host memory does not)
   hipLaunchKernelGGL(psmf::psmf_publish_err_k, dim3(1), dim3(1), 0, h->stream, (const DevState*)h->st, h->err_host_dev);
-  const double t_s1 = g_host_timing ? host_now_ms() : 0.0;
+  const double t_s1 = h->sw.host_timing ? host_now_ms() : 0.0;
   HIP_TRY(h, spin_stream(h->stream));
   for (int i = 0; i < h->evk_pending; ++i) {         // the chained filter launches that finished: their durations
     float ms = 0.f;
@@ -1527,7 +1524,7 @@ int psmf_sync(psmf_handle h) {
     else (void)hipGetLastError();
   }
   h->evk_pending = 0;
-  if (g_host_timing) { const double t = host_now_ms(); if (t_s1 - t_s0 > 5.0) fprintf(stderr, "[psmf host timing] memcpyAsync call %.1f ms\n", t_s1 - t_s0); if (t - t_s1 > 5.0) fprintf(stderr, "[psmf host timing] spin wait %.1f ms\n", t - t_s1); }
+  if (h->sw.host_timing) { const double t = host_now_ms(); if (t_s1 - t_s0 > 5.0) fprintf(stderr, "[psmf host timing] memcpyAsync call %.1f ms\n", t_s1 - t_s0); if (t - t_s1 > 5.0) fprintf(stderr, "[psmf host timing] spin wait %.1f ms\n", t - t_s1); }
   const int err = *h->err_host;
   if (err == -7) {
     long long fl[8] = {0};
@@ -1682,7 +1679,7 @@ int psmf_counters(psmf_handle h, int64_t* out8, int reset) {
   HIP_TRY(h, hipMemcpy(g, h->st->dbg, sizeof(g), hipMemcpyDeviceToHost));
   for (int i = 0; i < 8; ++i) out8[i] = c[i];
   out8[6] = g[5];       // kernel launches of psmf_blk_filter3 (cnt[7] counts blocks; cnt[6] is a raw time stamp)
-  if (getenv("PSMF_DBG_BREAKDOWN") && c[7] > 0)
+  if (h->sw.dbg_breakdown && c[7] > 0)
     fprintf(stderr, "[psmf] filter3 per launch: hand-off %.2f us, K %.2f, init %.2f, steps %.2f, end %.2f\n", 0.01 * g[0] / c[7], 0.01 * g[1] / c[7],
             0.01 * g[2] / c[7], 0.01 * g[3] / c[7], 0.01 * g[4] / c[7]);
   if (reset) { HIP_TRY(h, hipMemset(h->st->cnt, 0, sizeof(c))); HIP_TRY(h, hipMemset(h->st->dbg, 0, sizeof(g))); HIP_TRY(h, hipDeviceSynchronize()); }   // (before the next run's kernels on the non-blocking stream count)
@@ -1774,12 +1771,10 @@ int psmf_project(psmf_handle h, const double* mu, int64_t n_pred, double* out) {
   HIP_TRY(h, hipMemcpy(dmu, mu, mbytes, hipMemcpyHostToDevice));
   const int grid = (dl + psmf::WG - 1) / psmf::WG;
   const size_t lds = (size_t)64 * r * sizeof(double);
-  if (h->cfg.storage == PSMF_F64)
-    hipLaunchKernelGGL(psmf::psmf_predict_rows<double>, dim3(grid), dim3(psmf::WG), lds, h->stream,
-                       (const double*)h->C, dl, r, h->geo.rp, (const double*)dmu, (int)n_pred, dout);
-  else
-    hipLaunchKernelGGL(psmf::psmf_predict_rows<float>, dim3(grid), dim3(psmf::WG), lds, h->stream,
-                       (const float*)h->C, dl, r, h->geo.rp, (const double*)dmu, (int)n_pred, dout);
+  by_storage(h, [&](auto t) {
+    hipLaunchKernelGGL(psmf::psmf_predict_rows<decltype(t)>, dim3(grid), dim3(psmf::WG), lds, h->stream,
+                       (const decltype(t)*)h->C, dl, r, h->geo.rp, (const double*)dmu, (int)n_pred, dout);
+  });
   HIP_TRY(h, hipGetLastError());
   if (h->rotU) {                         // non-diagonal R: C here is U^T C -- rotate the projections back
     rc = ensure_rot_tmp(h, obytes);
@@ -1834,12 +1829,10 @@ int psmf_sq_error(psmf_handle h, int64_t t0, int64_t nt, double* out) {
   rc = ensure_scratch(h, grid * sizeof(double));
   if (rc) return rc;
   const size_t dl = h->cfg.d_local, n = (size_t)nt * dl, off = (size_t)t0 * dl;
-  if (h->cfg.storage == PSMF_F64)
-    hipLaunchKernelGGL(psmf::psmf_sq_error_k<double>, dim3(grid), dim3(psmf::WG), 0, h->stream,
-                       (const double*)h->YP + off, (const double*)h->Y + off, n, h->scratch);
-  else
-    hipLaunchKernelGGL(psmf::psmf_sq_error_k<float>, dim3(grid), dim3(psmf::WG), 0, h->stream,
-                       (const float*)h->YP + off, (const float*)h->Y + off, n, h->scratch);
+  by_storage(h, [&](auto t) {
+    hipLaunchKernelGGL(psmf::psmf_sq_error_k<decltype(t)>, dim3(grid), dim3(psmf::WG), 0, h->stream,
+                       (const decltype(t)*)h->YP + off, (const decltype(t)*)h->Y + off, n, h->scratch);
+  });
   HIP_TRY(h, hipGetLastError());
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   std::vector<double> part(grid);
@@ -2133,12 +2126,10 @@ int psmf_masked_metrics(psmf_handle h, const uint8_t* Mmiss, int64_t t0, int64_t
   rc = ensure_scratch(h, (size_t)gx * gy * 4 * sizeof(double));
   if (rc) return rc;
   const size_t lds = (size_t)32 * h->cfg.r * sizeof(double);
-  if (h->cfg.storage == PSMF_F64)
-    hipLaunchKernelGGL(psmf::psmf_masked_metrics_k<double>, dim3(gx, gy), dim3(psmf::WG), lds, h->stream, h->sp, (const uint8_t*)h->mask,
+  by_storage(h, [&](auto t) {
+    hipLaunchKernelGGL(psmf::psmf_masked_metrics_k<decltype(t)>, dim3(gx, gy), dim3(psmf::WG), lds, h->stream, h->sp, (const uint8_t*)h->mask,
                        (const uint8_t*)h->mmiss, (const double*)h->sc_hist, (long long)t0, (int)nt, chunk, sig, h->cfg.robust, h->scratch);
-  else
-    hipLaunchKernelGGL(psmf::psmf_masked_metrics_k<float>, dim3(gx, gy), dim3(psmf::WG), lds, h->stream, h->sp, (const uint8_t*)h->mask,
-                       (const uint8_t*)h->mmiss, (const double*)h->sc_hist, (long long)t0, (int)nt, chunk, sig, h->cfg.robust, h->scratch);
+  });
   HIP_TRY(h, hipGetLastError());
   std::vector<double> part((size_t)gx * gy * 4);
   HIP_TRY(h, hipMemcpyAsync(part.data(), h->scratch, part.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -2178,7 +2169,8 @@ int psmf_measure_copy_bandwidth(int device, size_t bytes, int iters, double* gbp
   size_t gsz = n16 / ((size_t)psmf::WG * 4);
   if (gsz < 1024) gsz = 1024;
   if (gsz > ((size_t)1 << 20)) gsz = (size_t)1 << 20;
-  const int grid = getenv("PSMF_COPY_GRID") ? atoi(getenv("PSMF_COPY_GRID")) : (int)gsz;
+  const int copy_grid = Switches().copy_grid;
+  const int grid = copy_grid ? copy_grid : (int)gsz;
   for (int i = 0; i < 3; ++i) hipLaunchKernelGGL(psmf::psmf_copy_k, dim3(grid), dim3(psmf::WG), 0, s, (const float4*)src, (float4*)dst, n16);
   HIP_TRY(h, hipEventRecord(e0, s));
   for (int i = 0; i < iters; ++i) hipLaunchKernelGGL(psmf::psmf_copy_k, dim3(grid), dim3(psmf::WG), 0, s, (const float4*)src, (float4*)dst, n16);

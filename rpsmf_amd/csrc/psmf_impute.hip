@@ -579,10 +579,10 @@ namespace {
 // Which column loop a shape gets (also what psmf_impute_kernel_id reports): 2 = psmf_impute_kernel2 (round 1's loop, id 1, was removed in round 5),
 // 300 + NG = psmf_impute_kernel3<NG> (d <= 80, r <= 14), 4 = the masked per-step engine of the large-d handle (any d, r <= PSMF_RMAX):
 // one workgroup per replica needs the replica's C, V, x in LDS (d <= 512, r <= 16).
-int impute_select(int d, int r, size_t* lds_out) {
+int impute_select(int d, int r, bool allow_v3, size_t* lds_out) {
   using namespace psmf;
   if (r > IR || d > 2 * WG) return 4;
-  const bool v3 = impute3_ok(d, r) && !(getenv("PSMF_IMPUTE_V3") && atoi(getenv("PSMF_IMPUTE_V3")) == 0);   // small shapes: every wave its own Gram
+  const bool v3 = impute3_ok(d, r) && allow_v3;   // small shapes: every wave its own Gram
   const size_t lds = v3 ? impute3_lds_bytes(d, r) : impute2_lds_bytes(d, r);
   if (lds > 160 * 1024) return 4;
   if (lds_out) *lds_out = lds;
@@ -596,7 +596,7 @@ int impute_run_large(const psmf_impute_config* cfg, const double* YorgInt, const
 
 extern "C" int psmf_impute_kernel_id(const psmf_impute_config* cfg) {
   if (!cfg || cfg->abi_version != PSMF_ABI_VERSION || cfg->d < 1 || cfg->r < 1 || cfg->r > PSMF_RMAX) return PSMF_ERR_ARG;
-  return impute_select(cfg->d, cfg->r, nullptr);
+  return impute_select(cfg->d, cfg->r, Switches().impute_v3, nullptr);
 }
 
 extern "C" int psmf_impute_run(const psmf_impute_config* cfg, const double* YorgInt, const uint8_t* M,
@@ -614,8 +614,9 @@ extern "C" int psmf_impute_run(const psmf_impute_config* cfg, const double* Yorg
   if (n < 2 || B < 1 || cfg->n_iter < 1) return fail(PSMF_ERR_ARG, "bad n / batch / n_iter");
   if (cfg->method < 0 || cfg->method > 3) return fail(PSMF_ERR_ARG, "method must be 0 (PSMF), 1 (rPSMF), 2 (MLE-SMF) or 3 (TMF)");
   if (cfg->want_bands && (!Yrec || !YrecL || !YrecH)) return fail(PSMF_ERR_ARG, "want_bands needs Yrec, YrecL, YrecH");
+  const Switches sw;      // no handle here: read at entry, on every call
   size_t lds = 0;
-  const int sel = impute_select(d, r, &lds);
+  const int sel = impute_select(d, r, sw.impute_v3, &lds);
   if (sel == 4)       // beyond one workgroup's LDS: the replicas one after the other on the masked per-step engine (psmf_masked.hip)
     return impute_run_large(cfg, YorgInt, M, Mmiss, C, X, V, P, Q, rho, Epred, Efull, inside, Yrec, YrecL, YrecH, status, elapsed_ms);
   const bool v3 = sel >= 300;
@@ -669,7 +670,7 @@ extern "C" int psmf_impute_run(const psmf_impute_config* cfg, const double* Yorg
   ip.Yorg = dY; ip.M = dM; ip.Mmiss = dMm; ip.C = dC; ip.X = dX; ip.V0 = dV; ip.P0 = dP; ip.Q0 = dQ;
   ip.Epred = dEp; ip.Efull = dEf; ip.inside = dIn; ip.Yrec = dYr; ip.YrecL = dYl; ip.YrecH = dYh; ip.err = dErr; ip.prof = nullptr;
   {
-    bool iso = Q[0] > 0.0 && !(getenv("PSMF_IMPUTE_PAR") && atoi(getenv("PSMF_IMPUTE_PAR")) == 0);
+    bool iso = Q[0] > 0.0 && sw.impute_par;
     for (int i = 0; i < r && iso; ++i)
       for (int c = 0; c < r; ++c)
         if (Q[i * r + c] != (i == c ? Q[0] : 0.0)) { iso = false; break; }
