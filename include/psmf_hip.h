@@ -302,7 +302,8 @@ typedef struct {
  *   Mmiss    batch x n x d  uint8   1 = artificially removed (evaluation set)
  *   C        batch x d x r  float64 in: C0   out: final C
  *   X        batch x n x r  float64 in: X0   out: final X (the reference mutates X in place)
- *   V, P, Q  r x r float64 (shared initial values);  rho = uniform diag(R)
+ *   V, P, Q  r x r float64 (shared initial values);  rho = uniform diag(R) (R = rho I; a diagonal R with unequal entries:
+ *            psmf_impute_run_rows below)
  *   Epred, Efull  batch x n_iter  (RMSE after each pass, PSMF.py:88-89)
  *   inside        batch           (coverage, common.py:87-94)
  *   Yrec, YrecL, YrecH  batch x n x d float64 or NULL
@@ -317,6 +318,17 @@ int psmf_impute_run(const psmf_impute_config* cfg, const double* YorgInt, const 
                     const uint8_t* Mmiss, double* C, double* X, const double* V,
                     const double* P, const double* Q, double rho, double* Epred, double* Efull,
                     double* inside, double* Yrec, double* YrecL, double* YrecH, int32_t* status, float* elapsed_ms);
+/* psmf_impute_run with per-row observation noise: R = diag(rho_rows), d values >= 0 shared by the replicas -- the reference's masked
+ * filters read np.diag(R) row by row (ExperimentImpute/PSMF.py:70-72, rPSMF.py:91-98, MLESMF.py:70-76); rPSMF's R = omega R
+ * (rPSMF.py:134) scales all of them.  Every other argument as in psmf_impute_run.  Entries all equal, and method 3 (TMF ignores R),
+ * run psmf_impute_run's own kernels with rho = rho_rows[0] (the same bits).  Unequal entries run the row-noise instances of the
+ * one-workgroup kernels (psmf_impute_kernel3w<NG>, psmf_impute_kernel2w), i.e. the shapes psmf_impute_kernel_id answers with 2 or
+ * 300 + NG: d <= 512, r <= 16.  On a shape it answers with 4 (the masked per-step engine of the large-d handle, which carries one
+ * scalar rho) unequal entries are PSMF_ERR_ARG; so is an entry that is negative or not finite. */
+int psmf_impute_run_rows(const psmf_impute_config* cfg, const double* YorgInt, const uint8_t* M,
+                         const uint8_t* Mmiss, double* C, double* X, const double* V,
+                         const double* P, const double* Q, const double* rho_rows, double* Epred, double* Efull,
+                         double* inside, double* Yrec, double* YrecL, double* YrecH, int32_t* status, float* elapsed_ms);
 /* Which column loop psmf_impute_run uses for cfg->d, cfg->r (with the present environment switches): 1 = round 1's loop,
  * 2 = psmf_impute_kernel2, 300 + NG = psmf_impute_kernel3<NG> (d <= 80, r <= 14; NG = 4-row groups: 3, 5, 8, 12, 20),
  * 4 = masked per-step engine of the large-d handle.  Negative = error.  (Diagnostics; the reference has one code path.) */

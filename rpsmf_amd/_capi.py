@@ -81,6 +81,8 @@ SIGNATURES = {
     "psmf_measure_copy_bandwidth": (C.c_int, [C.c_int, C.c_size_t, C.c_int, _dp]),
     "psmf_impute_run": (C.c_int, [C.POINTER(PsmfImputeConfig), _dp, _u8p, _u8p, _dp, _dp, _dp, _dp, _dp,
                                   C.c_double, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
+    "psmf_impute_run_rows": (C.c_int, [C.POINTER(PsmfImputeConfig), _dp, _u8p, _u8p, _dp, _dp, _dp, _dp, _dp,
+                                       _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
     "psmf_impute_kernel_id": (C.c_int, [C.POINTER(PsmfImputeConfig)]),
     "psmf_comm_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "psmf_device_pci_bus_id": (C.c_int, [C.c_int, C.c_char_p, C.c_int]),

@@ -61,6 +61,7 @@ struct ImputeParams {
   int* err;                // batch
   int q_iso;               // Q0 = q I with q > 0: the two r x r inversions of a column run in parallel on two waves
   unsigned long long* prof;   // diagnostics (tools/impute_prof.hip) or nullptr
+  const double* rho_rows;  // d: diag(R) of the row-noise instances (psmf_impute_run_rows; shared by the replicas), else nullptr
 };
 
 // End of a pass: sum over the held-out entries of (C x_t - y_t)^2 with the pass's final C (ExperimentImpute/PSMF.py:86-89, the RMSE of C @ X).
@@ -179,7 +180,13 @@ __device__ __forceinline__ void imp_barrier_check(const int n, int* errflag) {
   __syncthreads();
 }
 
-template <int WV>
+// RW: per-row observation noise, R = diag(rho_i) (p.rho_rows; psmf_impute_run_rows): the weights kappa_i = m_i / (c_t rho_i + s) stay
+// inside the contractions.  The Gram waves accumulate a WEIGHTED tile (A operand kappa_i * row: G_R, b, and q = sum kappa_i e_i^2 at
+// (r, r)) beside the plain one, which is still needed for <G, P + Q>; they form s themselves (wave 0 has it only at barrier 2) and read
+// c_t -- the factor R = omega R has put on R since the start of the pass, rPSMF.py:134 -- from ssc[7], where the uniform instance
+// publishes its kappa.  Wave 0 forms q and sum_i m_i rho_i beside sum(e^2) in P2.  RW = false compiles to what it was before the
+// parameter existed.
+template <int WV, bool RW = false>
 __device__ __forceinline__ void impute2_wave(const ImputeParams& p) {
   int nbar = 0;          // barriers this wave has executed (imp_barrier_check at the end)
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -203,6 +210,8 @@ __device__ __forceinline__ void impute2_wave(const ImputeParams& p) {
   double* sW = ssc + 8;                       // 256: W_{t-1} = (M_{t-1} + I / q_{t-1})^-1 in MFMA output layout (parallel inversions)
   double* sred = sW + 256;                    // 16: end-of-pass reductions
   int* errflag = reinterpret_cast<int*>(sred + 16);
+  double* srho = sred + 16 + 2;               // (RW) d4: diag(R); padding rows 1
+  double* sgw = srho + d4;                    // (RW) 3 waves x 2 tiles x 256: the weighted Gram partials
 
   const double* Yorg = p.Yorg;
   const uint8_t* Mk = p.M + (size_t)rep * n * d;
@@ -210,6 +219,8 @@ __device__ __forceinline__ void impute2_wave(const ImputeParams& p) {
   double* Cg = p.C + (size_t)rep * d * r;
   double* Xg = p.X + (size_t)rep * n * r;
 
+  if constexpr (RW)
+    for (int idx = tid; idx < d4; idx += WG) srho[idx] = idx < d ? p.rho_rows[idx] : 1.0;
   for (int idx = tid; idx < d4 * IR; idx += WG) { const int i = idx >> 4, l = idx & 15; sC[idx] = (i < d && l < r) ? Cg[i * r + l] : 0.0; }
   for (int idx = tid; idx < IR * IR; idx += WG) { const int i = idx >> 4, l = idx & 15; sV[idx] = (i < r && l < r) ? p.V0[i * r + l] : 0.0; }
   if (tid < 2 * IR) sx[tid] = (tid < r) ? Xg[(size_t)(n - 1) * r + tid] : 0.0;   // t = 0 wraps to the last column (PSMF.py:65)
@@ -218,7 +229,7 @@ __device__ __forceinline__ void impute2_wave(const ImputeParams& p) {
   if (tid == 0) *errflag = 0;
   const double dd = (double)d, idd = 1.0 / dd;
   const bool sgd = p.method >= 2;     // MLE-SMF / TMF: gradient step on C along x_p, no V
-  const bool tmf = p.method == 3;
+  const bool tmf = !RW && p.method == 3;      // (TMF ignores R: it never runs the row-noise instance)
   const bool one_tile = r < 16;       // the augmented column e fits the 16 x 16 tile
   // Q = q I (every experiment): the two inversions of a column are made independent, as in the blocked engine (psmf_block.hip):
   //   P+_t = M_t^-1,  M_t = Lbar_t + kappa_t G_t                                   (wave 0)
@@ -239,7 +250,8 @@ __device__ __forceinline__ void impute2_wave(const ImputeParams& p) {
     Pm[q] = inq[q] ? 0.5 * (p.P0[a] + p.P0[b]) : 0.0;
     Qm[q] = inq[q] ? 0.5 * (p.Q0[a] + p.Q0[b]) : 0.0;
   }
-  double rho = p.rho0, lam = p.lambda0;
+  const double rho_start = RW ? 1.0 : p.rho0;      // RW: rho is c_t
+  double rho = rho_start, lam = p.lambda0;
   double qv = p.Q0[0], iqv = 1.0;     // running q of Q = q I and its reciprocal (parallel inversions)
   Sw16K swk;                          // (waves 0, 1: the lane constants of wave_sweep16m)
   if (WV < 2) sw16k_init(swk, lk, lr);
@@ -257,10 +269,11 @@ __device__ __forceinline__ void impute2_wave(const ImputeParams& p) {
         const int a = inq[q] ? i * r + lr : 0, b = inq[q] ? lr * r + i : 0;
         Qm[q] = inq[q] ? 0.5 * (p.Q0[a] + p.Q0[b]) : 0.0;
       }
-      rho = p.rho0;
+      rho = rho_start;
       lam = p.lambda0;
       qv = p.Q0[0];
     }
+    if (RW && wv == 0 && lane == 0) ssc[7] = rho;      // c_t for the Gram waves (read after barrier 1 of the first column)
     if (par && (it == 0 || p.robust)) {
       // Lbar_0 = (P + q I)^-1 by one sweep, handed over as the W that reproduces it: W = q I - q^2 Lbar (omega = 1)
       if (wv == 0) {
@@ -344,7 +357,29 @@ __device__ __forceinline__ void impute2_wave(const ImputeParams& p) {
       // ---- P2: augmented masked Gram on the matrix cores, wave w: 4-row groups w, w + 4, ... ----
       double G[4], Bq[4], PP[4], kappa = 0.0, N = 0.0, eta = 0.0, s = 0.0, ee = 0.0, phi = 1.0, msum = 0.0, ild = 0.0;
       double Lb[4] = {0.0, 0.0, 0.0, 0.0}, iqt_w1 = 0.0, kap_w1 = 0.0;
-      if (wv == 0) {
+      double Gt[4] = {0.0, 0.0, 0.0, 0.0}, qw = 0.0;      // the plain Gram for the trace; (RW) q = sum kappa_i e_i^2
+      if (RW && wv == 0) {
+        // wave 0 meanwhile, row-noise form: also sum_i m_i rho_i (for eta) and q
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const double qd = par ? ((lk + 4 * q) == lr ? qv : 0.0) : Qm[q];
+          PP[q] = inq[q] ? Pm[q] + qd : 0.0;
+        }
+        s = wave_sum_f64_dpp(lane < IR ? sxc[lane & 15] * sw[lane & 15] : 0.0);                              // s = x^T V x
+        if (lane == 0) ssc[0] = s;
+        double ms = 0.0, es = 0.0, qs = 0.0;
+        for (int i = lane; i < d4; i += 64) {                     // (padding rows: e = m = 0, rho = 1)
+          const double ev = se[i], ri = srho[i], e2 = ev * ev;
+          ms = fma(smk[i], ri, ms);
+          es += e2;
+          qs = fma(fast_rcp(sgd ? ri : fma(rho, ri, s)), e2, qs);
+        }
+        msum = wave_sum_f64_dpp(ms);
+        ee = wave_sum_f64_dpp(es);
+        qw = wave_sum_f64_dpp(qs);
+        kappa = 1.0;
+        ild = fast_rcp(lam + dd);
+      } else if (wv == 0) {
         // wave 0 meanwhile: everything of P3a that does not need the Gram
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -363,6 +398,12 @@ __device__ __forceinline__ void impute2_wave(const ImputeParams& p) {
         if (lane == 0) ssc[7] = kappa;
       } else {
         f64x4 acc1 = {0.0, 0.0, 0.0, 0.0}, acc2 = {0.0, 0.0, 0.0, 0.0};
+        f64x4 accw1 = {0.0, 0.0, 0.0, 0.0}, accw2 = {0.0, 0.0, 0.0, 0.0};      // (RW) the weighted tiles
+        double ct_g = 1.0, s_g = 0.0;
+        if constexpr (RW) {
+          ct_g = ssc[7];
+          s_g = wave_sum_f64_dpp(lane < IR ? sxc[lane & 15] * sw[lane & 15] : 0.0);      // the same sum, the same bits as wave 0's s
+        }
         const int ngrp = (d + 3) >> 2;
         for (int g = wv - 1; g < ngrp; g += 3) {
           const int k = 4 * g + lk;                                     // < d4: padding rows hold zeros
@@ -372,14 +413,29 @@ __device__ __forceinline__ void impute2_wave(const ImputeParams& p) {
           const double a = mk * cval + eaug;                           // (m is 0 / 1: exact; cval = 0 where eaug != 0)
           const double b1 = cval + eaug;
           acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b1, acc1, 0, 0, 0);
-          if (!one_tile) acc2 = __builtin_amdgcn_mfma_f64_16x16x4f64(a, (lr == 0 && kin) ? ek : 0.0, acc2, 0, 0, 0);
+          if (!RW && !one_tile) acc2 = __builtin_amdgcn_mfma_f64_16x16x4f64(a, (lr == 0 && kin) ? ek : 0.0, acc2, 0, 0, 0);
+          if constexpr (RW) {
+            const double wk = mk * fast_rcp(sgd ? srho[k] : fma(ct_g, srho[k], s_g));
+            const double aw = wk * b1;
+            accw1 = __builtin_amdgcn_mfma_f64_16x16x4f64(aw, b1, accw1, 0, 0, 0);
+            if (!one_tile) accw2 = __builtin_amdgcn_mfma_f64_16x16x4f64(aw, lr == 0 ? ek : 0.0, accw2, 0, 0, 0);
+          }
         }
         double* o = sgp + (size_t)(wv - 1) * 512;
 #pragma unroll
         for (int q = 0; q < 4; ++q) o[q * 64 + lane] = acc1[q];
-        if (!one_tile) {
+        if (!RW && !one_tile) {
 #pragma unroll
           for (int q = 0; q < 4; ++q) o[256 + q * 64 + lane] = acc2[q];
+        }
+        if constexpr (RW) {
+          double* ow = sgw + (size_t)(wv - 1) * 512;
+#pragma unroll
+          for (int q = 0; q < 4; ++q) ow[q * 64 + lane] = accw1[q];
+          if (!one_tile) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) ow[256 + q * 64 + lane] = accw2[q];
+          }
         }
       }
       IMP_T(2);
@@ -391,14 +447,24 @@ __device__ __forceinline__ void impute2_wave(const ImputeParams& p) {
         for (int q = 0; q < 4; ++q) {
           const double g0 = (sgp[q * 64 + lane] + sgp[512 + q * 64 + lane]) + sgp[1024 + q * 64 + lane];
           double g1 = 0.0;
-          if (!one_tile) g1 = (sgp[256 + q * 64 + lane] + sgp[768 + q * 64 + lane]) + sgp[1280 + q * 64 + lane];
-          G[q] = inq[q] ? g0 : 0.0;
-          Bq[q] = one_tile ? g0 : g1;      // b_i = (C^T e)_i sits in column r (one tile) / column 0 (second tile) of rows i
+          if (!RW && !one_tile) g1 = (sgp[256 + q * 64 + lane] + sgp[768 + q * 64 + lane]) + sgp[1280 + q * 64 + lane];
+          if constexpr (RW) {
+            const double w0 = (sgw[q * 64 + lane] + sgw[512 + q * 64 + lane]) + sgw[1024 + q * 64 + lane];
+            double w1 = 0.0;
+            if (!one_tile) w1 = (sgw[256 + q * 64 + lane] + sgw[768 + q * 64 + lane]) + sgw[1280 + q * 64 + lane];
+            Gt[q] = inq[q] ? g0 : 0.0;
+            G[q] = inq[q] ? w0 : 0.0;      // G_R
+            Bq[q] = one_tile ? w0 : w1;    // b_i = sum_k kappa_k e_k c_ki
+          } else {
+            G[q] = inq[q] ? g0 : 0.0;
+            Gt[q] = G[q];
+            Bq[q] = one_tile ? g0 : g1;    // b_i = (C^T e)_i sits in column r (one tile) / column 0 (second tile) of rows i
+          }
         }
         if (par) {
           const double iom = ssc[4], iq = ssc[5];
           iqt_w1 = ssc[6];                 // read HERE, before barrier 3: wave 0 rewrites these slots at the end of its P3b
-          kap_w1 = ssc[7];
+          kap_w1 = RW ? 1.0 : ssc[7];
           const double c1 = iom * iq, c2 = c1 * iq;
 #pragma unroll
           for (int q = 0; q < 4; ++q) Lb[q] = inq[q] ? ((lk + 4 * q) == lr ? c1 : 0.0) - c2 * sW[q * 64 + lane] : 0.0;
@@ -407,7 +473,7 @@ __device__ __forceinline__ void impute2_wave(const ImputeParams& p) {
       if (wv == 0) {
         double tr = 0.0;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) tr += G[q] * PP[q];
+        for (int q = 0; q < 4; ++q) tr += Gt[q] * PP[q];
         const double trGP = wave_sum_f64_dpp(tr);
         eta = (rho * msum + trGP) * idd;     // divide by d, not by #observed (PSMF.py:77)
         N = s + eta;
@@ -471,7 +537,7 @@ __device__ __forceinline__ void impute2_wave(const ImputeParams& p) {
           }
         }
         double omega = 1.0;
-        if (p.robust) omega = (lam + kappa * ee - kappa * kappa * bPb) * ild;   // rPSMF.py:105
+        if (p.robust) omega = (lam + (RW ? qw : kappa * ee) - kappa * kappa * bPb) * ild;   // rPSMF.py:105
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           Pm[q] = inq[q] ? omega * -A[q] : 0.0;
@@ -483,6 +549,7 @@ __device__ __forceinline__ void impute2_wave(const ImputeParams& p) {
           iqv *= iom;
         }
         if (p.robust) { rho *= omega; lam += dd; qv *= omega; }
+        if (RW && p.robust && lane == 0) ssc[7] = rho;      // c_{t+1}: read by the Gram waves after barrier 1 of the next column
       } else {
         // ---- P4a (the other waves): rank-1 updates of C and V with N, phi of this column ----
         const double Nn = ssc[2], ph = ssc[3], et = ssc[1];
@@ -563,9 +630,18 @@ __global__ __launch_bounds__(WG) void psmf_impute_kernel2(ImputeParams p) {
   else impute2_wave<3>(p);
 }
 
-inline size_t impute2_lds_bytes(int d, int r) {
+// the same loop with per-row observation noise (psmf_impute_run_rows)
+__global__ __launch_bounds__(WG) void psmf_impute_kernel2w(ImputeParams p) {
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (wv == 0) impute2_wave<0, true>(p);
+  else if (wv == 1) impute2_wave<1, true>(p);
+  else if (wv == 2) impute2_wave<2, true>(p);
+  else impute2_wave<3, true>(p);
+}
+
+inline size_t impute2_lds_bytes(int d, int r, bool row_noise = false) {
   const size_t d4 = ((size_t)d + 3) & ~(size_t)3;
-  const size_t doubles = d4 * IR + IR * IR + 3 * IR + 2 * d4 + 4 * 2 * 256 + 8 + 256 + 16 + 2;
+  const size_t doubles = d4 * IR + IR * IR + 3 * IR + 2 * d4 + 4 * 2 * 256 + 8 + 256 + 16 + 2 + (row_noise ? d4 + 3 * 2 * 256 : 0);
   return (doubles * 8 + 15) & ~(size_t)15;
 }
 
@@ -579,11 +655,11 @@ namespace {
 // Which column loop a shape gets (also what psmf_impute_kernel_id reports): 2 = psmf_impute_kernel2 (round 1's loop, id 1, was removed in round 5),
 // 300 + NG = psmf_impute_kernel3<NG> (d <= 80, r <= 14), 4 = the masked per-step engine of the large-d handle (any d, r <= PSMF_RMAX):
 // one workgroup per replica needs the replica's C, V, x in LDS (d <= 512, r <= 16).
-int impute_select(int d, int r, bool allow_v3, size_t* lds_out) {
+int impute_select(int d, int r, bool allow_v3, size_t* lds_out, bool row_noise = false) {
   using namespace psmf;
   if (r > IR || d > 2 * WG) return 4;
   const bool v3 = impute3_ok(d, r) && allow_v3;   // small shapes: every wave its own Gram
-  const size_t lds = v3 ? impute3_lds_bytes(d, r) : impute2_lds_bytes(d, r);
+  const size_t lds = v3 ? impute3_lds_bytes(d, r, row_noise) : impute2_lds_bytes(d, r, row_noise);
   if (lds > 160 * 1024) return 4;
   if (lds_out) *lds_out = lds;
   return v3 ? 300 + impute3_groups(d) : 2;
@@ -599,12 +675,14 @@ extern "C" int psmf_impute_kernel_id(const psmf_impute_config* cfg) {
   return impute_select(cfg->d, cfg->r, Switches().impute_v3, nullptr);
 }
 
-extern "C" int psmf_impute_run(const psmf_impute_config* cfg, const double* YorgInt, const uint8_t* M,
-                               const uint8_t* Mmiss, double* C, double* X, const double* V, const double* P,
-                               const double* Q, double rho, double* Epred, double* Efull, double* inside,
-                               double* Yrec, double* YrecL, double* YrecH, int32_t* status, float* elapsed_ms) {
+namespace {
+// psmf_impute_run (rho_rows == nullptr: R = rho I) and psmf_impute_run_rows (R = diag(rho_rows), entries not all equal; `rho` unused)
+int impute_run_impl(const char* who, const psmf_impute_config* cfg, const double* YorgInt, const uint8_t* M,
+                    const uint8_t* Mmiss, double* C, double* X, const double* V, const double* P,
+                    const double* Q, double rho, const double* rho_rows, double* Epred, double* Efull, double* inside,
+                    double* Yrec, double* YrecL, double* YrecH, int32_t* status, float* elapsed_ms) {
   using namespace psmf;
-  auto fail = [&](int code, const std::string& msg) { g_create_error = "psmf_impute_run: " + msg; return code; };
+  auto fail = [&](int code, const std::string& msg) { g_create_error = std::string(who) + ": " + msg; return code; };
   if (!cfg || !YorgInt || !M || !Mmiss || !C || !X || !V || !P || !Q || !Epred || !Efull || !inside)
     return fail(PSMF_ERR_ARG, "null argument");
   if (cfg->abi_version != PSMF_ABI_VERSION) return fail(PSMF_ERR_ARG, "ABI version mismatch");
@@ -616,7 +694,11 @@ extern "C" int psmf_impute_run(const psmf_impute_config* cfg, const double* Yorg
   if (cfg->want_bands && (!Yrec || !YrecL || !YrecH)) return fail(PSMF_ERR_ARG, "want_bands needs Yrec, YrecL, YrecH");
   const Switches sw;      // no handle here: read at entry, on every call
   size_t lds = 0;
-  const int sel = impute_select(d, r, sw.impute_v3, &lds);
+  const bool rw = rho_rows != nullptr;
+  const int sel = impute_select(d, r, sw.impute_v3, &lds, rw);
+  if (sel == 4 && rw)
+    return fail(PSMF_ERR_ARG, "per-row observation noise (unequal entries of diag(R)) runs on the one-workgroup kernels only, "
+                              "d <= 512 and r <= 16: this shape belongs to the masked per-step engine of the large-d handle, which takes R = rho I");
   if (sel == 4)       // beyond one workgroup's LDS: the replicas one after the other on the masked per-step engine (psmf_masked.hip)
     return impute_run_large(cfg, YorgInt, M, Mmiss, C, X, V, P, Q, rho, Epred, Efull, inside, Yrec, YrecL, YrecH, status, elapsed_ms);
   const bool v3 = sel >= 300;
@@ -632,6 +714,8 @@ extern "C" int psmf_impute_run(const psmf_impute_config* cfg, const double* Yorg
 
   int rc = PSMF_OK;
   const size_t nd = (size_t)n * d, bnd = (size_t)B * nd;
+  double *dRho = nullptr;
+  const void* kern = nullptr;
   double *dY = nullptr, *dC = nullptr, *dX = nullptr, *dV = nullptr, *dP = nullptr, *dQ = nullptr, *dEp = nullptr,
          *dEf = nullptr, *dIn = nullptr, *dYr = nullptr, *dYl = nullptr, *dYh = nullptr;
   uint8_t *dM = nullptr, *dMm = nullptr;
@@ -657,6 +741,10 @@ extern "C" int psmf_impute_run(const psmf_impute_config* cfg, const double* Yorg
     I_TRY(hipMalloc((void**)&dYl, bnd * 8));
     I_TRY(hipMalloc((void**)&dYh, bnd * 8));
   }
+  if (rw) {
+    I_TRY(hipMalloc((void**)&dRho, (size_t)d * 8));
+    I_TRY(hipMemcpy(dRho, rho_rows, (size_t)d * 8, hipMemcpyHostToDevice));
+  }
   I_TRY(hipMemcpy(dY, YorgInt, nd * 8, hipMemcpyHostToDevice));
   I_TRY(hipMemcpy(dM, M, bnd, hipMemcpyHostToDevice));
   I_TRY(hipMemcpy(dMm, Mmiss, bnd, hipMemcpyHostToDevice));
@@ -669,6 +757,7 @@ extern "C" int psmf_impute_run(const psmf_impute_config* cfg, const double* Yorg
   ip.sig = cfg->sig; ip.lambda0 = cfg->lambda0; ip.rho0 = rho;
   ip.Yorg = dY; ip.M = dM; ip.Mmiss = dMm; ip.C = dC; ip.X = dX; ip.V0 = dV; ip.P0 = dP; ip.Q0 = dQ;
   ip.Epred = dEp; ip.Efull = dEf; ip.inside = dIn; ip.Yrec = dYr; ip.YrecL = dYl; ip.YrecH = dYh; ip.err = dErr; ip.prof = nullptr;
+  ip.rho_rows = dRho;
   {
     bool iso = Q[0] > 0.0 && sw.impute_par;
     for (int i = 0; i < r && iso; ++i)
@@ -676,14 +765,12 @@ extern "C" int psmf_impute_run(const psmf_impute_config* cfg, const double* Yorg
         if (Q[i * r + c] != (i == c ? Q[0] : 0.0)) { iso = false; break; }
     ip.q_iso = iso ? 1 : 0;
   }
-  if (lds > 48 * 1024)
-    I_TRY(hipFuncSetAttribute(v3 ? impute3_kernel(d) : (const void*)psmf_impute_kernel2,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  kern = v3 ? impute3_kernel(d, rw) : (rw ? (const void*)psmf_impute_kernel2w : (const void*)psmf_impute_kernel2);
+  if (lds > 48 * 1024) I_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   I_TRY(hipEventCreate(&e0));
   I_TRY(hipEventCreate(&e1));
   I_TRY(hipEventRecord(e0, 0));
-  if (v3) { void* args[] = {&ip}; I_TRY(hipLaunchKernel(impute3_kernel(d), dim3(B), dim3(WG), args, lds, 0)); }
-  else hipLaunchKernelGGL(psmf_impute_kernel2, dim3(B), dim3(WG), lds, 0, ip);
+  { void* args[] = {&ip}; I_TRY(hipLaunchKernel(kern, dim3(B), dim3(WG), args, lds, 0)); }
   I_TRY(hipGetLastError());
   I_TRY(hipEventRecord(e1, 0));
   I_TRY(hipEventSynchronize(e1));
@@ -717,10 +804,43 @@ extern "C" int psmf_impute_run(const psmf_impute_config* cfg, const double* Yorg
   }
 done:
   hipFree(dY); hipFree(dM); hipFree(dMm); hipFree(dC); hipFree(dX); hipFree(dV); hipFree(dP); hipFree(dQ);
-  hipFree(dEp); hipFree(dEf); hipFree(dIn); hipFree(dErr); hipFree(dYr); hipFree(dYl); hipFree(dYh);
+  hipFree(dEp); hipFree(dEf); hipFree(dIn); hipFree(dErr); hipFree(dYr); hipFree(dYl); hipFree(dYh); hipFree(dRho);
   if (e0) hipEventDestroy(e0);
   if (e1) hipEventDestroy(e1);
 #undef I_TRY
   return rc;
+}
+}  // namespace
+
+extern "C" int psmf_impute_run(const psmf_impute_config* cfg, const double* YorgInt, const uint8_t* M,
+                               const uint8_t* Mmiss, double* C, double* X, const double* V, const double* P,
+                               const double* Q, double rho, double* Epred, double* Efull, double* inside,
+                               double* Yrec, double* YrecL, double* YrecH, int32_t* status, float* elapsed_ms) {
+  return impute_run_impl("psmf_impute_run", cfg, YorgInt, M, Mmiss, C, X, V, P, Q, rho, nullptr, Epred, Efull, inside, Yrec, YrecL, YrecH,
+                         status, elapsed_ms);
+}
+
+// R = diag(rho_rows), d entries shared by the replicas (the reference reads np.diag(R) row by row: ExperimentImpute/PSMF.py:70-72,
+// rPSMF.py:91-98, MLESMF.py:70-76).  Entries all equal -- and TMF, which ignores R (TMF.py:30-73) -- are psmf_impute_run itself: the
+// same kernels, the same bits.  Unequal entries run the row-noise instances of the one-workgroup kernels (psmf_impute_kernel3w<NG>,
+// psmf_impute_kernel2w: d <= 512, r <= 16); a shape beyond them is PSMF_ERR_ARG.
+extern "C" int psmf_impute_run_rows(const psmf_impute_config* cfg, const double* YorgInt, const uint8_t* M,
+                                    const uint8_t* Mmiss, double* C, double* X, const double* V, const double* P,
+                                    const double* Q, const double* rho_rows, double* Epred, double* Efull, double* inside,
+                                    double* Yrec, double* YrecL, double* YrecH, int32_t* status, float* elapsed_ms) {
+  const char* who = "psmf_impute_run_rows";
+  if (!cfg || !rho_rows) { g_create_error = std::string(who) + ": null argument"; return PSMF_ERR_ARG; }
+  if (cfg->abi_version != PSMF_ABI_VERSION) { g_create_error = std::string(who) + ": ABI version mismatch"; return PSMF_ERR_ARG; }
+  if (cfg->d < 1) { g_create_error = std::string(who) + ": need d >= 1"; return PSMF_ERR_ARG; }
+  bool uniform = true;
+  for (int i = 0; i < cfg->d; ++i) {
+    if (!std::isfinite(rho_rows[i]) || rho_rows[i] < 0.0) {
+      g_create_error = std::string(who) + ": the entries of diag(R) must be finite and >= 0 (row " + std::to_string(i) + ")";
+      return PSMF_ERR_ARG;
+    }
+    uniform = uniform && rho_rows[i] == rho_rows[0];
+  }
+  return impute_run_impl(who, cfg, YorgInt, M, Mmiss, C, X, V, P, Q, rho_rows[0], (uniform || cfg->method == 3) ? nullptr : rho_rows,
+                         Epred, Efull, inside, Yrec, YrecL, YrecH, status, elapsed_ms);
 }
 #endif  // PSMF_IMPUTE_KERNEL_ONLY

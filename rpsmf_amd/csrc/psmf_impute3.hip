@@ -39,13 +39,20 @@ namespace psmf {
 inline bool impute3_ok(int d, int r) { return d <= 80 && r <= IR - 2; }
 inline int impute3_groups(int d) { return d <= 12 ? 3 : (d <= 20 ? 5 : (d <= 32 ? 8 : (d <= 48 ? 12 : 20))); }     // template parameter NG: 4 NG rows of LDS
 
-inline size_t impute3_lds_bytes(int d, int r) {
+inline size_t impute3_lds_bytes(int d, int r, bool row_noise = false) {
   const size_t d4 = 4 * (size_t)impute3_groups(d);
-  const size_t doubles = 2 * d4 * IR + IR * IR + 3 * IR + 2 * d4 + 2 * 16 + 2 * 256 + 2 * 256 + 16 + 2;
+  const size_t doubles = 2 * d4 * IR + IR * IR + 3 * IR + 2 * d4 + 2 * 16 + 2 * 256 + 2 * 256 + 16 + 2 + (row_noise ? d4 : 0);
   return (doubles * 8 + 15) & ~(size_t)15;
 }
 
-template <int WV, int NG>
+// RW: per-row observation noise, R = diag(rho_i) (p.rho_rows; psmf_impute_run_rows).  The weights kappa_i = m_i / (c_t rho_i + s)
+// no longer factor out of the contractions: G_R = sum_i kappa_i c_i c_i^T, b = sum_i kappa_i e_i c_i, q = sum_i kappa_i e_i^2 are one
+// WEIGHTED augmented Gram (A operand kappa_i * row), which waves 0 and 1 form and consume; the plain one (G for <G, P + Q>, e^T e for
+// phi, and sum_i m_i rho_i in place of sum(m): rho_i is the A-side factor of the column of ones) goes to the waves that form eta.  Each
+// wave forms only what it consumes (wave 1 of the wide shapes both).  rho_i sits in registers for the whole run; the scalar that
+// R = omega R multiplies every column (rPSMF.py:134), c_t, lives where rho lives in the uniform instances (wave 0, ssc[8]).  RW = false
+// compiles to the code it was before the parameter existed.
+template <int WV, int NG, bool RW = false>
 __device__ __forceinline__ void impute3_wave(const ImputeParams& p) {
   int nbar = 0;          // barriers this wave has executed (imp_barrier_check, psmf_impute.hip)
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -65,6 +72,7 @@ __device__ __forceinline__ void impute3_wave(const ImputeParams& p) {
   double* sPP = sW + 2 * 256;                 // 2 x 256: P_{t-1} + Q_t, MFMA output layout (for <G, P + Q>)
   double* sred = sPP + 2 * 256;               // 16: end-of-pass reductions
   int* errflag = reinterpret_cast<int*>(sred + 16);
+  double* srho = sred + 16 + 2;               // (RW) D4: diag(R); padding rows 1
 
   const double* Yorg = p.Yorg;
   const uint8_t* Mk = p.M + (size_t)rep * n * d;
@@ -72,6 +80,8 @@ __device__ __forceinline__ void impute3_wave(const ImputeParams& p) {
   double* Cg = p.C + (size_t)rep * d * r;
   double* Xg = p.X + (size_t)rep * n * r;
 
+  if constexpr (RW)
+    for (int idx = tid; idx < D4; idx += WG) srho[idx] = idx < d ? p.rho_rows[idx] : 1.0;
   for (int idx = tid; idx < 2 * D4 * IR; idx += WG) {
     const int i = (idx >> 4) % D4, l = idx & 15;
     sC[idx] = (i < d && l < r) ? Cg[i * r + l] : ((i < d && l == r + (r & 1) + 1) ? 1.0 : 0.0);
@@ -85,7 +95,7 @@ __device__ __forceinline__ void impute3_wave(const ImputeParams& p) {
   if (tid == 0) *errflag = 0;
   const double dd = (double)d, idd = 1.0 / dd;
   const bool sgd = p.method >= 2;     // MLE-SMF / TMF: gradient step on C along x_p, no V
-  const bool tmf = p.method == 3;
+  const bool tmf = !RW && p.method == 3;      // (TMF ignores R: it never runs a row-noise instance)
   const bool par = p.q_iso && !tmf;   // Q = q I: the two inversions of a column are independent (see version 2)
   const int r2 = r + (r & 1);         // sweep size: even, identity-padded; also the tile column of e / of kappa b
   // where the scalar by-products of the Gram sit: element (r2, r2) = e^T e, (r2 + 1, r2 + 1) = sum(m)
@@ -108,7 +118,8 @@ __device__ __forceinline__ void impute3_wave(const ImputeParams& p) {
   if (WV < 2) sw16k_init(swk, lk, lr);
   // wave 0: P, Q in the MFMA output layout (element (lk + 4 q, lr)), rho, lambda, q
   double Pm[4] = {0.0, 0.0, 0.0, 0.0}, Qm[4] = {0.0, 0.0, 0.0, 0.0};
-  double rho = p.rho0, lam = p.lambda0, qv = p.Q0[0], iqv = 1.0;
+  const double rho_start = RW ? 1.0 : p.rho0;      // RW: rho is c_t, the factor omega has put on R since the start of the pass
+  double rho = rho_start, lam = p.lambda0, qv = p.Q0[0], iqv = 1.0;
   if (WV == 0) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -131,6 +142,15 @@ __device__ __forceinline__ void impute3_wave(const ImputeParams& p) {
   const bool rown = ROWS && rowi < d && (WIDE || lane < 32);
   imp_barrier_full(nbar);
   IMP_T0();
+  // (RW) rho_i of the rows this lane feeds to the MFMAs (row 4 g + lk), and the same as the factor of the column of ones (lr == r2 + 1)
+  double rv[RW ? NG : 1], rf[RW ? NG : 1];
+  if constexpr (RW) {
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+      rv[g] = srho[4 * g + lk];
+      rf[g] = lr == r2 + 1 ? rv[g] : 1.0;
+    }
+  }
   for (int it = 0; it < p.n_iter; ++it) {
     const double gam = 1e-6 / pow((double)(it + 1), 0.7);     // MLESMF.py:59-60, TMF.py:46-48
     if (WV == 0) {
@@ -142,7 +162,7 @@ __device__ __forceinline__ void impute3_wave(const ImputeParams& p) {
           const int a = in ? i * r + lr : 0, b = in ? lr * r + i : 0;
           Qm[q] = in ? 0.5 * (p.Q0[a] + p.Q0[b]) : 0.0;
         }
-        rho = p.rho0;
+        rho = rho_start;
         lam = p.lambda0;
         qv = p.Q0[0];
       }
@@ -257,33 +277,71 @@ __device__ __forceinline__ void impute3_wave(const ImputeParams& p) {
         for (int q = 0; q < 4; ++q) PPv[q] = sPP[cur * 256 + q * 64 + lane];
       }
       IMP_T(2);
-      // ---- augmented masked Gram [C | e | 1]^T diag(m) [C | e | 1], two accumulators ----
-      f64x4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
+      double G[4], Gt[4], Bq[4];      // G: what the inversions take (RW: G_R itself); Gt: the plain Gram, for the trace
+      double ee = 0.0, msum = 0.0;    // RW: ee is q = sum kappa_i e_i^2 on wave 0, msum is sum m_i rho_i
+      double kappa = 1.0;
+      if constexpr (!RW) {
+        // ---- augmented masked Gram [C | e | 1]^T diag(m) [C | e | 1], two accumulators ----
+        f64x4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-      for (int g = 0; g < NG; ++g) {
-        if (g & 1) acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(mk[g] * cv[g], cv[g], acc1, 0, 0, 0);
-        else acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(mk[g] * cv[g], cv[g], acc0, 0, 0, 0);
-      }
-      double G[4], Bq[4];
+        for (int g = 0; g < NG; ++g) {
+          if (g & 1) acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(mk[g] * cv[g], cv[g], acc1, 0, 0, 0);
+          else acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(mk[g] * cv[g], cv[g], acc0, 0, 0, 0);
+        }
 #pragma unroll
-      for (int q = 0; q < 4; ++q) { Bq[q] = acc0[q] + acc1[q]; G[q] = finq[q] * Bq[q]; }   // b_i = (C^T e)_i: column r of rows i
-      double ee = 0.0, msum = 0.0;
-      if (WV >= 2 || ROWS || (WV == 0 && p.robust)) {
-        const double ee_r = rq_e == 0 ? Bq[0] : (rq_e == 1 ? Bq[1] : (rq_e == 2 ? Bq[2] : Bq[3]));
-        ee = readlane_f64(ee_r, ln_e);
+        for (int q = 0; q < 4; ++q) { Bq[q] = acc0[q] + acc1[q]; G[q] = finq[q] * Bq[q]; Gt[q] = G[q]; }   // b_i = (C^T e)_i: column r of rows i
+        if (WV >= 2 || ROWS || (WV == 0 && p.robust)) {
+          const double ee_r = rq_e == 0 ? Bq[0] : (rq_e == 1 ? Bq[1] : (rq_e == 2 ? Bq[2] : Bq[3]));
+          ee = readlane_f64(ee_r, ln_e);
+        }
+        if (WV >= 2 || ROWS) {
+          const double ms_r = rq_m == 0 ? Bq[0] : (rq_m == 1 ? Bq[1] : (rq_m == 2 ? Bq[2] : Bq[3]));
+          msum = readlane_f64(ms_r, ln_m);
+        }
+        // weights of the observed rows: PSMF / rPSMF 1 / (rho + s) (PSMF.py:71-72), MLE-SMF 1 / rho (MLESMF.py:70), TMF 1
+        kappa = tmf ? 1.0 : fast_rcp(sgd ? rho_t : rho_t + s);
+      } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { G[q] = 0.0; Gt[q] = 0.0; Bq[q] = 0.0; }
+        if constexpr (WV >= 2 || ROWS) {
+          // ---- the plain product: G, e^T e at (r2, r2), sum_i m_i rho_i at (r2 + 1, r2 + 1) ----
+          f64x4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+          for (int g = 0; g < NG; ++g) {
+            if (g & 1) acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(mk[g] * rf[g] * cv[g], cv[g], acc1, 0, 0, 0);
+            else acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(mk[g] * rf[g] * cv[g], cv[g], acc0, 0, 0, 0);
+          }
+          double Bp[4];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) { Bp[q] = acc0[q] + acc1[q]; Gt[q] = finq[q] * Bp[q]; }
+          const double ee_r = rq_e == 0 ? Bp[0] : (rq_e == 1 ? Bp[1] : (rq_e == 2 ? Bp[2] : Bp[3]));
+          ee = readlane_f64(ee_r, ln_e);
+          const double ms_r = rq_m == 0 ? Bp[0] : (rq_m == 1 ? Bp[1] : (rq_m == 2 ? Bp[2] : Bp[3]));
+          msum = readlane_f64(ms_r, ln_m);
+        }
+        if constexpr (WV < 2) {
+          // ---- the weighted product, kappa_i = m_i / (c_t rho_i + s) (MLE-SMF: m_i / rho_i): G_R, b in column r2, q at (r2, r2) ----
+          f64x4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+          for (int g = 0; g < NG; ++g) {
+            const double wk = mk[g] * fast_rcp(sgd ? rv[g] : fma(rho_t, rv[g], s));
+            if (g & 1) acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(wk * cv[g], cv[g], acc1, 0, 0, 0);
+            else acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(wk * cv[g], cv[g], acc0, 0, 0, 0);
+          }
+#pragma unroll
+          for (int q = 0; q < 4; ++q) { Bq[q] = acc0[q] + acc1[q]; G[q] = finq[q] * Bq[q]; }
+          if (WV == 0 && p.robust) {
+            const double q_r = rq_e == 0 ? Bq[0] : (rq_e == 1 ? Bq[1] : (rq_e == 2 ? Bq[2] : Bq[3]));
+            ee = readlane_f64(q_r, ln_e);
+          }
+        }
       }
-      if (WV >= 2 || ROWS) {
-        const double ms_r = rq_m == 0 ? Bq[0] : (rq_m == 1 ? Bq[1] : (rq_m == 2 ? Bq[2] : Bq[3]));
-        msum = readlane_f64(ms_r, ln_m);
-      }
-      // weights of the observed rows: PSMF / rPSMF 1 / (rho + s) (PSMF.py:71-72), MLE-SMF 1 / rho (MLESMF.py:70), TMF 1
-      const double kappa = tmf ? 1.0 : fast_rcp(sgd ? rho_t : rho_t + s);
       // eta, N, phi: the updating waves form them for themselves
       double eta = 0.0, N = 0.0, phi = 1.0;
       if (WV >= 2 || ROWS) {
         double tr = 0.0;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) tr = fma(G[q], PPv[q], tr);
+        for (int q = 0; q < 4; ++q) tr = fma(Gt[q], PPv[q], tr);
         const double trGP = wave_sum_f64_dpp(tr);
         eta = (rho_t * msum + trGP) * idd;     // divide by d, not by #observed (PSMF.py:77)
         N = s + eta;
@@ -438,8 +496,26 @@ __global__ __launch_bounds__(WG) void psmf_impute_kernel3(ImputeParams p) {
   else impute3_wave<3, NG>(p);
 }
 
-inline const void* impute3_kernel(int d) {
+// the same loop with per-row observation noise (psmf_impute_run_rows)
+template <int NG>
+__global__ __launch_bounds__(WG) void psmf_impute_kernel3w(ImputeParams p) {
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (wv == 0) impute3_wave<0, NG, true>(p);
+  else if (wv == 1) impute3_wave<1, NG, true>(p);
+  else if (wv == 2) impute3_wave<2, NG, true>(p);
+  else impute3_wave<3, NG, true>(p);
+}
+
+inline const void* impute3_kernel(int d, bool row_noise = false) {
   const int ng = impute3_groups(d);
+  if (row_noise)
+    switch (ng) {
+      case 3: return (const void*)psmf_impute_kernel3w<3>;
+      case 5: return (const void*)psmf_impute_kernel3w<5>;
+      case 8: return (const void*)psmf_impute_kernel3w<8>;
+      case 12: return (const void*)psmf_impute_kernel3w<12>;
+      default: return (const void*)psmf_impute_kernel3w<20>;
+    }
   switch (ng) {
     case 3: return (const void*)psmf_impute_kernel3<3>;
     case 5: return (const void*)psmf_impute_kernel3<5>;

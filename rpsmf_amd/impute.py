@@ -22,16 +22,32 @@ __all__ = ["ProbabilisticSequentialMatrixFactorizer", "robust_PSMF", "stochastic
 METHODS = {"psmf": 0, "rpsmf": 1, "mle_smf": 2, "tmf": 3}
 
 
-def _uniform_rho(R, d):
+ROW_NOISE_MAX_D, ROW_NOISE_MAX_R = 512, 16     # the one-workgroup kernels (psmf_impute_kernel_id: 2 or 300 + NG)
+
+
+def _row_noise(R, d):
+    """The observation noise the caller passed, as (rho, rows): a scalar, a (d,) vector = diag(R), or a (d, d) matrix whose
+    off-diagonal is zero -- the reference reads np.diag(R) row by row (ExperimentImpute/PSMF.py:70-72, rPSMF.py:91-98,
+    MLESMF.py:70-76).  A scalar, and a vector or matrix with a constant diagonal, give (rho, None): psmf_impute_run with
+    R = rho I (the same bits whichever form was passed).  Unequal entries give (None, rows): psmf_impute_run_rows."""
     if np.ndim(R) == 0:
-        return float(R)
+        return float(R), None
     R = np.asarray(R, dtype=float)
-    dg = R if R.ndim == 1 else np.diagonal(R)
+    if R.ndim == 1:
+        dg = R
+    elif R.ndim == 2 and R.shape[0] == R.shape[1]:
+        dg = np.diagonal(R)
+    else:
+        raise ValueError(f"R must be a scalar, a ({d},) vector or a ({d}, {d}) diagonal matrix, not an array of shape {R.shape}")
+    if dg.shape[0] != d:
+        raise ValueError(f"R has {dg.shape[0]} diagonal entries, the data has d = {d} rows")
     if R.ndim == 2 and np.count_nonzero(R) != np.count_nonzero(dg):
         raise NotImplementedError("the device path assumes a diagonal R (as the reference's comments do)")
-    if not np.all(dg == dg[0]):
-        raise NotImplementedError("the device path needs R = rho * I")
-    return float(dg[0])
+    if not np.all(np.isfinite(dg)) or np.any(dg < 0):
+        raise ValueError("the entries of diag(R) must be finite and >= 0")
+    if np.all(dg == dg[0]):
+        return float(dg[0]), None
+    return None, np.ascontiguousarray(dg, dtype=np.float64)
 
 
 def kernel_name(d, r):
@@ -92,7 +108,8 @@ def _impute_batch_devices(devices, YorgInt, M, Mmiss, C0, X0, *args, **kw):
 def impute_batch(YorgInt, M, Mmiss, C0, X0, V, Q, R, P, sig, Iter, robust=False, lambda0=0.0, device=0,
                  want_bands=False, method=None):
     """Run `batch` replicas.  Reference layouts: YorgInt (d, n); M, Mmiss (batch, d, n);
-    C0 (batch, d, r); X0 (batch, r, n).  Returns a dict with Epred, Efull (batch, Iter),
+    C0 (batch, d, r); X0 (batch, r, n).  R: a scalar rho (R = rho I), a (d,) vector diag(R) or a (d, d) diagonal matrix, shared by
+    the replicas; unequal entries (per-row observation noise) need d <= 512 and r <= 16.  Returns a dict with Epred, Efull (batch, Iter),
     inside (batch,), C (batch, d, r), X (batch, r, n), elapsed_ms and, if requested,
     Yrec / YrecL / YrecH (batch, d, n).  `device`: a HIP device ordinal, or a sequence of them -- the replicas are then dealt
     over those devices in contiguous slices (replica_slices) and run side by side."""
@@ -115,6 +132,13 @@ def impute_batch(YorgInt, M, Mmiss, C0, X0, V, Q, R, P, sig, Iter, robust=False,
     r = C0.shape[2]
     if M.shape != (B, d, n) or Mmiss.shape != (B, d, n) or C0.shape != (B, d, r) or X0.shape != (B, r, n):
         raise ValueError("inconsistent shapes")
+    rho, rho_rows = _row_noise(R, d)
+    if rho_rows is not None and meth == METHODS["tmf"]:
+        rho, rho_rows = float(rho_rows[0]), None          # TMF ignores R (TMF.py:30-73)
+    if rho_rows is not None and kernel_name(d, r) == "masked per-step engine":
+        raise NotImplementedError(
+            f"per-row observation noise (unequal entries of diag(R)) runs on the one-workgroup kernels only: d <= {ROW_NOISE_MAX_D} and "
+            f"r <= {ROW_NOISE_MAX_R}; d = {d}, r = {r} belongs to the masked per-step engine, which takes R = rho * I")
     # time-major device layout: column t of the reference's (d, n) arrays is row t
     Yt = np.ascontiguousarray(YorgInt.T)
     Mt = np.ascontiguousarray(np.transpose(M != 0, (0, 2, 1)).astype(np.uint8))
@@ -133,9 +157,10 @@ def impute_batch(YorgInt, M, Mmiss, C0, X0, V, Q, R, P, sig, Iter, robust=False,
     status = np.zeros(B, dtype=np.int32)
     dp = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
     up = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint8))
-    rc = lib.psmf_impute_run(C.byref(cfg), dp(Yt), up(Mt), up(Mmt), dp(Cb), dp(Xb), dp(Vm), dp(Pm), dp(Qm),
-                             _uniform_rho(R, d), dp(Epred), dp(Efull), dp(inside), dp(bands[0]), dp(bands[1]),
-                             dp(bands[2]), status.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(ms))
+    run, noise = (lib.psmf_impute_run, rho) if rho_rows is None else (lib.psmf_impute_run_rows, dp(rho_rows))
+    rc = run(C.byref(cfg), dp(Yt), up(Mt), up(Mmt), dp(Cb), dp(Xb), dp(Vm), dp(Pm), dp(Qm),
+             noise, dp(Epred), dp(Efull), dp(inside), dp(bands[0]), dp(bands[1]),
+             dp(bands[2]), status.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(ms))
     if rc != _capi.OK:
         msg = lib.psmf_last_error(None).decode()
         if rc == _capi.ERR_NUMERIC:
@@ -146,7 +171,8 @@ def impute_batch(YorgInt, M, Mmiss, C0, X0, V, Q, R, P, sig, Iter, robust=False,
     # a replica whose r x r system broke down has NaN results and status != 0; the others are complete (the reference's
     # repeats loop records NaN for such a repeat and carries on, ExperimentImpute/rPSMF.py:236-243)
     out = dict(Epred=Epred, Efull=Efull, inside=inside, C=Cb, X=np.transpose(Xb, (0, 2, 1)), elapsed_ms=ms.value, status=status,
-               kernel=kernel_name(d, r))
+               kernel=kernel_name(d, r) if rho_rows is None else
+               kernel_name(d, r).replace("kernel3<", "kernel3w<").replace("kernel2", "kernel2w"))     # the row-noise instances
     if want_bands:
         out.update(Yrec=np.transpose(bands[0], (0, 2, 1)), YrecL=np.transpose(bands[1], (0, 2, 1)),
                    YrecH=np.transpose(bands[2], (0, 2, 1)))
