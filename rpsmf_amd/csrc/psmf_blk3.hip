@@ -149,7 +149,111 @@ struct F3Blk {
   double* Bcoef;
   const double* XG;
   const double* Aprev;    // nullptr: the previous block of the same launch left its coefficients in sA
+  int from_lds, to_lds;   // chain carry (F3Carry): the r x r state arrives from / leaves for the next block through LDS, not DevState
 };
+
+// Chain carry (BlockParams::carry, filter3 only).  Between two blocks of ONE launch nobody but this workgroup reads the r x r
+// state, so it does not travel through the DevState dump (global stores that the hand-off has to drain, an L2 round trip to read
+// them back): every wave parks what it holds in LDS that is idle at a block boundary and picks it up in its next prologue.
+//   Xc (wave c's column of its iterate)   dump, parity 0, the wave's own slot            [e][lane]
+//   Xa (its float32 A operands)           dumpP, the wave's own slot of both parities    [e >> 3][.][e & 7][lane]
+//   G (wave 0), W (wave 2)                dump, parity 1: the slots of waves 0-1 / 2-3   [e][lane]   (as the dump: one writer each)
+//   V (wave 4), the scalars               the sweep images (nothing sweeps at a boundary)
+//   mu_bar                                stays in L.mub
+// The dump, the images and dumpP are read for the last time before the barrier of the block end and written next behind the
+// first step's B1; the K assembly touches none of them.  DevState gets the state where the launch ends (f3_ns_dump, f3_v0_dump).
+enum { F3C_IQW = 0, F3C_IOM, F3C_PSCALE, F3C_Q, F3C_RHO, F3C_LAM, F3C_PHI, F3C_OMEGA, F3C_EE, F3C_S, F3C_ETA, F3C_N };
+struct F3Carry {
+  double* Xc;       // [4 waves][8][64]
+  float* Xa;        // see f3_carry_xa
+  double* G;        // [16][64]
+  double* W;        // [16][64]
+  double* V;        // [16][64]
+  double* sc;       // F3C_*
+};
+__device__ __forceinline__ F3Carry f3_carry(const F3Lds& L) {
+  F3Carry c;
+  c.Xc = L.dump;
+  c.Xa = L.dumpP;
+  c.G = L.dump + 4 * 8 * 64;
+  c.W = L.dump + 6 * 8 * 64;
+  c.V = L.img;
+  c.sc = L.img + 16 * 64;
+  return c;
+}
+__device__ __forceinline__ int f3_carry_xa(const int role, const int e, const int lane) { return (((e >> 3) * 4 + role) * 8 + (e & 7)) * 64 + lane; }
+
+// The inversion waves' share of the DevState dump (valid while ns_valid == 3): what a later launch, or the host, starts from
+__device__ __forceinline__ void f3_ns_dump(DevState* st, const int role, const int lane, const double (&Xc)[8], const float (&Xa)[16],
+                                           const double (&G)[16], const double (&Wf)[16], const double iq_w) {
+  // the state for the next block, as held: coalesced rows
+#pragma unroll
+  for (int e = 0; e < 8; ++e) st->f3_Xc[role][e * 64 + lane] = Xc[e];
+#pragma unroll
+  for (int e = 0; e < 16; ++e) st->f3_Xa[role][e * 64 + lane] = Xa[e];
+  if (role == 0) {
+#pragma unroll
+    for (int e = 0; e < 16; ++e) st->f3_G[e * 64 + lane] = G[e];
+    if (lane == 0) st->f3_sc[0] = iq_w;
+  }
+  if (role == 2) {
+#pragma unroll
+    for (int e = 0; e < 16; ++e) st->f3_W[e * 64 + lane] = Wf[e];
+  }
+}
+
+// Wave 4's share: V, mu and the scalars.  sc: F3C_* (F3C_IQW unused).  last: the row-major V and Q as well (end of a run)
+__device__ __forceinline__ void f3_v0_dump(DevState* st, const F3Lds& L, const int r, const int lane, const long long kdone, const bool last,
+                                           const double* V, const double* sc) {
+  const int j = lane & 31, hf = lane >> 5;
+  const double q = sc[F3C_Q];
+#pragma unroll
+  for (int t = 0; t < 16; ++t) st->f3_V[t * 64 + lane] = V[t];
+  if (last) {
+#pragma unroll
+    for (int t = 0; t < 16; ++t) {
+      const int i = 16 * hf + t;
+      if (i < r && j < r) {
+        st->V[i * r + j] = V[t];
+        st->Q[i * r + j] = (i == j) ? q : 0.0;
+      }
+    }
+  } else if (hf == 0 && j < r) {
+    st->Q[j * r + j] = q;             // Q = q I: the diagonal is what the next block reads (Q[0])
+  }
+  if (lane < r) st->mu[lane] = L.mub[lane];
+  if (lane == 0) {
+    st->f3_sc[1] = sc[F3C_IOM]; st->f3_sc[2] = sc[F3C_PSCALE];
+    st->k = kdone;
+    st->rho = sc[F3C_RHO]; st->lam = sc[F3C_LAM]; st->phi = sc[F3C_PHI]; st->omega = sc[F3C_OMEGA]; st->ee = sc[F3C_EE];
+    st->s_done = sc[F3C_S]; st->eta_done = sc[F3C_ETA]; st->N_done = sc[F3C_N];
+    st->ns_valid = 3;
+  }
+}
+
+// A chained launch that ends between two blocks (dead hand-off): the state of the blocks completed, parked in LDS, goes to
+// DevState as a block that does not carry would have left it.  Called by the whole workgroup behind a barrier.
+__device__ __forceinline__ void f3_carry_flush(const BlockParams& b, const F3Lds& L, const long long kdone, const int tid) {
+  DevState* st = b.sp.st;
+  const int role = tid >> 6, lane = tid & 63;
+  const F3Carry cy = f3_carry(L);
+  if (role < 4) {
+    double Xc[8], G[16], Wf[16];
+    float Xa[16];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) Xc[e] = cy.Xc[role * 512 + e * 64 + lane];
+#pragma unroll
+    for (int e = 0; e < 16; ++e) { Xa[e] = cy.Xa[f3_carry_xa(role, e, lane)]; G[e] = cy.G[e * 64 + lane]; Wf[e] = cy.W[e * 64 + lane]; }
+    f3_ns_dump(st, role, lane, Xc, Xa, G, Wf, cy.sc[F3C_IQW]);
+  } else if (role == 4) {
+    double V[16], sc[12];
+#pragma unroll
+    for (int t = 0; t < 16; ++t) V[t] = cy.V[t * 64 + lane];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) sc[i] = cy.sc[i];
+    f3_v0_dump(st, L, b.sp.r, lane, kdone, false, V, sc);
+  }
+}
 
 __device__ __forceinline__ void f3_assemble_K(const BlockParams& b, const F3Blk& k, const F3Lds& L, const int r, const int tid) {
   const int nb = k.nb, lane = tid & 63, w = tid >> 6, lrow = lane >> 4, lcol = lane & 15;
@@ -160,8 +264,9 @@ __device__ __forceinline__ void f3_assemble_K(const BlockParams& b, const F3Blk&
   // every global load of the assembly is issued before the first barrier (one L2 round trip, not two)
   double gv[2], yy[5];
 #pragma unroll
-  for (int u = 0; u < 2; ++u) gv[u] = st->f3_G[(w + 8 * u) * 64 + lane];     // tracked G of the previous block (T-layout dump:
-                                                                               // an assembled block always follows a filter3 block)
+  for (int u = 0; u < 2; ++u)                                                  // tracked G of the previous block (T-layout dump: an
+    gv[u] = k.from_lds ? f3_carry(L).G[(w + 8 * u) * 64 + lane]                // assembled block always follows a filter3 block);
+                       : st->f3_G[(w + 8 * u) * 64 + lane];                    // chain carry: where wave 0 parked it
 #pragma unroll
   for (int u = 0; u < 5; ++u) {
     const int idx = min(tid + u * F3_NT, nb * nb - 1), q = idx / nb, q2 = idx - q * nb;
@@ -327,7 +432,9 @@ __device__ __forceinline__ void f3_ns_program(const BlockParams& b, const F3Blk&
   double G[16], Wf[16], Xc[8];
   float Xa[16];                             // float32 A operands of the correction product (see f3_ns_iter)
   const int pcol = (lcol >> 2) + 4 * (lcol & 3);     // pi(lcol)       // Wf: W of the last step (zero outside r x r): Lbar = (I / q - W / q^2) / omega
-  const double q0 = st->Q[0];
+  const bool from_lds = k.from_lds != 0;     // chain carry (implies carried): nothing below reads DevState
+  const F3Carry cy = f3_carry(L);
+  const double q0 = from_lds ? 0.0 : st->Q[0];
   F3Mask<FULL> mk;
   const int rt = FULL == 2 ? r : r - 16;               // extent of the partially filled tile (tile 0 when r <= 16, else tile 1)
   mk.c1 = lcol < rt;
@@ -343,7 +450,9 @@ __device__ __forceinline__ void f3_ns_program(const BlockParams& b, const F3Blk&
         const bool in = row < r && col < r;
         const int e = (ti * 2 + tj) * 4 + qq;
         G[e] = in ? L.sK[row * RB + col] : 0.0;                              // G_0: exact Gram of the stored C / tracked G
-        if (carried) {
+        if (from_lds) {
+          Wf[e] = cy.W[e * 64 + lane];
+        } else if (carried) {
           Wf[e] = st->f3_W[e * 64 + lane];
         } else {
           // the block starts from Lbar itself (just formed by the sweep): as a W, q I - q^2 Lbar
@@ -354,12 +463,14 @@ __device__ __forceinline__ void f3_ns_program(const BlockParams& b, const F3Blk&
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     const int row = 16 * (e >> 2) + lrow + 4 * (e & 3);
-    Xc[e] = carried ? st->f3_Xc[role][e * 64 + lane] : (row == 16 * C + lcol ? 1.0 : 0.0);
+    if (from_lds) Xc[e] = cy.Xc[role * 512 + e * 64 + lane];
+    else Xc[e] = carried ? st->f3_Xc[role][e * 64 + lane] : (row == 16 * C + lcol ? 1.0 : 0.0);
   }
 #pragma unroll
   for (int e = 0; e < 16; ++e) {
     const int row = 16 * ((e >> 2) & 1) + lrow + 4 * (e & 3), cp = 16 * (e >> 3) + pcol;
-    Xa[e] = carried ? st->f3_Xa[role][e * 64 + lane] : (row == cp ? 1.f : 0.f);
+    if (from_lds) Xa[e] = cy.Xa[f3_carry_xa(role, e, lane)];
+    else Xa[e] = carried ? st->f3_Xa[role][e * 64 + lane] : (row == cp ? 1.f : 0.f);
   }
   if (isX) {
     // <G_0, P> and tr G_0 of the own column, for eta of the first step (Pbar_1 = P + q I); carried: P = beta omega P+
@@ -449,7 +560,9 @@ __device__ __forceinline__ void f3_ns_program(const BlockParams& b, const F3Blk&
   F3Ctl ctl = {carried, 0, 0, 0, 0, 0};
   int w_par = 0;
   bool w_from_img = false, fetch_late = false;
-  double iq_w = carried ? st->f3_sc[0] : 1.0 / q0;          // 1 / q that Wf was formed with
+  double iq_w;                                              // 1 / q that Wf was formed with
+  if (from_lds) iq_w = cy.sc[F3C_IQW];
+  else iq_w = carried ? st->f3_sc[0] : 1.0 / q0;
   double kap_prev = 1.0;                                    // kappa of the step that just ended (start predictor)
   bool smw_ok = false;                                      // that step left a = Z h, b = Z w behind (not the first step of a block)
   BLK_T0();
@@ -655,19 +768,23 @@ __device__ __forceinline__ void f3_ns_program(const BlockParams& b, const F3Blk&
   if (k.nb > 0) F3_W_AND_TRACES();
   f3_barrier();                       // wave 4 has published pscale and 1 / omega of the last step
   const double ps = L.sc[F3_PSCALE], iom = L.sc[F3_IOM];
-  // the state for the next block, as held: coalesced rows
+  if (k.to_lds) {
+    // chain carry: the next block of this launch picks the state up from LDS (every reader of the dump is behind the barrier above)
 #pragma unroll
-  for (int e = 0; e < 8; ++e) st->f3_Xc[role][e * 64 + lane] = Xc[e];
+    for (int e = 0; e < 8; ++e) cy.Xc[role * 512 + e * 64 + lane] = Xc[e];
 #pragma unroll
-  for (int e = 0; e < 16; ++e) st->f3_Xa[role][e * 64 + lane] = Xa[e];
-  if (role == 0) {
+    for (int e = 0; e < 16; ++e) cy.Xa[f3_carry_xa(role, e, lane)] = Xa[e];
+    if (role == 0) {
 #pragma unroll
-    for (int e = 0; e < 16; ++e) st->f3_G[e * 64 + lane] = G[e];
-    if (lane == 0) st->f3_sc[0] = iq_w;
-  }
-  if (role == 2) {
+      for (int e = 0; e < 16; ++e) cy.G[e * 64 + lane] = G[e];
+      if (lane == 0) cy.sc[F3C_IQW] = iq_w;
+    }
+    if (role == 2) {
 #pragma unroll
-    for (int e = 0; e < 16; ++e) st->f3_W[e * 64 + lane] = Wf[e];
+      for (int e = 0; e < 16; ++e) cy.W[e * 64 + lane] = Wf[e];
+    }
+  } else {
+    f3_ns_dump(st, role, lane, Xc, Xa, G, Wf, iq_w);
   }
   if (k.last) {
 #pragma unroll
@@ -715,13 +832,21 @@ __device__ __forceinline__ void f3_v_program(const BlockParams& b, const F3Blk& 
   for (int i = 0; i < 32; ++i) pr[i] = 0.0;
   // wave 4's running scalars (every lane holds the same values)
   double kappa = 0.0, Nk = 0.0, invN = 0.0, s_k = 0.0, eta_k = 0.0, ee_k = 0.0, phi = 1.0, omega = 1.0, pscale = 1.0, wj = 0.0;
-  double q = st->Q[0];                  // Q = q I (checked by the host)
-  double rho = st->rho, lam = st->lam;
+  const bool from_lds = k.from_lds != 0;       // chain carry (implies carried): nothing below reads DevState
+  const F3Carry cy = f3_carry(L);
+  double q, rho, lam;
+  if (from_lds) { q = cy.sc[F3C_Q]; rho = cy.sc[F3C_RHO]; lam = cy.sc[F3C_LAM]; }
+  else { q = st->Q[0]; rho = st->rho; lam = st->lam; }      // Q = q I (checked by the host)
   double iom0 = 1.0;                    // 1 / omega of the last step of the previous block (carried W is not yet divided by it)
   double kap7 = 1.0;                    // wave 7: kappa of the step that just ended
   if (isV0) {
     const int j = lane & 31, hf = lane >> 5;
-    if (carried) {
+    if (from_lds) {
+#pragma unroll
+      for (int t = 0; t < 16; ++t) pr[t] = cy.V[t * 64 + lane];
+      iom0 = cy.sc[F3C_IOM];
+      pscale = cy.sc[F3C_PSCALE];
+    } else if (carried) {
 #pragma unroll
       for (int t = 0; t < 16; ++t) pr[t] = st->f3_V[t * 64 + lane];
       iom0 = st->f3_sc[1];
@@ -943,30 +1068,21 @@ __device__ __forceinline__ void f3_v_program(const BlockParams& b, const F3Blk& 
   }
   f3_barrier();
   if (isV0) {
-    const int j = lane & 31, hf = lane >> 5;
+    double sc[12];
+    sc[F3C_IQW] = 0.0; sc[F3C_IOM] = L.sc[F3_IOM]; sc[F3C_PSCALE] = pscale; sc[F3C_Q] = q; sc[F3C_RHO] = rho; sc[F3C_LAM] = lam;
+    sc[F3C_PHI] = phi; sc[F3C_OMEGA] = omega; sc[F3C_EE] = ee_k; sc[F3C_S] = s_k; sc[F3C_ETA] = eta_k; sc[F3C_N] = Nk;
+    if (k.to_lds) {
+      // chain carry: V and the scalars wait in the sweep images (mu_bar stays in L.mub); sc[F3C_IQW] is wave 0's
 #pragma unroll
-    for (int t = 0; t < 16; ++t) st->f3_V[t * 64 + lane] = pr[t];
-    if (k.last) {
+      for (int t = 0; t < 16; ++t) cy.V[t * 64 + lane] = pr[t];
+      if (lane == 0) {
 #pragma unroll
-      for (int t = 0; t < 16; ++t) {
-        const int i = 16 * hf + t;
-        if (i < r && j < r) {
-          st->V[i * r + j] = pr[t];
-          st->Q[i * r + j] = (i == j) ? q : 0.0;
-        }
+        for (int i = 1; i < 12; ++i) cy.sc[i] = sc[i];
       }
-    } else if (hf == 0 && j < r) {
-      st->Q[j * r + j] = q;             // Q = q I: the diagonal is what the next block reads (Q[0])
+    } else {
+      f3_v0_dump(st, L, r, lane, k.k0 + k.nb, k.last != 0, pr, sc);
     }
-    if (lane < r) st->mu[lane] = L.mub[lane];
-    if (lane == 0) {
-      st->f3_sc[1] = L.sc[F3_IOM]; st->f3_sc[2] = pscale;
-      st->k = k.k0 + k.nb;
-      st->rho = rho; st->lam = lam; st->phi = phi; st->omega = omega; st->ee = ee_k;
-      st->s_done = s_k; st->eta_done = eta_k; st->N_done = Nk;
-      if (*L.errflag && st->err == 0) st->err = (int)(k.k0 + 1);
-      st->ns_valid = 3;
-    }
+    if (lane == 0 && *L.errflag && st->err == 0) st->err = (int)(k.k0 + 1);
   }
   // A_B (wave 5's rows) left through LDS before the barrier above: all four vector waves store it, coalesced
   for (int idx = tid - 256; idx < RB * r; idx += 256) { const int m = idx / r, c = idx - m * r; coef_store(k.Acoef + idx, L.sA[m * F3_AS + c]); }
@@ -1026,8 +1142,10 @@ __device__ __forceinline__ void blk_filter3_body(const BlockParams& b0) {
 
   // ---- one launch = `chain` consecutive blocks (1 when the blocks are launched one by one) ----
   // Chained, the blocks of a run pay the kernel launch, the cold instruction cache and the hand-off round trips once
-  // instead of once per block; the state still travels from block to block through the f3_* dump (this CU's L1 / L2).
+  // instead of once per block; the state travels from block to block through LDS (chain carry) or the f3_* dump (this CU's L1 / L2).
+  // Chain carry (KIND 0): between the blocks of one launch the state stays on chip (F3Carry); DevState gets it where the launch ends.
   const int nchain = b0.chain > 1 ? b0.chain : 1;
+  const bool carry = KIND == 0 && b0.chain > 1 && b0.carry != 0;
   for (int j = 0; j < nchain; ++j) {
   // (the thread index is made opaque per block: otherwise everything the programs' prologues derive from it -- lane masks,
   //  LDS addresses, layouts -- is loop-invariant, gets hoisted out of this loop and stays live across it: 3.3 KB of spills)
@@ -1038,6 +1156,8 @@ __device__ __forceinline__ void blk_filter3_body(const BlockParams& b0) {
   const BlockParams& b = b0;
   F3Blk k;
   k.k0 = b0.k0; k.nb = b0.nb; k.last = b0.last; k.Acoef = b0.Acoef; k.Bcoef = b0.Bcoef; k.XG = b0.XG; k.Aprev = b0.Aprev;
+  k.from_lds = (carry && j > 0) ? 1 : 0;
+  k.to_lds = (carry && j < nchain - 1) ? 1 : 0;
   int assemble = b0.assemble;
   long long seq = b0.seq;
   if (b0.chain > 1) {
@@ -1057,7 +1177,10 @@ __device__ __forceinline__ void blk_filter3_body(const BlockParams& b0) {
   }
   const long long t_begin = (long long)__builtin_amdgcn_s_memrealtime();      // 100 MHz: in-situ duration / gap diagnostics
   if (j > 0) {
-    if (!blk_chain_next(b0, seq)) return;
+    if (!blk_chain_next(b0, seq)) {
+      if (k.from_lds) f3_carry_flush(b0, L, k.k0, tid);                // the blocks completed, as they would have left DevState
+      return;
+    }
   } else {
     // Touch what the start-up will read -- the cross-Gram, the previous block's coefficients, the carried register dump --
     // while the hand-off flags are in flight: one memory round trip for the three instead of three in a row.  (A cross-Gram
@@ -1085,7 +1208,10 @@ __device__ __forceinline__ void blk_filter3_body(const BlockParams& b0) {
   // filter4, a block that follows another one in the same launch: h, w, ee, N, kappa and (a, b) of that block's last step stay
   // where they are in LDS -- the first step's start predictor uses them
   const bool warm = KIND == 1 && j > 0;      // (filter5 has no start to predict)
-  if (tid < RM) { L.mub[tid] = (tid < r && KIND == 0) ? st->mu[tid] : 0.0; if (!warm) { L.w[tid] = 0.0; L.h[tid] = 0.0; } }
+  if (tid < RM) {
+    if (!k.from_lds) L.mub[tid] = (tid < r && KIND == 0) ? st->mu[tid] : 0.0;      // (chain carry: mu_bar is where the last step left it)
+    if (!warm) { L.w[tid] = 0.0; L.h[tid] = 0.0; }
+  }
   if (tid < F3_NSC && !warm) L.sc[tid] = 0.0;
   if (KIND >= 1) {
     // filter4 / filter5: mu_{k0}, theta and the block's share of the R_k / Q_k schedules into LDS (mu_bar, F of the first step: X pair's prologue)
@@ -1105,7 +1231,8 @@ __device__ __forceinline__ void blk_filter3_body(const BlockParams& b0) {
       if (p.q_sched) D.qs[jb_] = p.q_sched[ks];
     }
   }
-  const bool carried = st->ns_valid == (KIND == 2 ? 5 : (KIND == 1 ? 4 : 3));       // the previous block (or run) left the f3_* register dump behind
+  // the previous block (or run) left the f3_* register dump behind -- or, chain carry, the state itself in LDS
+  const bool carried = k.from_lds ? true : st->ns_valid == (KIND == 2 ? 5 : (KIND == 1 ? 4 : 3));
   __syncthreads();
   const long long t_a = (long long)__builtin_amdgcn_s_memrealtime();
   if (!carried && KIND == 0) {

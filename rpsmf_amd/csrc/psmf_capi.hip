@@ -65,6 +65,7 @@ struct Switches {
   bool filter6_dual = !off("PSMF_FILTER6_DUAL"), block_dual = !off("PSMF_BLOCK_DUAL");      // the two inversions side by side
   bool block_pipe = !off("PSMF_BLOCK_PIPE");             // =0: blocks one after the other
   bool block_chain = !off("PSMF_BLOCK_CHAIN");           // =0: one filter launch per block
+  bool chain_carry = !off("PSMF_CHAIN_CARRY");           // =0: the blocks of a chained filter3 launch hand the r x r state on through DevState
   bool block_flags = !off("PSMF_BLOCK_FLAGS");           // =0: event hand-off instead of device flags
   int reserved_cus = as_int("PSMF_RESERVED_CUS", 8);     // CUs that the filter chain's stream owns
   int bulk_wgs_env = as_int("PSMF_BULK_WGS", 0);         // workgroups of the streaming bulk kernels (8..256, rounded down to a multiple of 8 where it is used)
@@ -543,6 +544,7 @@ int enqueue_blocks_pipelined(psmf_filter* h, int64_t k_begin, int64_t k_end) {
     c.chain = (int)nblk;
     c.chain_B = B;
     c.chain_kend = k_end;
+    c.carry = h->sw.chain_carry ? 1 : 0;
     c.Acoef0 = h->Acoef;
     c.Bcoef0 = h->Bcoef;
     c.XG0 = h->XG;
