@@ -126,6 +126,8 @@ struct F3Lds {
   double* rowbufY;  // 4 RM
   int* errflag;
   long long* tick;  // 2: loop start / loop end (s_memrealtime), diagnostics
+  long long* acc;   // F3A_*: counters and tick sums of a chained launch (thread 0 only), flushed to DevState where the launch ends
+  long long* hand;  // chain carry: [0] sequence number of the next block, [1] 1: wave 6 saw its cross-Gram announced (f3_chain_next)
 };
 
 constexpr int F3_AS = 48;           // row stride of the K-assembly staging (16 mod 32: conflict-free MFMA operand reads)
@@ -255,6 +257,41 @@ __device__ __forceinline__ void f3_carry_flush(const BlockParams& b, const F3Lds
   }
 }
 
+// Diagnostics of a chained launch (F3Lds::acc).  One launch per block adds its counters and tick sums to DevState when the block
+// ends; chained, that was five dependent global round trips of one lane between two blocks with all eight waves waiting at the
+// hand-off behind it.  The host reads cnt / dbg after a launch has ended, so a chained launch sums in LDS (thread 0 writes and
+// reads every word) and adds the sums to DevState once: after its last block, or where a dead hand-off ends it.
+enum { F3A_CNT = 0, F3A_DUR = 4, F3A_GAP, F3A_TEND, F3A_BLOCKS, F3A_DBG = 8, F3A_BLK = 13, F3A_N = 17 };   // F3A_BLK: this block's cnt[0..3]
+__device__ __forceinline__ void f3_acc_flush(DevState* st, const long long* a) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) st->cnt[i] += a[F3A_CNT + i];
+  st->cnt[4] += a[F3A_DUR];
+  st->cnt[5] += a[F3A_GAP];
+  st->cnt[6] = a[F3A_TEND];
+  st->cnt[7] += a[F3A_BLOCKS];
+#pragma unroll
+  for (int i = 0; i < 5; ++i) st->dbg[i] += a[F3A_DBG + i];
+  st->dbg[5] += 1;                          // kernel launches
+}
+
+// Chain carry: between two blocks of one launch.  blk_chain_next with the ACQUIRE taken out of it: whether the next block's
+// cross-Gram is there and the run alive was asked by wave 6 during the last timestep of the block that just ended
+// (f3_v_program) and waits in L.hand[1]; a "yes" -- all but the first blocks of a pass -- costs one LDS read instead of an
+// agent-scope round trip and a second barrier.  The ANNOUNCE stays where it was: every wave drains its stores (the coefficients
+// the apply kernel reads), barrier, flag store -- by wave 6, whose step loop never waits on vmcnt, so nobody waits for the
+// store's acknowledgement.  Nothing a carried block reads comes from DevState through the scalar cache (no scalar load of it is
+// left inside the chain loop), so there is nothing to invalidate.  Anything but "yes" takes blk_chain_next as it is: announce,
+// bounded wait, abort flag, error -7.
+__device__ __forceinline__ bool f3_chain_next(const BlockParams& b, const F3Lds& L, const long long seq) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  f3_barrier();                     // every wave's stores are complete; the block end's LDS traffic | the next block's set-up
+  if (__builtin_amdgcn_readfirstlane((int)L.hand[1]) != 0) {
+    if (threadIdx.x == 6 * 64) flag_store(b.flags + 1, seq);           // blocks < seq are complete
+    return true;
+  }
+  return blk_chain_next(b, seq);
+}
+
 __device__ __forceinline__ void f3_assemble_K(const BlockParams& b, const F3Blk& k, const F3Lds& L, const int r, const int tid) {
   const int nb = k.nb, lane = tid & 63, w = tid >> 6, lrow = lane >> 4, lcol = lane & 15;
   double* sK = L.sK;
@@ -310,7 +347,7 @@ __device__ __forceinline__ void f3_assemble_K(const BlockParams& b, const F3Blk&
       if (i < r && c < nb) { sK[i * RB + r + c] = acc[q]; sK[(r + c) * RB + i] = acc[q]; }
     }
   }
-  __syncthreads();
+  f3_barrier();               // (LDS order is all that is needed; __syncthreads() would make wave 6 wait for its flag store's acknowledgement)
 }
 
 // Knock-out switches for tools/blk3_knock.hip (timing what each piece costs on the critical path; results are wrong
@@ -805,7 +842,8 @@ __device__ __forceinline__ void f3_ns_program(const BlockParams& b, const F3Blk&
         }
       }
   }
-  if (role == 0 && lane == 0) { st->cnt[0] += ctl.c_ns; st->cnt[1] += ctl.c_sw; st->cnt[2] += ctl.c_it; st->cnt[3] += ctl.c_fail; }
+  // (thread 0: blk_filter3_body adds them to DevState, or to the sums of a chained launch)
+  if (role == 0 && lane == 0) { L.acc[F3A_BLK] = ctl.c_ns; L.acc[F3A_BLK + 1] = ctl.c_sw; L.acc[F3A_BLK + 2] = ctl.c_it; L.acc[F3A_BLK + 3] = ctl.c_fail; }
 #undef F3_ITERATE
 #undef F3_FETCH_PARTNER
 #undef F3_W_AND_TRACES
@@ -894,6 +932,11 @@ __device__ __forceinline__ void f3_v_program(const BlockParams& b, const F3Blk& 
   BLK_T0();
   for (int jb = 0; jb < k.nb; ++jb) {
     // =============================== phase 0 ===============================
+    // chain carry, last timestep of a block that hands on (wave 6, which has the shortest phases): is the next block's cross-Gram
+    // announced, is the run alive?  Asked here, answered into L.hand[1] in phase 2: f3_chain_next finds it there
+    const bool poll = isV2 && k.to_lds && jb == k.nb - 1;
+    long long poll_xg = 0, poll_ab = 1;
+    if (poll) { poll_xg = flag_load(b.flags + 0); poll_ab = flag_load(b.flags + 2); }
     double cm = 0.0;                       // V1: a_m, V2: (K a)_m  (kept for the rank-1 update of phase 2)
     if (isV0 && !(F3_KNOCK & 1024)) {
       const int j = lane & 31, hf = lane >> 5;
@@ -1030,6 +1073,7 @@ __device__ __forceinline__ void f3_v_program(const BlockParams& b, const F3Blk& 
 #pragma unroll
       for (int t = 0; t < 16; ++t) pr[t] = vscale * (pr[t] - L.w[16 * hf + t] * wjn);   // psmf.py:135-138
     }
+    if (poll && lane == 0) L.hand[1] = (poll_ab == 0 && poll_xg >= L.hand[0]) ? 1 : 0;
     BLK_T(3);
     if (!done) {
       f3_barrier();                                                   // ---- B3
@@ -1135,6 +1179,10 @@ __device__ __forceinline__ void blk_filter3_body(const BlockParams& b0) {
   L.s32 = hotS;
   __shared__ long long s_tick[2];
   L.tick = s_tick;
+  __shared__ long long s_acc[F3A_N];
+  __shared__ long long s_hand[2];
+  L.acc = s_acc;
+  L.hand = s_hand;
   __shared__ __attribute__((aligned(16))) double hot4[KIND >= 1 ? 5 * RM + 2 * 48 + F4_NKC : 2];
   F4Lds D;
   D.fd = hot4; D.mu = D.fd + RM; D.tp = D.mu + RM; D.th = D.tp + RM; D.rs = D.th + 2 * RM; D.qs = D.rs + 48; D.kc = D.qs + 48;
@@ -1146,6 +1194,13 @@ __device__ __forceinline__ void blk_filter3_body(const BlockParams& b0) {
   // Chain carry (KIND 0): between the blocks of one launch the state stays on chip (F3Carry); DevState gets it where the launch ends.
   const int nchain = b0.chain > 1 ? b0.chain : 1;
   const bool carry = KIND == 0 && b0.chain > 1 && b0.carry != 0;
+  const bool acc_lds = b0.chain > 1;      // the diagnostics of a chained launch are summed in LDS (f3_acc_flush)
+  if (tid0 == 0) {
+#pragma unroll
+    for (int i = 0; i < F3A_N; ++i) s_acc[i] = 0;
+    if (acc_lds) s_acc[F3A_TEND] = st->cnt[6];      // end of the filter kernel before this launch
+    s_hand[1] = 0;
+  }
   for (int j = 0; j < nchain; ++j) {
   // (the thread index is made opaque per block: otherwise everything the programs' prologues derive from it -- lane masks,
   //  LDS addresses, layouts -- is loop-invariant, gets hoisted out of this loop and stays live across it: 3.3 KB of spills)
@@ -1177,8 +1232,9 @@ __device__ __forceinline__ void blk_filter3_body(const BlockParams& b0) {
   }
   const long long t_begin = (long long)__builtin_amdgcn_s_memrealtime();      // 100 MHz: in-situ duration / gap diagnostics
   if (j > 0) {
-    if (!blk_chain_next(b0, seq)) {
+    if (!(carry ? f3_chain_next(b0, L, seq) : blk_chain_next(b0, seq))) {
       if (k.from_lds) f3_carry_flush(b0, L, k.k0, tid);                // the blocks completed, as they would have left DevState
+      if (tid == 0) f3_acc_flush(st, L.acc);
       return;
     }
   } else {
@@ -1204,7 +1260,7 @@ __device__ __forceinline__ void blk_filter3_body(const BlockParams& b0) {
   } else {
     f3_assemble_K(b, k, L, r, tid);
   }
-  if (tid == 0) *L.errflag = 0;
+  if (tid == 0) { *L.errflag = 0; L.hand[0] = seq + 1; L.hand[1] = 0; L.acc[F3A_BLK] = 0; L.acc[F3A_BLK + 1] = 0; L.acc[F3A_BLK + 2] = 0; L.acc[F3A_BLK + 3] = 0; }
   // filter4, a block that follows another one in the same launch: h, w, ee, N, kappa and (a, b) of that block's last step stay
   // where they are in LDS -- the first step's start predictor uses them
   const bool warm = KIND == 1 && j > 0;      // (filter5 has no start to predict)
@@ -1233,7 +1289,7 @@ __device__ __forceinline__ void blk_filter3_body(const BlockParams& b0) {
   }
   // the previous block (or run) left the f3_* register dump behind -- or, chain carry, the state itself in LDS
   const bool carried = k.from_lds ? true : st->ns_valid == (KIND == 2 ? 5 : (KIND == 1 ? 4 : 3));
-  __syncthreads();
+  f3_barrier();               // (what was loaded from global memory above sits in LDS writes, which wait for it themselves)
   const long long t_a = (long long)__builtin_amdgcn_s_memrealtime();
   if (!carried && KIND == 0) {
     // Lbar_1 = (P + q I)^-1 by the direct sweep: both halves run it in lockstep on their own image
@@ -1295,19 +1351,38 @@ __device__ __forceinline__ void blk_filter3_body(const BlockParams& b0) {
   if (tid == 0) {
     // cnt[4]: sum of in-kernel durations, cnt[5]: sum of the gaps to the previous filter kernel, cnt[7]: launches (10 ns ticks)
     const long long t_end = (long long)__builtin_amdgcn_s_memrealtime();
-    st->dbg[0] += t_h - t_begin; st->dbg[1] += t_a - t_h; st->dbg[2] += L.tick[0] - t_a; st->dbg[3] += L.tick[1] - L.tick[0]; st->dbg[4] += t_end - L.tick[1];
-    st->cnt[4] += t_end - t_begin;
-    if (st->cnt[6] != 0) st->cnt[5] += t_begin - st->cnt[6];
-    st->cnt[6] = t_end;
-    st->cnt[7] += 1;
-    if (j == 0) st->dbg[5] += 1;            // kernel launches
+    const long long dt[5] = {t_h - t_begin, t_a - t_h, L.tick[0] - t_a, L.tick[1] - L.tick[0], t_end - L.tick[1]};
+    if (acc_lds) {
+      long long* a = L.acc;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) a[F3A_CNT + i] += a[F3A_BLK + i];
+#pragma unroll
+      for (int i = 0; i < 5; ++i) a[F3A_DBG + i] += dt[i];
+      a[F3A_DUR] += t_end - t_begin;
+      if (a[F3A_TEND] != 0) a[F3A_GAP] += t_begin - a[F3A_TEND];
+      a[F3A_TEND] = t_end;
+      a[F3A_BLOCKS] += 1;
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) st->cnt[i] += L.acc[F3A_BLK + i];
+#pragma unroll
+      for (int i = 0; i < 5; ++i) st->dbg[i] += dt[i];
+      st->cnt[4] += t_end - t_begin;
+      if (st->cnt[6] != 0) st->cnt[5] += t_begin - st->cnt[6];
+      st->cnt[6] = t_end;
+      st->cnt[7] += 1;
+      if (j == 0) st->dbg[5] += 1;            // kernel launches
+    }
   }
   }   // chained blocks
   if (b0.chain > 1) {
     // the last block of the chain: complete, announced (the apply kernel of the bulk stream is waiting for it)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (tid0 == 0) flag_store(b0.flags + 1, b0.seq + nchain);
+    if (tid0 == 0) {
+      flag_store(b0.flags + 1, b0.seq + nchain);
+      f3_acc_flush(st, s_acc);
+    }
   }
 }
 

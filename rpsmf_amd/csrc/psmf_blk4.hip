@@ -565,7 +565,7 @@ __device__ __forceinline__ void f4_x_program(const BlockParams& b, const F3Blk& 
         }
       }
   }
-  if (role == 0 && lane == 0) { st->cnt[0] += ctl.c_ns; st->cnt[1] += ctl.c_sw; st->cnt[2] += ctl.c_it; st->cnt[3] += ctl.c_fail; }
+  if (role == 0 && lane == 0) { L.acc[F3A_BLK] = ctl.c_ns; L.acc[F3A_BLK + 1] = ctl.c_sw; L.acc[F3A_BLK + 2] = ctl.c_it; L.acc[F3A_BLK + 3] = ctl.c_fail; }
 #undef Y_WORK
 #undef Y_TO_IMAGE
 }
