@@ -1564,70 +1564,108 @@ int psmf_run_timed(psmf_handle h, int64_t k_begin, int64_t k_end, float* ms) {
   return psmf_sync(h);
 }
 
-int psmf_time_kernel(psmf_handle h, int which, int iters, float* avg_us) {
-  if (!h || !avg_us || iters < 1 || which < 0 || which > 2) return PSMF_ERR_ARG;
-  if (!h->have_state || !h->Y) return fail(h, PSMF_ERR_STATE, "psmf_time_kernel: needs state and series");
-  int rc = set_device(h);
-  if (rc) return rc;
-  if (h->engine == 2) {
-    const int nb = (int)(h->T_cap < h->block_steps ? h->T_cap : h->block_steps);
-    psmf::BlockParams b;
-    fill_block_params(h, b, h->sp.series_t0, nb);
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    const size_t cbytes = (size_t)h->cfg.d_local * h->geo.rp * h->elem();
-    void* Csave = nullptr; DevState* ssave = nullptr; double* thsave = nullptr;
-    const size_t thbytes = 4 * h->th_cap * sizeof(double);     // theta, gradient sums, Adam moments: the filter kernels step them too
-    HIP_TRY(h, hipMalloc(&Csave, cbytes));
-    HIP_TRY(h, hipMalloc((void**)&ssave, sizeof(DevState)));
-    HIP_TRY(h, hipMalloc((void**)&thsave, thbytes));
-    HIP_TRY(h, hipMemcpy(Csave, h->C, cbytes, hipMemcpyDeviceToDevice));
-    HIP_TRY(h, hipMemcpy(ssave, h->st, sizeof(DevState), hipMemcpyDeviceToDevice));
-    HIP_TRY(h, hipMemcpy(thsave, h->thbuf, thbytes, hipMemcpyDeviceToDevice));
-    HIP_TRY(h, hipDeviceSynchronize());      // (device-to-device copies on the null stream are not ordered against the handle's non-blocking stream)
-    launch_blk_gram(h, b);           // a valid K for the filter / apply measurements
-    launch_blk_filter(h, b);
-    auto one = [&]() {
-      if (which == 0) { HIP_TRY(h, hipMemcpyAsync(h->st, ssave, sizeof(DevState), hipMemcpyDeviceToDevice, h->stream)); launch_blk_filter(h, b); }
-      else if (which == 1) {
-        // the per-block d-sized contraction: the cross-Gram for the next block (+ reduction) when the series holds
-        // two blocks, else the plain block Gram
-        if (h->T_cap >= 2 * (int64_t)nb) {
-          psmf::BlockParams x = b;
-          x.k1 = b.k0 + nb; x.nb1 = nb;
-          launch_blk_xgram(h, x, h->XG, h->stream);
-        } else {
-          launch_blk_gram(h, b);
-        }
-      }
-      else launch_blk_apply(h, b);
-      return (int)PSMF_OK;
-    };
-    for (int i = 0; i < 2; ++i) { rc = one(); if (rc) return rc; }
-    HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
-    for (int i = 0; i < iters; ++i) { rc = one(); if (rc) return rc; }
-    HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
-    HIP_TRY(h, hipEventSynchronize(h->ev1));
-    float ms = 0.f;
-    HIP_TRY(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    *avg_us = ms * 1000.f / iters;
-    HIP_TRY(h, hipMemcpy(h->C, Csave, cbytes, hipMemcpyDeviceToDevice));
-    HIP_TRY(h, hipMemcpy(h->st, ssave, sizeof(DevState), hipMemcpyDeviceToDevice));
-    HIP_TRY(h, hipMemcpy(h->thbuf, thsave, thbytes, hipMemcpyDeviceToDevice));
-    HIP_TRY(h, hipFree(Csave));
-    HIP_TRY(h, hipFree(ssave));
-    HIP_TRY(h, hipFree(thsave));
-    return PSMF_OK;
+// psmf_time_kernel launches a step's kernels at the FIRST steps of the uploaded series whatever the handle has run so far: they
+// overwrite the y_hat rows and the posterior means recorded for those steps, which the caller reads after a run
+// (psmf_download_y_pred, psmf_sq_error, psmf_download_mu).  These records are saved and restored with the state.
+struct StepRecords {
+  void* yp = nullptr; double* mu = nullptr;
+  size_t yp_bytes = 0, mu_bytes = 0;
+};
+
+static int save_step_records(psmf_filter* h, int64_t yp_rows, int64_t mu_rows, StepRecords& s) {
+  if (yp_rows > h->T_cap) yp_rows = h->T_cap;
+  if (mu_rows > h->T_cap + 1) mu_rows = h->T_cap + 1;
+  if (h->YP && yp_rows > 0) {
+    s.yp_bytes = (size_t)yp_rows * h->cfg.d_local * h->elem();
+    HIP_TRY(h, hipMalloc(&s.yp, s.yp_bytes));
+    HIP_TRY(h, hipMemcpy(s.yp, h->YP, s.yp_bytes, hipMemcpyDeviceToDevice));
   }
-  if (h->need_prep) { rc = prepare(h, h->k_done); if (rc) return rc; }
+  if (h->mu_hist && mu_rows > 0) {
+    s.mu_bytes = (size_t)mu_rows * h->cfg.r * sizeof(double);
+    HIP_TRY(h, hipMalloc((void**)&s.mu, s.mu_bytes));
+    HIP_TRY(h, hipMemcpy(s.mu, h->mu_hist, s.mu_bytes, hipMemcpyDeviceToDevice));
+  }
+  return PSMF_OK;
+}
+
+static int restore_step_records(psmf_filter* h, StepRecords& s) {
+  if (s.yp) { HIP_TRY(h, hipMemcpy(h->YP, s.yp, s.yp_bytes, hipMemcpyDeviceToDevice)); HIP_TRY(h, hipFree(s.yp)); s.yp = nullptr; }
+  if (s.mu) { HIP_TRY(h, hipMemcpy(h->mu_hist, s.mu, s.mu_bytes, hipMemcpyDeviceToDevice)); HIP_TRY(h, hipFree(s.mu)); s.mu = nullptr; }
+  return PSMF_OK;
+}
+
+// Everything psmf_time_kernel's launches mutate: C, the DevState, theta with its gradient sums and Adam moments (the filter
+// kernels and the serial stage step them too), and the step records above.
+struct TimingSave {
+  void* C = nullptr; DevState* st = nullptr; double* th = nullptr;
+  size_t cbytes = 0, thbytes = 0;
+  StepRecords rec;
+  bool complete = false;
+};
+
+static int save_for_timing(psmf_filter* h, int64_t yp_rows, int64_t mu_rows, TimingSave& s) {
+  s.cbytes = (size_t)h->cfg.d_local * h->geo.rp * h->elem();
+  s.thbytes = 4 * h->th_cap * sizeof(double);
+  HIP_TRY(h, hipMalloc(&s.C, s.cbytes));
+  HIP_TRY(h, hipMalloc((void**)&s.st, sizeof(DevState)));
+  HIP_TRY(h, hipMalloc((void**)&s.th, s.thbytes));
+  HIP_TRY(h, hipMemcpy(s.C, h->C, s.cbytes, hipMemcpyDeviceToDevice));
+  HIP_TRY(h, hipMemcpy(s.st, h->st, sizeof(DevState), hipMemcpyDeviceToDevice));
+  HIP_TRY(h, hipMemcpy(s.th, h->thbuf, s.thbytes, hipMemcpyDeviceToDevice));
+  int rc = save_step_records(h, yp_rows, mu_rows, s.rec);
+  if (rc) return rc;
+  HIP_TRY(h, hipDeviceSynchronize());      // (device-to-device copies on the null stream are not ordered against the handle's non-blocking stream)
+  s.complete = true;
+  return PSMF_OK;
+}
+
+static int restore_after_timing(psmf_filter* h, TimingSave& s) {
   HIP_TRY(h, hipStreamSynchronize(h->stream));
-  // save everything the kernels mutate
-  const size_t cbytes = (size_t)h->cfg.d_local * h->geo.rp * h->elem();
-  void* Csave = nullptr; DevState* ssave = nullptr;
-  HIP_TRY(h, hipMalloc(&Csave, cbytes));
-  HIP_TRY(h, hipMalloc((void**)&ssave, sizeof(DevState)));
-  HIP_TRY(h, hipMemcpy(Csave, h->C, cbytes, hipMemcpyDeviceToDevice));
-  HIP_TRY(h, hipMemcpy(ssave, h->st, sizeof(DevState), hipMemcpyDeviceToDevice));
-  HIP_TRY(h, hipDeviceSynchronize());
+  HIP_TRY(h, hipMemcpy(h->C, s.C, s.cbytes, hipMemcpyDeviceToDevice));
+  HIP_TRY(h, hipMemcpy(h->st, s.st, sizeof(DevState), hipMemcpyDeviceToDevice));
+  HIP_TRY(h, hipMemcpy(h->thbuf, s.th, s.thbytes, hipMemcpyDeviceToDevice));
+  return restore_step_records(h, s.rec);
+}
+
+static void free_timing_save(TimingSave& s) {
+  (void)hipFree(s.C); (void)hipFree(s.st); (void)hipFree(s.th); (void)hipFree(s.rec.yp); (void)hipFree(s.rec.mu);
+  s = TimingSave();
+}
+
+static int time_block_kernels(psmf_filter* h, int which, int iters, int nb, const TimingSave& sv, float* avg_us) {
+  psmf::BlockParams b;
+  fill_block_params(h, b, h->sp.series_t0, nb);
+  launch_blk_gram(h, b);           // a valid K for the filter / apply measurements
+  launch_blk_filter(h, b);
+  auto one = [&]() {
+    if (which == 0) { HIP_TRY(h, hipMemcpyAsync(h->st, sv.st, sizeof(DevState), hipMemcpyDeviceToDevice, h->stream)); launch_blk_filter(h, b); }
+    else if (which == 1) {
+      // the per-block d-sized contraction: the cross-Gram for the next block (+ reduction) when the series holds
+      // two blocks, else the plain block Gram
+      if (h->T_cap >= 2 * (int64_t)nb) {
+        psmf::BlockParams x = b;
+        x.k1 = b.k0 + nb; x.nb1 = nb;
+        launch_blk_xgram(h, x, h->XG, h->stream);
+      } else {
+        launch_blk_gram(h, b);
+      }
+    }
+    else launch_blk_apply(h, b);
+    return (int)PSMF_OK;
+  };
+  int rc;
+  for (int i = 0; i < 2; ++i) { rc = one(); if (rc) return rc; }
+  HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
+  for (int i = 0; i < iters; ++i) { rc = one(); if (rc) return rc; }
+  HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
+  HIP_TRY(h, hipEventSynchronize(h->ev1));
+  float ms = 0.f;
+  HIP_TRY(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+  *avg_us = ms * 1000.f / iters;
+  return PSMF_OK;
+}
+
+static int time_step_kernels(psmf_filter* h, int which, int iters, float* avg_us) {
   {  // the sweep reads y_k / writes y_hat_k at the step counter: point it at a valid row of the series
     long long k0 = h->sp.series_t0;
     HIP_TRY(h, hipMemcpy(&h->st->k, &k0, sizeof(k0), hipMemcpyHostToDevice));
@@ -1642,11 +1680,35 @@ int psmf_time_kernel(psmf_handle h, int which, int iters, float* avg_us) {
   float ms = 0.f;
   HIP_TRY(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
   *avg_us = ms * 1000.f / iters;
-  HIP_TRY(h, hipMemcpy(h->C, Csave, cbytes, hipMemcpyDeviceToDevice));
-  HIP_TRY(h, hipMemcpy(h->st, ssave, sizeof(DevState), hipMemcpyDeviceToDevice));
-  HIP_TRY(h, hipFree(Csave));
-  HIP_TRY(h, hipFree(ssave));
   return PSMF_OK;
+}
+
+int psmf_time_kernel(psmf_handle h, int which, int iters, float* avg_us) {
+  if (!h || !avg_us || iters < 1 || which < 0 || which > 2) return PSMF_ERR_ARG;
+  if (!h->have_state || !h->Y) return fail(h, PSMF_ERR_STATE, "psmf_time_kernel: needs state and series");
+  int rc = set_device(h);
+  if (rc) return rc;
+  const bool blocked = h->engine == 2;
+  if (!blocked && h->need_prep) { rc = prepare(h, h->k_done); if (rc) return rc; }
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  // Save everything the kernels mutate; from here on there is one way out, which puts it back and frees the copies.
+  TimingSave sv;
+  double* const hist = h->sp.mu_hist;
+  const int nb = (int)(h->T_cap < h->block_steps ? h->T_cap : h->block_steps);
+  if (blocked) {
+    rc = save_for_timing(h, nb, nb + 1, sv);       // the block's y_hat rows (apply) and posterior means (filter)
+  } else {
+    // the sweep writes y_hat of the series' first step; every launch of the serial stage advances the step counter and records
+    // the posterior mean of that step: rows 1 .. iters + 3 of the history (a history shorter than that is not written at all)
+    const int64_t serial_launches = (int64_t)iters + 3;
+    if (serial_launches > h->T_cap) h->sp.mu_hist = nullptr;
+    rc = save_for_timing(h, 1, h->sp.mu_hist ? serial_launches + 1 : 0, sv);
+  }
+  if (!rc) rc = blocked ? time_block_kernels(h, which, iters, nb, sv, avg_us) : time_step_kernels(h, which, iters, avg_us);
+  h->sp.mu_hist = hist;
+  if (sv.complete) { const int rc2 = restore_after_timing(h, sv); if (!rc) rc = rc2; }     // (a failed measurement too leaves the state as it found it)
+  free_timing_save(sv);
+  return rc;
 }
 
 int psmf_geometry(psmf_handle h, int32_t* out7) {

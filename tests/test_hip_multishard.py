@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 from conftest import relerr
+from host_group import HostGroup
 from oracle import psmf_oracle as O
 from rpsmf_amd.sharding import shard_rows
 
@@ -26,33 +27,6 @@ def _capi():
     from rpsmf_amd import _capi
 
     return _capi
-
-
-class HostGroup:
-    """In-process stand-in of a communicator: `nranks` threads, sum in rank order, same bits for everybody."""
-
-    def __init__(self, nranks, timeout=60.0):
-        self.n = nranks
-        self.slots = [None] * nranks
-        self.barrier = threading.Barrier(nranks)
-        self.timeout = timeout
-        self.calls = [0] * nranks
-        self.sizes = []
-
-    def allreduce(self, rank):
-        def f(v):
-            self.slots[rank] = v
-            self.barrier.wait(self.timeout)
-            tot = self.slots[0].copy()
-            for i in range(1, self.n):
-                assert self.slots[i].shape == tot.shape
-                tot += self.slots[i]
-            if rank == 0:
-                self.sizes.append(tot.size)
-            self.calls[rank] += 1
-            self.barrier.wait(self.timeout)
-            return tot
-        return f
 
 
 def _run(c, nshards, d, r, Y, C0, st0, T, *, engine, storage, robust, env=None, extra=None, theta=None, want_kernel=None):
