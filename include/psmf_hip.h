@@ -262,7 +262,7 @@ int psmf_geometry(psmf_handle h, int32_t* out7);
  * 8 = psmf_blk_filter6 (every configuration at r <= 16 but the simplified hooks), 9 = psmf_blk_filter6d (its instantiation with the two
  * inversions side by side: random walk, Q = q I), 10 = psmf_blk_filter7 (the same design on 2 x 2 tiles: what is left at 17 <= r <= 32),
  * 11 = psmf_pstep_k, the per-step engine as ONE persistent launch per run (C on chip, device-flag hand-offs; psmf_pstep.hip).
- * The same function decides what is launched (select_filter_kernel, psmf_capi.hip).
+ * The same function decides what is launched (select_filter_kernel, psmf_blocked.hip).
  * (New: diagnostics for tests and bench.py -- the reference has one code path, pypsmf/psmf/psmf.py:90-102.) */
 int psmf_filter_kernel(psmf_handle h);
 /* diagnostics of the blocked engine's r x r inversions since the last reset: out[0] = timesteps inverted by

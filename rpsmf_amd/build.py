@@ -3,15 +3,19 @@
     python -m rpsmf_amd.build            # libpsmf_hip.so  (only what is stale)
     python -m rpsmf_amd.build --force    # everything from source
 
-The library is three translation units, compiled side by side and linked: the C ABI with the two-launch and blocked engines
-(psmf_capi.hip and what it includes), the persistent per-step engine (psmf_pstep.hip), and the build identity (psmf_buildid.cpp:
-`psmf_build_id()` returns the SHA-256 of every source file and of the compiler flags the library was built from).  `build_library`
-rebuilds whenever that hash differs from the sources on disk -- modification times play no part -- and `source_hash()` /
-`library_build_id()` let `__graft_entry__.build()` prove that the shipped binary is the compiled form of the shipped sources.
+The library is a handful of translation units, compiled side by side (at most 16 at a time) and linked: the C ABI with the launched
+per-step engine (psmf_capi.hip), the blocked engine's host driver and kernels (psmf_blocked.hip), the filter3 family of block filters
+(psmf_filter34.hip), the masked small-shape engine (psmf_impute.hip), the persistent per-step engine (psmf_pstep.hip), and the build
+identity (psmf_buildid.cpp: `psmf_build_id()` returns the SHA-256 of every source file and of the compiler flags the library was built
+from).  An object is stale when the hash of what its source reaches through `#include "..."`, followed transitively, differs from the one
+it was compiled from -- no list of dependencies is kept by hand.  `build_library` rebuilds whenever the whole-library hash differs from
+the sources on disk -- modification times play no part -- and `source_hash()` / `library_build_id()` let `__graft_entry__.build()`
+prove that the shipped binary is the compiled form of the shipped sources.
 """
 
 import hashlib
 import os
+import re
 import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
@@ -32,7 +36,8 @@ FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-Wno-unused-val
 FLAGS += os.environ.get("PSMF_CXXFLAGS", "").split()      # diagnostic builds (e.g. -DPSTEP_PROF); part of the build id
 LINK = ["-L/opt/rocm/lib", "-lrccl", "-Wl,-rpath,/opt/rocm/lib"]
 
-_PSTEP_FILES = ("psmf_pstep.hip", "psmf_pstep.h", "psmf_ns.hip", "psmf_device.h")
+UNITS = ("psmf_capi.hip", "psmf_blocked.hip", "psmf_filter34.hip", "psmf_impute.hip", "psmf_pstep.hip")
+MAX_JOBS = 16
 
 
 def _sources():
@@ -54,16 +59,26 @@ def source_hash():
     return _hash_files(_sources() + [HEADER])
 
 
+_INCLUDE = re.compile(r'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', re.M)
+
+
+def _reached(src):
+    """the files `src` reaches through #include "...", followed transitively; `src` itself first"""
+    seen, todo = [], [os.path.normpath(src)]
+    while todo:
+        p = todo.pop()
+        if p in seen:
+            continue
+        seen.append(p)
+        with open(p, encoding="utf-8") as f:
+            text = f.read()
+        todo += [os.path.normpath(os.path.join(os.path.dirname(p), inc)) for inc in _INCLUDE.findall(text)]
+    return [seen[0]] + sorted(seen[1:])
+
+
 def _units():
     """(object name, source, files whose content decides whether the object is stale, extra flags)"""
-    srcs = _sources()
-    pstep_deps = [os.path.join(CSRC, f) for f in _PSTEP_FILES]
-    capi_deps = [p for p in srcs if os.path.basename(p) not in ("psmf_pstep.hip", "psmf_buildid.cpp")] + [HEADER]
-    pstep = os.path.join(CSRC, "psmf_pstep.hip")
-    return [
-        ("psmf_capi.o", os.path.join(CSRC, "psmf_capi.hip"), capi_deps, []),
-        ("psmf_pstep.o", pstep, pstep_deps, []),          # persistent per-step kernel (+ its host entry points)
-    ]
+    return [(u.replace(".hip", ".o"), os.path.join(CSRC, u), _reached(os.path.join(CSRC, u)), []) for u in UNITS]
 
 
 def library_build_id():
@@ -111,7 +126,7 @@ def build_library(force=False, verbose=True):
         with open(stamp, "w") as f:
             f.write(dep_hash)
 
-    with ThreadPoolExecutor(max_workers=max(1, len(jobs))) as ex:
+    with ThreadPoolExecutor(max_workers=max(1, min(MAX_JOBS, len(jobs)))) as ex:
         list(ex.map(compile_one, jobs))
     idobj = os.path.join(OBJ_DIR, "psmf_buildid.o")
     _run([hipcc, "-O2", "-std=c++17", "-fPIC", "-x", "c++", f'-DPSMF_BUILD_ID="{want}"'] + inc + ["-c", os.path.join(CSRC, "psmf_buildid.cpp"), "-o", idobj], verbose)

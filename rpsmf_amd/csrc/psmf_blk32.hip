@@ -1,7 +1,7 @@
 // psmf_blk_filter7: psmf_blk_filter6's design (psmf_blk16.hip: one program per wave, the r x r state in ONE wave's registers in the
 // MFMA output layout, wave-local sweeps, stages that do not depend on each other side by side) for the ranks 17 <= r <= 32 --
 // everything the general one-group kernel psmf_blk_filter<32> took there: dense-Jacobian dynamics (scaled walk, scaled sinusoid,
-// Fourier basis), a general Q, and -- measured faster than filter4's sweep regime -- nothing else for now (psmf_capi.hip decides).
+// Fourier basis), a general Q, and -- measured faster than filter4's sweep regime -- nothing else for now (select_filter_kernel in psmf_blocked.hip decides).
 // A 32 x 32 matrix is 2 x 2 tiles of 16 x 16: tile (ti, tj), lane l, register q = element (16 ti + (l >> 4) + 4 q, 16 tj + (l & 15)).
 //   dynamics forward (waves 1-3, psmf_dyn.hip; the matrix wave only joins the barriers)
 //   A  wave 0: Pbar = F P F^T + Q -- T = P F^T and F T, 32 + 32 float64 MFMAs whose operands need no shuffling (a symmetric matrix in

@@ -1,5 +1,5 @@
 // Role-specialised coefficient-space filter of the blocked engine for state transitions with a DIAGONAL Jacobian
-// ("filter4"; included from psmf_blk3.hip, whose helpers, LDS layout and T- / P-layouts it shares):
+// ("filter4"; built on psmf_blk3.hip, whose helpers, LDS layout and T- / P-layouts it shares):
 //
 //     random walk with per-step R_k / Q_k schedules          psmf.py:115,123,141
 //     f = cos(2 pi theta t + x)                               ExperimentSynthetic/synthetic_psmf.py:105-106 (full filter)
@@ -24,6 +24,10 @@
 // The vector waves 4-7 are filter3's (V and the scalars; A by rows; KA by rows; A^T by columns); wave 4 also owns the r-sized
 // theta path (g_f, gradient sums, Adam), mu_bar_{k+1} = f(theta, mu_k, k + 1) and F_{k+1} are formed by the lanes of the X pair
 // that have just formed mu_k.  Three workgroup barriers per timestep in the steady state, as in filter3.
+#pragma once
+#include "psmf_blk3.hip"
+
+namespace psmf {
 
 struct F4Lds {
   double* fd;       // RM: diagonal of F of the current step (0 beyond r)
@@ -1389,3 +1393,5 @@ __device__ __forceinline__ void f5_v_program(const BlockParams& b, const F3Blk& 
   }
   for (int idx = tid - 256; idx < RB * r; idx += 256) { const int m = idx / r, c = idx - m * r; coef_store(k.Acoef + idx, L.sA[m * F3_AS + c]); }
 }
+
+}  // namespace psmf

@@ -229,7 +229,7 @@ __global__ __launch_bounds__(256) void psmf_blk_xreduce2(const double* __restric
 // ------------------------------------------------------------------------------------------------------------
 constexpr int AP2_SC = 36;     // staging row stride (floats) of the C part  [16 rows][rp <= 32]
 constexpr int AP2_SY = 20;     // staging stride (floats) of the series part  [column][16 rows]
-constexpr int AP2_NY = 48;     // series columns staged = the longest block (psmf_capi.hip caps blocks at 48 timesteps)
+constexpr int AP2_NY = 48;     // series columns staged = the longest block (init_blocked caps blocks at 48 timesteps)
 constexpr int AP2_FZ = 64 * BK_FS;      // floats of a wave's slab image [64 coefficient columns][16 rows + 4], float32 as loaded
 constexpr size_t AP2_WAVE_BYTES = (size_t)AP2_FZ * 4 + BK_TR * AP2_SC * 4 + AP2_NY * AP2_SY * 4;
 inline size_t blk_apply2_lds_bytes() { return (size_t)RB * GZ_S * 8 + (size_t)BK_WAVES * AP2_WAVE_BYTES; }

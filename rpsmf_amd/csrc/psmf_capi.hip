@@ -1,19 +1,11 @@
 // C ABI of libpsmf_hip.so (include/psmf_hip.h): host-side orchestration of the large-d engine.
 // One handle = one HIP stream, one device-resident filter (or row shard), one hipGraph of
 // per-step launches replayed over the series.  No torch, no hipBLAS: plain HIP + RCCL.
-#include "../../include/psmf_hip.h"
+#include "psmf_host.h"
 #include "psmf_kernels.hip"
 #include "psmf_masked.hip"
-#include <chrono>
-#include "psmf_block.hip"
-#include "psmf_blk3.hip"
-#include "psmf_blk16.hip"
-#include "psmf_blk32.hip"
-#include "psmf_bulk.hip"
 #include "psmf_rotate.hip"
-#include "psmf_pstep.h"       // persistent per-step engine: its kernels are a translation unit of their own (psmf_pstep.hip)
-
-#include <rccl/rccl.h>
+#include "psmf_wave16.hip"     // solve_block_wave: the per-step engine's solve block
 
 #include <cmath>
 #include <cstddef>
@@ -26,18 +18,9 @@
 #include <type_traits>
 #include <vector>
 
-using psmf::DevState;
-using psmf::StepParams;
-
-namespace {
-
 thread_local std::string g_create_error;
 
-struct Geometry {
-  int vec, nv, rp, gs, rpp, rpad, nt;
-  int n_sweep_wg, rows_per_wg, ps;
-  size_t sweep_lds;
-};
+namespace {
 
 #ifndef PSMF_SWEEP_UNROLL
 #define PSMF_SWEEP_UNROLL 4
@@ -46,185 +29,6 @@ constexpr int kUnroll = PSMF_SWEEP_UNROLL;      // row passes (16-byte loads per
 constexpr int kGramWG = 128;
 
 }  // namespace
-
-// Environment switches: one row each, and this struct is the library's only reader of the environment.  The rows
-// are read when a Switches is constructed: ONCE per handle, with the handle at psmf_create -- tests flip them between handles of one
-// process, and nothing on the per-block host path looks at the environment; the entry points without a handle (psmf_impute_*,
-// psmf_measure_copy_bandwidth) construct one at entry, on every call.
-struct Switches {
-  static bool set(const char* name) { return getenv(name) != nullptr; }                                  // present at all
-  static bool on(const char* name) { const char* e = getenv(name); return e && atoi(e) != 0; }           // set and non-zero
-  static bool off(const char* name) { const char* e = getenv(name); return e && atoi(e) == 0; }          // set to zero
-  static int as_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
-  static double as_double(const char* name, double dflt) { const char* e = getenv(name); return e ? atof(e) : dflt; }
-
-  int engine_env = as_int("PSMF_ENGINE", 0);             // 1 | 2: force the per-step / blocked engine (2 only where the blocked engine applies)
-  // blocked engine; "=0" puts the older / more general kernel in the place of the role-specialised one
-  bool bulk2 = !off("PSMF_BULK2");                       // streaming cross-Gram / apply kernels (psmf_bulk.hip)
-  bool filter3 = !off("PSMF_FILTER3"), filter4 = !off("PSMF_FILTER4"), filter6 = !off("PSMF_FILTER6"), filter7 = !off("PSMF_FILTER7");
-  bool filter6_dual = !off("PSMF_FILTER6_DUAL"), block_dual = !off("PSMF_BLOCK_DUAL");      // the two inversions side by side
-  bool block_pipe = !off("PSMF_BLOCK_PIPE");             // =0: blocks one after the other
-  bool block_chain = !off("PSMF_BLOCK_CHAIN");           // =0: one filter launch per block
-  bool chain_carry = !off("PSMF_CHAIN_CARRY");           // =0: the blocks of a chained filter3 launch hand the r x r state on through DevState
-  bool block_flags = !off("PSMF_BLOCK_FLAGS");           // =0: event hand-off instead of device flags
-  int reserved_cus = as_int("PSMF_RESERVED_CUS", 8);     // CUs that the filter chain's stream owns
-  int bulk_wgs_env = as_int("PSMF_BULK_WGS", 0);         // workgroups of the streaming bulk kernels (8..256, rounded down to a multiple of 8 where it is used)
-  bool host_comm_flags = on("PSMF_HOST_COMM_FLAGS");     // device-flag hand-off (and chained filter launches) under a host-mediated communicator too
-  bool force_collective = set("PSMF_FORCE_COLLECTIVE");  // the RCCL path with one rank
-  // per-step engine
-  bool step_persistent = !off("PSMF_STEP_PERSISTENT");   // one persistent launch per run (psmf_pstep.hip) where it applies; =0: two launches per timestep
-  bool pstep_big = !off("PSMF_PSTEP_BIG");               // =0: the persistent kernel for r <= 32 only
-  bool pstep_prof = set("PSMF_PSTEP_PROF");              // diagnostic (-DPSTEP_PROF builds): per-phase clock sums, printed at psmf_destroy
-  bool wave_solve = !off("PSMF_STEP_WAVE_SOLVE"), wave_big = !off("PSMF_STEP_WAVE_BIG");      // =0: LDS-and-barrier sweeps in the solve block, for every r / for r > 32
-  bool step_dual = !off("PSMF_STEP_DUAL"), serial_wide = !off("PSMF_SERIAL_WIDE"), wgram_mfma = !off("PSMF_WGRAM_MFMA");
-  int sweep_threads = as_int("PSMF_SWEEP_THREADS", 512) == 256 ? 256 : 512;
-  int tail_reduce = as_int("PSMF_TAIL_REDUCE", -1);      // 0 | 1: the serial stage / the last row workgroup sums the partial rows (unset: by shape)
-  // Newton-Schulz starts of the inversions; the *_set ones have defaults that depend on the handle (fill_step_params, update_ns_policy)
-  bool ns = !off("PSMF_NS");                             // =0: direct sweeps only
-  int ns_predict = as_int("PSMF_NS_PREDICT", 7);         // bits: 1 a / b (phase F), 2 core (wave 7), 4 applied
-  bool ns_tol_set = set("PSMF_NS_TOL"); double ns_tol = as_double("PSMF_NS_TOL", 0.0);      // diagnostic: acceptance tolerance
-  bool ns_far_set = set("PSMF_NS_FAR"); double ns_far = as_double("PSMF_NS_FAR", 0.3);      // diagnostic: residual at which a start is given up
-  bool ns_skip_set = set("PSMF_NS_SKIP"); int ns_skip = as_int("PSMF_NS_SKIP", 3);          // diagnostic: timesteps that then sweep unasked
-  double ns_far4 = as_double("PSMF_NS_FAR4", 0.6);       // filter4 / filter4s: their give-up residual (PSMF_NS_FAR, when set, rules both)
-  // small-shape masked engine (psmf_impute.hip)
-  bool impute_v3 = !off("PSMF_IMPUTE_V3"), impute_par = !off("PSMF_IMPUTE_PAR");      // =0: round 2's loop for the small shapes too; inversions one after the other
-  // diagnostics
-  bool dbg_breakdown = set("PSMF_DBG_BREAKDOWN");        // psmf_counters prints the in-situ breakdown of a filter3 launch
-  bool host_timing = on("PSMF_HOST_TIMING");             // report slow host-side enqueues and waits
-  int copy_grid = as_int("PSMF_COPY_GRID", 0);           // grid of the copy-bandwidth probe (0, unset: sized from the buffer)
-};
-
-struct psmf_filter {
-  psmf_config cfg;
-  Geometry geo;
-  Switches sw;
-  hipStream_t stream = nullptr;
-  DevState* st = nullptr;
-  void* C = nullptr;
-  void* Y = nullptr;
-  void* YP = nullptr;
-  double* partials = nullptr;
-  double* gpart = nullptr;
-  double* thbuf = nullptr;     // theta | gradsum | adam_m | adam_v, th_cap doubles each
-  size_t th_cap = 0;
-  double* rho_rows = nullptr;  // d_local per-row diag(R) (cfg.nonuniform_R)
-  double* rotU = nullptr;      // d x d: eigenvectors of a non-diagonal R in its columns (psmf_set_noise_rotation); series, C, y_hat are kept rotated
-  void* rot_tmp = nullptr;     // staging of a rotation (the GEMM is out of place)
-  size_t rot_tmp_bytes = 0;
-  // masked filter (cfg.masked, psmf_masked.hip)
-  uint8_t* mask = nullptr;     // T_cap x d_local observation mask (psmf_upload_mask)
-  uint8_t* mmiss = nullptr;    // staging of the held-out mask for psmf_masked_metrics (mmiss_cap bytes)
-  size_t mmiss_cap = 0;
-  double* mg = nullptr;        // r*r + 1: masked Gram and observed count of the current step, summed over workgroups (and ranks)
-  double* sc_hist = nullptr;   // T_cap x 2: (s_k, eta_k) of every step -- the bands are formed from them
-  bool have_mask = false;
-  double* sched = nullptr;     // rho_k | q_k schedules, sched_n doubles each (psmf_set_schedules)
-  int64_t sched_n = 0;
-  double* qmat = nullptr;      // Q_k matrices, (qmat_n + 1) x r x r (psmf_set_q_matrix_schedule)
-  int64_t qmat_n = 0;
-  double* mu_hist = nullptr;   // (T_cap + 1) x r
-  hipStream_t fstream = nullptr;   // blocked engine, pipelined: the filter chain's own stream, pinned to reserved CUs (or nullptr)
-  bool streams_concurrent = false;           // the filter stream's kernels run concurrently with the bulk stream's (probed at creation)
-  // HIP-event timing of the chained filter launches (one per run): a ring of event pairs, read out at the next sync
-  static constexpr int kTimedRuns = 256;
-  hipEvent_t evK0[kTimedRuns] = {}, evK1[kTimedRuns] = {};
-  hipEvent_t evC = nullptr;        // end of the chained filter launch: orders the handle's main stream (host reads of DevState) after it
-  int evk_pending = 0;
-  double kernel_ms_sum = 0.0;
-  long long kernel_launches = 0;
-  int reserved_cus = 0;
-  int bulk_wgs = 256;          // workgroups of the streaming bulk kernels (one per CU of the bulk stream: a 257th would wait for a whole round)
-  double* scratch = nullptr;   // sq-error partials / predict staging
-  // blocked engine
-  int engine = 1;              // 1 per-step, 2 blocked
-  int block_steps = 0;         // B = RB - r
-  bool q_iso = false;          // Q = q I with q > 0 as last uploaded (two-group block filter applies)
-  double q_last = 0.0, p_diag_max = 0.0;      // Q[0][0] and max_i P[i][i] as last uploaded: the give-up policy of the Newton-Schulz starts (update_ns_policy)
-  double* Kpart = nullptr;
-  double* Kmat = nullptr;
-  double* Acoef = nullptr;     // 2 x RB x RM   (ping-pong across pipelined blocks)
-  double* Bcoef = nullptr;     // 2 x RB x RB
-  double* XGpart = nullptr;    // BLK_GRAM_WG x (RB + XGB) x XGB
-  double* XG = nullptr;        // 2 x (RB + XGB) x XGB
-  long long* flags = nullptr;  // device-flag hand-off of the pipelined blocks (psmf_block.hip): xg_seq, filt_seq, abort
-  long long seq_next = 1;      // sequence number of the next block to be enqueued
-  hipStream_t bulk = nullptr;  // Gram / cross-Gram / apply of the pipelined blocked engine
-  hipEvent_t evF[4] = {}, evA[4] = {}, evX[4] = {}, evS = nullptr;
-  size_t scratch_bytes = 0;
-  int64_t T_cap = 0;
-  StepParams sp;
-  hipGraph_t graph = nullptr;
-  hipGraphExec_t gexec = nullptr;
-  int chunk = 0;
-  // persistent per-step engine (psmf_pstep.hip): geometry of a launch and its communication block (flags | packet | partial rows)
-  psmf::PstepPlan ps_plan = {};
-  bool ps_ok = false;
-  void* ps_comm = nullptr;
-  long long* ps_prof = nullptr;    // PSMF_PSTEP_PROF=1 with a -DPSTEP_PROF build: per-phase clock sums of the last launch, printed at psmf_destroy
-  long long ps_prof_steps = 0;
-  long long ps_launches = 0;
-  bool have_state = false;
-  bool need_prep = true;
-  int64_t k_done = 0;
-  ncclComm_t comm = nullptr;
-  int nranks = 1, rank = 0;
-  bool use_coll = false;   // per-step all-reduce on (nranks > 1, or forced for single-GPU testing)
-  // host-mediated collective (psmf_comm_init_host): the sum-all-reduce goes through a caller-supplied function
-  psmf_allreduce_fn host_fn = nullptr;
-  void* host_ctx = nullptr;
-  double* host_buf = nullptr;      // pinned staging buffer, kHostBufElems doubles
-  static constexpr size_t kHostBufElems = 8192;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  int* err_host = nullptr;     // pinned, device-mapped: a one-thread kernel publishes the device error flag here
-  int* err_host_dev = nullptr;
-  std::string err;
-  size_t elem() const { return cfg.storage == PSMF_F64 ? 8 : 4; }
-};
-
-namespace {
-
-int fail(psmf_handle h, int code, const std::string& msg) {
-  if (h) h->err = msg; else g_create_error = msg;
-  return code;
-}
-
-#define HIP_TRY(h, expr)                                                                   \
-  do {                                                                                     \
-    hipError_t e_ = (expr);                                                                \
-    if (e_ != hipSuccess)                                                                  \
-      return fail(h, PSMF_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));    \
-  } while (0)
-
-#define NCCL_TRY(h, expr)                                                                  \
-  do {                                                                                     \
-    ncclResult_t e_ = (expr);                                                              \
-    if (e_ != ncclSuccess)                                                                 \
-      return fail(h, PSMF_ERR_RCCL, std::string(#expr) + ": " + ncclGetErrorString(e_));  \
-  } while (0)
-
-int next_pow2(int x) { int p = 1; while (p < x) p <<= 1; return p; }
-
-// The one dispatch on the storage type: f(T()) with T = double or float (the argument only carries the type: decltype(t)).
-template <typename F>
-auto by_storage(const psmf_filter* h, F&& f) { return h->cfg.storage == PSMF_F64 ? f(double()) : f(float()); }
-
-// A kernel whose dynamic LDS may need the opt-in (hipFuncAttributeMaxDynamicSharedMemorySize): psmf_create sets it for the
-// kernels the handle can launch (opt_in_lds), on the handle's device; the launchers only launch.
-template <typename Fn>
-struct LdsKernel { Fn fn; int threads; size_t lds; };
-
-// Completion waits by polling: hipStreamSynchronize / hipEventSynchronize fall back to an interrupt wait that, on this
-// stack, now and then returns ~70 ms after the work is done (seen as wall time without matching event time).
-hipError_t spin_stream(hipStream_t s) {
-  hipError_t e;
-  while ((e = hipStreamQuery(s)) == hipErrorNotReady) { __builtin_ia32_pause(); }
-  return e;
-}
-hipError_t spin_event(hipEvent_t ev) {
-  hipError_t e;
-  while ((e = hipEventQuery(ev)) == hipErrorNotReady) { __builtin_ia32_pause(); }
-  return e;
-}
 
 // The one exchange of the sharded engines: in-place sum of `count` float64 on the device over all ranks.  RCCL on the given
 // stream, or -- host-mediated communicator -- device -> pinned host -> caller's function -> device, synchronously.
@@ -241,6 +45,15 @@ int all_reduce_sum(psmf_filter* h, double* buf, size_t count, hipStream_t s) {
   NCCL_TRY(h, ncclAllReduce(buf, buf, count, ncclDouble, ncclSum, h->comm, s));
   return PSMF_OK;
 }
+
+namespace {
+
+int next_pow2(int x) { int p = 1; while (p < x) p <<= 1; return p; }
+
+// A kernel whose dynamic LDS may need the opt-in (hipFuncAttributeMaxDynamicSharedMemorySize): psmf_create sets it for the
+// kernels the handle can launch (opt_in_lds), on the handle's device; the launchers only launch.
+template <typename Fn>
+struct LdsKernel { Fn fn; int threads; size_t lds; };
 
 typedef void (*sweep_fn_t)(StepParams);
 typedef void (*serial_fn_t)(StepParams, int);
@@ -313,89 +126,7 @@ int enqueue_step(psmf_filter* h) {
   return PSMF_OK;
 }
 
-// one block of nb steps of the blocked engine: Gram, reduction, (all-reduce), coefficient-space filter, apply
-void fill_block_params(psmf_filter* h, psmf::BlockParams& b, int64_t k0, int nb, int slot = 0) {
-  memset(&b, 0, sizeof(b));
-  b.last = 1;            // standalone block; the pipelined loop clears it for all but a run's last block
-  b.sp = h->sp;
-  b.Kpart = h->Kpart; b.K = h->Kmat;
-  b.Acoef = h->Acoef + (size_t)slot * psmf::RB * psmf::RM;
-  b.Bcoef = h->Bcoef + (size_t)slot * psmf::RB * psmf::RB;
-  b.XGpart = h->XGpart;
-  b.k0 = k0; b.nb = nb;
-  b.gram_rows = (h->cfg.d_local + psmf::BLK_GRAM_WG - 1) / psmf::BLK_GRAM_WG;
-}
-
-void launch_blk_gram(psmf_filter* h, const psmf::BlockParams& b, hipStream_t stream = nullptr) {
-  if (!stream) stream = h->stream;
-  by_storage(h, [&](auto t) { hipLaunchKernelGGL(psmf::psmf_blk_gram_mfma<decltype(t)>, dim3(psmf::BLK_GRAM_WG), dim3(psmf::WG), 0, stream, b); });
-  hipLaunchKernelGGL(psmf::psmf_blk_reduce, dim3(psmf::RB * psmf::RB / 128), dim3(128), 0, stream, b, (int)psmf::BLK_GRAM_WG);
-}
-
-// streaming bulk kernels (psmf_bulk.hip): float32 storage, d_local a multiple of 4, 16 <= r <= 32
-bool blk_bulk2_ok(const psmf_filter* h) {
-  return h->sw.bulk2 && h->cfg.storage == PSMF_F32 && (h->cfg.d_local % 4) == 0 && h->cfg.r <= 32 && (h->geo.rp % 4) == 0;
-}
-
-void launch_blk_xgram(psmf_filter* h, const psmf::BlockParams& x, double* xg, hipStream_t stream) {
-  const size_t xg_elems = (size_t)(psmf::RB + psmf::XGB) * psmf::XGB;
-  if (blk_bulk2_ok(h)) {
-    const int nct = (h->block_steps + 15) / 16;
-    const size_t lds = psmf::blk_xgram2_lds_bytes();
-    if (nct <= 2) {
-      hipLaunchKernelGGL(psmf::psmf_blk_xgram2<2>, dim3(h->bulk_wgs), dim3(psmf::BK_NT), lds, stream, x);
-      hipLaunchKernelGGL(psmf::psmf_blk_xreduce2<2>, dim3(6 * 2 * 256 / 32), dim3(256), 0, stream, (const double*)x.XGpart, xg, h->bulk_wgs);
-    } else {
-      hipLaunchKernelGGL(psmf::psmf_blk_xgram2<3>, dim3(h->bulk_wgs), dim3(psmf::BK_NT), lds, stream, x);
-      hipLaunchKernelGGL(psmf::psmf_blk_xreduce2<3>, dim3(7 * 3 * 256 / 32), dim3(256), 0, stream, (const double*)x.XGpart, xg, h->bulk_wgs);
-    }
-    return;
-  }
-  by_storage(h, [&](auto t) { hipLaunchKernelGGL(psmf::psmf_blk_xgram_mfma<decltype(t)>, dim3(psmf::BLK_GRAM_WG), dim3(psmf::WG), 0, stream, x); });
-  hipLaunchKernelGGL(psmf::psmf_blk_xreduce, dim3((int)(xg_elems / 128)), dim3(128), 0, stream, x, xg, (int)psmf::BLK_GRAM_WG);
-}
-
-bool blk_small_dual(const psmf_filter* h);
-bool blk_use_filter3(const psmf_filter* h) { return h->sw.filter3 && !blk_small_dual(h); }
-
-bool blk_dual_ok(const psmf_filter* h) {
-  // The two-inversion kernels (filter3, filter3s, filter2) read rho and q ONCE per block: per-step R_k / Q_k schedules
-  // (psmf_set_schedules; the reference reads R[k], Q[k] every step, psmf.py:115,123,141) go to the general kernel.
-  return h->sw.block_dual && h->q_iso && h->cfg.coef_update && h->cfg.pbar_predict && h->cfg.eta_full &&
-         h->cfg.dyn_kind == PSMF_DYN_RANDOM_WALK && !h->sp.rho_sched && !h->sp.q_sched;
-}
-
-// filter4 (psmf_blk4.hip): the role-specialised kernel for diagonal-Jacobian dynamics -- cos-phase, unscaled sinusoid, and the
-// random walk when R_k / Q_k schedules keep it off filter3 -- full filter, Q = q I, r <= 32; the recursive classes included
-// filter6 (psmf_blk16.hip): the general block filter for r <= 16, role-specialised -- whatever filter3s / filter5 do not take,
-// INCLUDING what filter4s would (measured at r = 10, d = 2e4: cos-phase full filter 117 k timesteps/s on filter4s, 316 k on
-// filter6; its recursive form 196 k against 214 k)
-bool blk_small_ok(const psmf_filter* h) { return h->sw.filter6 && h->cfg.r <= psmf::F6_RMAX; }
-
-// ... and the default model too (random walk, Q = q I; PSMF_FILTER6_DUAL=0: filter3s), psmf_blk_filter6d
-bool blk_small_dual(const psmf_filter* h) { return h->sw.filter6_dual && blk_small_ok(h) && blk_dual_ok(h); }
-
-bool blk_seq_ok(const psmf_filter* h) {
-  if (blk_small_ok(h)) return false;
-  const int kd = h->cfg.dyn_kind;
-  const bool diag_dyn = kd == PSMF_DYN_RANDOM_WALK || kd == PSMF_DYN_COS_PHASE || (kd == PSMF_DYN_SINUSOID && !(h->cfg.dyn_flags & 1));
-  return h->sw.filter4 && h->sw.filter3 && h->sw.block_dual && h->q_iso && h->cfg.coef_update && h->cfg.pbar_predict && h->cfg.eta_full && diag_dyn &&
-         h->cfg.r <= 32 && h->cfg.recursive != 2;      // (in-loop SGD: the kernels with dyn_adam_step carry it, filter4 / filter5 have an Adam step of their own)
-}
-
-// filter5: the simplified hook configuration (no coefficient update, eta = tr(R) / d, P_bar = P) with diagonal-Jacobian dynamics
-bool blk_simpl_ok(const psmf_filter* h) {
-  const int kd = h->cfg.dyn_kind;
-  const bool diag_dyn = kd == PSMF_DYN_RANDOM_WALK || kd == PSMF_DYN_COS_PHASE || (kd == PSMF_DYN_SINUSOID && !(h->cfg.dyn_flags & 1));
-  return h->sw.filter4 && h->sw.filter3 && !h->cfg.coef_update && !h->cfg.eta_full && !h->cfg.pbar_predict && diag_dyn && h->cfg.r <= 32 &&
-         !h->sp.q_sched && h->cfg.recursive != 2;
-}
-
-// The ONE place that decides which kernel advances the coefficient-space state of a block: launch_blk_filter switches on it
-// and psmf_filter_kernel reports it (tests and bench.py quote that name as evidence of what ran).  Values = the codes of
-// psmf_filter_kernel in include/psmf_hip.h.
-enum FilterKernel { FK_STEP = 0, FK_GENERAL = 1, FK_FILTER2 = 2, FK_FILTER3 = 3, FK_FILTER3S = 4, FK_FILTER4 = 5, FK_FILTER4S = 6,
-                    FK_FILTER5 = 7, FK_FILTER6 = 8, FK_FILTER6D = 9, FK_FILTER7 = 10, FK_PSTEP = 11 };
+}  // namespace
 
 // Can the handle's next run go through the persistent per-step kernel?  (one rank, uniform diagonal R, random walk or cos-phase
 // dynamics, r <= 32, rows that fit the row workgroups' registers, unmasked or the masked PSMF / rPSMF filter; everything else keeps
@@ -406,207 +137,7 @@ bool pstep_usable(const psmf_filter* h) {
          !h->cfg.nonuniform_R && h->cfg.dyn_kind <= PSMF_DYN_COS_PHASE && !h->sp.solve_lds && !h->sp.q_mat;
 }
 
-FilterKernel select_filter_kernel(const psmf_filter* h) {
-  if (h->engine != 2) return pstep_usable(h) ? FK_PSTEP : FK_STEP;
-  if (blk_simpl_ok(h)) return FK_FILTER5;
-  const bool dual3 = blk_dual_ok(h) && blk_use_filter3(h);
-  if (!dual3 && blk_seq_ok(h)) return h->cfg.r > 16 ? FK_FILTER4 : FK_FILTER4S;
-  if (blk_small_dual(h)) return FK_FILTER6D;      // random walk, Q = q I at r <= 16: filter6 with the two inversions side by side
-  if (dual3) return h->cfg.r > 16 ? FK_FILTER3 : FK_FILTER3S;
-  if (blk_dual_ok(h)) return FK_FILTER2;
-  if (blk_small_ok(h)) return FK_FILTER6;
-  // 17 <= r <= 32, whatever is left (dense Jacobians, a general Q, ...): filter6's design on 2 x 2 tiles (psmf_blk32.hip)
-  return (h->sw.filter7 && h->cfg.r > psmf::F6_RMAX && h->cfg.r <= 32) ? FK_FILTER7 : FK_GENERAL;
-}
-
-void launch_blk_filter(psmf_filter* h, const psmf::BlockParams& b, hipStream_t stream = nullptr) {
-  if (!stream) stream = h->stream;
-  const size_t lds3 = psmf::blk_filter3_lds_bytes(), lds = psmf::blk_filter_lds_bytes();
-  const FilterKernel fk = select_filter_kernel(h);
-  switch (fk) {
-    case FK_FILTER5: hipLaunchKernelGGL(psmf::psmf_blk_filter5, dim3(1), dim3(psmf::F3_NT), lds3, stream, b); return;
-    case FK_FILTER4:
-    case FK_FILTER4S: {
-      // filter4's fallback is the wave-local sweep (~5 us, five to six iterations' worth; filter3's LDS sweep: 15 us): a start
-      // beyond ||R||_F = 0.6 is cheaper swept than iterated (PSMF_NS_FAR4)
-      psmf::BlockParams b4 = b;
-      if (!h->sw.ns_far_set) b4.sp.ns_far2 = h->sw.ns_far4 * h->sw.ns_far4;
-      if (fk == FK_FILTER4) hipLaunchKernelGGL(psmf::psmf_blk_filter4, dim3(1), dim3(psmf::F3_NT), lds3, stream, b4);
-      else hipLaunchKernelGGL(psmf::psmf_blk_filter4s, dim3(1), dim3(psmf::F3_NT), lds3, stream, b4);
-      return;
-    }
-    case FK_FILTER6D: {
-      psmf::BlockParams b2 = b;
-      b2.dual6 = 1;
-      hipLaunchKernelGGL(psmf::psmf_blk_filter6d, dim3(1), dim3(psmf::WG), lds, stream, b2);
-      return;
-    }
-    case FK_FILTER3: hipLaunchKernelGGL(psmf::psmf_blk_filter3, dim3(1), dim3(psmf::F3_NT), lds3, stream, b); return;
-    case FK_FILTER3S: hipLaunchKernelGGL(psmf::psmf_blk_filter3s, dim3(1), dim3(psmf::F3_NT), lds3, stream, b); return;
-    case FK_FILTER2: {
-      const size_t lds2 = psmf::blk_filter2_lds_bytes();
-      switch (h->geo.rpad) {
-        case 8: hipLaunchKernelGGL(psmf::psmf_blk_filter2<8>, dim3(1), dim3(2 * psmf::WG), lds2, stream, b); break;
-        case 16: hipLaunchKernelGGL(psmf::psmf_blk_filter2<16>, dim3(1), dim3(2 * psmf::WG), lds2, stream, b); break;
-        default: hipLaunchKernelGGL(psmf::psmf_blk_filter2<32>, dim3(1), dim3(2 * psmf::WG), lds2, stream, b); break;
-      }
-      return;
-    }
-    case FK_FILTER6: hipLaunchKernelGGL(psmf::psmf_blk_filter6, dim3(1), dim3(psmf::WG), lds, stream, b); return;
-    case FK_FILTER7: hipLaunchKernelGGL(psmf::psmf_blk_filter7, dim3(1), dim3(psmf::WG), lds, stream, b); return;
-    case FK_GENERAL:
-    case FK_STEP:
-    case FK_PSTEP:
-      break;
-  }
-  switch (h->geo.rpad) {
-    case 8: hipLaunchKernelGGL(psmf::psmf_blk_filter<8>, dim3(1), dim3(psmf::WG), lds, stream, b); break;
-    case 16: hipLaunchKernelGGL(psmf::psmf_blk_filter<16>, dim3(1), dim3(psmf::WG), lds, stream, b); break;
-    default: hipLaunchKernelGGL(psmf::psmf_blk_filter<32>, dim3(1), dim3(psmf::WG), lds, stream, b); break;
-  }
-}
-
-void launch_blk_apply(psmf_filter* h, const psmf::BlockParams& b, hipStream_t stream = nullptr) {
-  if (!stream) stream = h->stream;
-  if (blk_bulk2_ok(h)) {
-    const int nyc = (h->block_steps + 15) / 16;
-    const size_t lds = psmf::blk_apply2_lds_bytes();
-    if (nyc <= 2) hipLaunchKernelGGL(psmf::psmf_blk_apply2<2>, dim3(h->bulk_wgs), dim3(psmf::BK_NT), lds, stream, b);
-    else hipLaunchKernelGGL(psmf::psmf_blk_apply2<3>, dim3(h->bulk_wgs), dim3(psmf::BK_NT), lds, stream, b);
-    return;
-  }
-  const int nslab = (h->cfg.d_local + 15) / 16;
-  int g = (nslab + 3) / 4;
-  if (g > 1024) g = 1024;
-  const size_t lds = psmf::blk_apply_lds_bytes();
-  by_storage(h, [&](auto t) { hipLaunchKernelGGL(psmf::psmf_blk_apply_mfma<decltype(t)>, dim3(g), dim3(psmf::WG), lds, stream, b); });
-}
-
-int enqueue_block(psmf_filter* h, int64_t k0, int nb) {
-  psmf::BlockParams b;
-  fill_block_params(h, b, k0, nb);
-  launch_blk_gram(h, b);
-  if (h->use_coll) { const int rc = all_reduce_sum(h, h->Kmat, psmf::RB * psmf::RB, h->stream); if (rc) return rc; }
-  launch_blk_filter(h, b);
-  launch_blk_apply(h, b);
-  return PSMF_OK;
-}
-
-// Pipelined blocks: the filter kernels chain back to back on the main stream; Gram of the first block,
-// cross-Grams (one block ahead) and applies run on the bulk stream, synchronised with events:
-//   bulk:  gram(0) | xgram(1) | [filter(0)] apply(0) | xgram(2) | [filter(1)] apply(1) | ...
-//   main:  [gram(0)] filter(0) | [xgram(1)] filter(1) | [xgram(2)] filter(2) | ...
-// xgram(b+1) reads C before apply(b) rewrites it (stream order on bulk); the ping-pong coefficient
-// buffers of block b are rewritten by filter(b+2), which waits for xgram(b+2), enqueued after apply(b).
-double host_now_ms() {
-  using namespace std::chrono;
-  return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
-}
-
-int enqueue_blocks_pipelined(psmf_filter* h, int64_t k_begin, int64_t k_end) {
-  const int B = h->block_steps;
-  const double t_enq0 = h->sw.host_timing ? host_now_ms() : 0.0;
-  double t_prev = t_enq0, t_worst = 0.0;
-  long long worst_blk = -1;
-  const int64_t nblk = (k_end - k_begin + B - 1) / B;
-  auto k0_of = [&](int64_t b) { return k_begin + b * B; };
-  auto nb_of = [&](int64_t b) { const int64_t left = k_end - k0_of(b); return (int)(left < B ? left : B); };
-  const size_t xg_elems = (size_t)(psmf::RB + psmf::XGB) * psmf::XGB;
-  HIP_TRY(h, hipEventRecord(h->evS, h->stream));            // everything enqueued so far (state uploads) is visible to bulk
-  HIP_TRY(h, hipStreamWaitEvent(h->bulk, h->evS, 0));
-  hipStream_t fs = h->fstream ? h->fstream : h->stream;    // the filter chain (its own CUs when the mask streams exist)
-  if (h->fstream) HIP_TRY(h, hipStreamWaitEvent(fs, h->evS, 0));
-  psmf::BlockParams b;
-  // hand-off by device flags when the filter chain has a stream (hardware queue) of its own; by events otherwise
-  const bool flags_off = !h->sw.block_flags;
-  // (a tool that serialises dispatches: events.  A host-mediated communicator synchronises the bulk stream at every exchange
-  //  anyway, and several such handles usually share one process and one GPU -- shards of a test -- where kernels that spin on
-  //  flags could end up behind each other in a shared hardware queue: events there, too -- unless PSMF_HOST_COMM_FLAGS=1 asks for the
-  //  flags, which is how tests/test_hip_multishard.py runs the flag hand-off and the chained launch with more than one shard)
-  const bool use_flags = h->fstream != nullptr && h->flags != nullptr && !flags_off && h->streams_concurrent && (!h->host_fn || h->sw.host_comm_flags);
-  const long long s0 = h->seq_next;
-  h->seq_next += nblk;
-  // chain: the filter kernels of the whole run as ONE launch (psmf_blk_filter3; the bulk stream is driven as before)
-  const bool chain_off = !h->sw.block_chain;
-  const bool chain = use_flags && !chain_off && nblk > 1 && ((blk_dual_ok(h) && blk_use_filter3(h)) || blk_seq_ok(h) || blk_simpl_ok(h));
-  // first block: plain Gram of the stored C
-  fill_block_params(h, b, k0_of(0), nb_of(0), 0);
-  launch_blk_gram(h, b, h->bulk);
-  if (h->use_coll) { const int rc = all_reduce_sum(h, h->Kmat, psmf::RB * psmf::RB, h->bulk); if (rc) return rc; }
-  if (use_flags) hipLaunchKernelGGL(psmf::psmf_flag_set_k, dim3(1), dim3(1), 0, h->bulk, h->flags + 0, s0);
-  else HIP_TRY(h, hipEventRecord(h->evX[0], h->bulk));
-  if (chain) {
-    psmf::BlockParams c;
-    fill_block_params(h, c, k0_of(0), nb_of(0), 0);
-    c.flags = h->flags;
-    c.seq = s0;
-    c.last = 1;
-    c.chain = (int)nblk;
-    c.chain_B = B;
-    c.chain_kend = k_end;
-    c.carry = h->sw.chain_carry ? 1 : 0;
-    c.Acoef0 = h->Acoef;
-    c.Bcoef0 = h->Bcoef;
-    c.XG0 = h->XG;
-    const int slot_ev = h->evk_pending < psmf_filter::kTimedRuns ? h->evk_pending : -1;
-    if (slot_ev >= 0) HIP_TRY(h, hipEventRecord(h->evK0[slot_ev], fs));
-    launch_blk_filter(h, c, fs);
-    if (slot_ev >= 0) { HIP_TRY(h, hipEventRecord(h->evK1[slot_ev], fs)); ++h->evk_pending; }
-    HIP_TRY(h, hipEventRecord(h->evC, fs));
-  }
-  for (int64_t bi = 0; bi < nblk; ++bi) {
-    const int slot = (int)(bi & 1);
-    // bulk: cross-Gram for block bi + 1 (needs C as of the start of block bi)
-    if (bi + 1 < nblk) {
-      psmf::BlockParams x;
-      fill_block_params(h, x, k0_of(bi), nb_of(bi), slot);
-      x.k1 = k0_of(bi + 1);
-      x.nb1 = nb_of(bi + 1);
-      double* xg = h->XG + (size_t)((bi + 1) & 1) * xg_elems;
-      launch_blk_xgram(h, x, xg, h->bulk);
-      if (h->use_coll) { const int rc = all_reduce_sum(h, xg, xg_elems, h->bulk); if (rc) return rc; }
-      if (use_flags) hipLaunchKernelGGL(psmf::psmf_flag_set_k, dim3(1), dim3(1), 0, h->bulk, h->flags + 0, s0 + bi + 1);
-      else HIP_TRY(h, hipEventRecord(h->evX[(bi + 1) & 3], h->bulk));
-    }
-    // filter stream: filter of block bi
-    fill_block_params(h, b, k0_of(bi), nb_of(bi), slot);
-    if (bi > 0) {
-      b.assemble = 1;
-      b.XG = h->XG + (size_t)(bi & 1) * xg_elems;
-      b.Aprev = h->Acoef + (size_t)(slot ^ 1) * psmf::RB * psmf::RM;
-    }
-    b.last = (bi + 1 == nblk) ? 1 : 0;
-    if (use_flags) {
-      b.flags = h->flags;
-      b.seq = s0 + bi;
-      if (!chain) {
-        launch_blk_filter(h, b, fs);
-        if (bi + 1 == nblk) hipLaunchKernelGGL(psmf::psmf_flag_set_k, dim3(1), dim3(1), 0, fs, h->flags + 1, s0 + nblk);   // the last block has no successor to announce it
-      }
-      hipLaunchKernelGGL(psmf::psmf_flag_wait_k, dim3(1), dim3(64), 0, h->bulk, h->flags, s0 + bi + 1, h->st);
-    } else {
-      HIP_TRY(h, hipStreamWaitEvent(fs, h->evX[bi & 3], 0));
-      launch_blk_filter(h, b, fs);
-      HIP_TRY(h, hipEventRecord(h->evF[bi & 3], fs));
-      HIP_TRY(h, hipStreamWaitEvent(h->bulk, h->evF[bi & 3], 0));
-    }
-    // bulk: apply of block bi
-    launch_blk_apply(h, b, h->bulk);
-    HIP_TRY(h, hipEventRecord(h->evA[bi & 3], h->bulk));
-    if (h->sw.host_timing) { const double t = host_now_ms(); if (t - t_prev > t_worst) { t_worst = t - t_prev; worst_blk = bi; } t_prev = t; }
-  }
-  if (h->sw.host_timing) {
-    const double t = host_now_ms();
-    if (t - t_enq0 > 20.0 || t_worst > 5.0)
-      fprintf(stderr, "[psmf host timing] enqueue of %lld blocks took %.1f ms, slowest block's calls %.1f ms (block %lld)\n", (long long)nblk, t - t_enq0, t_worst, worst_blk);
-  }
-  HIP_TRY(h, hipStreamWaitEvent(h->stream, h->evA[(nblk - 1) & 3], 0));   // the main stream sees the final C / y_hat
-  // ... and the r x r state: the chained kernel writes DevState in its tail, after it has released the last apply, so the end of
-  // that launch (not the apply alone) is what host reads / the next run's preparation on the main stream have to follow
-  if (chain) HIP_TRY(h, hipStreamWaitEvent(h->stream, h->evC, 0));
-  HIP_TRY(h, hipGetLastError());
-  return PSMF_OK;
-}
+namespace {
 
 int enqueue_gram_into(psmf_filter* h, double* Gout, const DevState* wst, const double* rho_rows) {
   const int r = h->cfg.r;
@@ -862,7 +393,7 @@ int prepare(psmf_filter* h, int64_t k_begin) {
   // step counter and error flag by a one-thread kernel (its arguments travel with the launch): no host buffer to keep
   // alive, so no synchronisation here -- consecutive passes over the series queue up back to back
   hipLaunchKernelGGL(psmf::psmf_prepare_k, dim3(1), dim3(1), 0, h->stream, h->st, (long long)k_begin);
-  if (h->flags) hipLaunchKernelGGL(psmf::psmf_flag_set_k, dim3(1), dim3(1), 0, h->stream, h->flags + 2, 0LL);
+  if (h->flags) clear_block_abort_flag(h);
   if (h->mu_hist)
     HIP_TRY(h, hipMemcpyAsync(h->mu_hist + (size_t)(k_begin - h->sp.series_t0) * h->cfg.r, h->st->mu, h->cfg.r * sizeof(double),
                               hipMemcpyDeviceToDevice, h->stream));
@@ -969,106 +500,6 @@ int alloc_common(psmf_filter* h) {
   h->th_cap = (size_t)(cfg->n_theta > psmf::RM ? cfg->n_theta : psmf::RM);
   HIP_TRY(h, hipMalloc((void**)&h->thbuf, 4 * h->th_cap * sizeof(double)));
   HIP_TRY(h, hipMemset(h->thbuf, 0, 4 * h->th_cap * sizeof(double)));
-  return PSMF_OK;
-}
-
-int opt_in_lds(psmf_filter* h, const void* fn, size_t bytes) {
-  HIP_TRY(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-  return PSMF_OK;
-}
-
-// blocked engine: buffers, CU-masked streams, events, the concurrency probe, the LDS opt-in of its kernels
-int init_blocked(psmf_filter* h) {
-  const psmf_config* cfg = &h->cfg;
-  // B = 64 - r timesteps per block, at most 48: the role-specialised filter kernel and the streaming bulk kernels stage
-  // up to three 16-column tiles of a series block (r < 16 would otherwise give blocks of 49..63)
-  h->block_steps = psmf::RB - cfg->r < 48 ? psmf::RB - cfg->r : 48;
-  HIP_TRY(h, hipMalloc((void**)&h->Kpart, (size_t)psmf::BLK_GRAM_WG * psmf::RB * psmf::RB * sizeof(double)));
-  HIP_TRY(h, hipMalloc((void**)&h->Kmat, (size_t)psmf::RB * psmf::RB * sizeof(double)));
-  HIP_TRY(h, hipMalloc((void**)&h->Acoef, (size_t)2 * psmf::RB * psmf::RM * sizeof(double)));
-  HIP_TRY(h, hipMalloc((void**)&h->Bcoef, (size_t)2 * psmf::RB * psmf::RB * sizeof(double)));
-  HIP_TRY(h, hipMemset(h->Bcoef, 0, (size_t)2 * psmf::RB * psmf::RB * sizeof(double)));
-  HIP_TRY(h, hipMalloc((void**)&h->XGpart, (size_t)psmf::BLK_GRAM_WG * (psmf::RB + psmf::XGB) * psmf::XGB * sizeof(double)));
-  HIP_TRY(h, hipMalloc((void**)&h->XG, (size_t)2 * (psmf::RB + psmf::XGB) * psmf::XGB * sizeof(double)));
-  HIP_TRY(h, hipMemset(h->XG, 0, (size_t)2 * (psmf::RB + psmf::XGB) * psmf::XGB * sizeof(double)));   // the all-reduce covers entries no kernel writes
-  HIP_TRY(h, hipMalloc((void**)&h->flags, 8 * sizeof(long long)));
-  HIP_TRY(h, hipMemset(h->flags, 0, 8 * sizeof(long long)));
-  // The filter chain is one workgroup on the critical path; the bulk kernels (cross-Gram, apply) run
-  // beside it and would be co-scheduled onto its CU, stretching it by 10-17 % (measured).  Partition the
-  // chip with CU masks: the filter's stream owns `nres` CUs, the bulk stream the others.
-  const int nres = h->sw.reserved_cus;
-  hipDeviceProp_t prop;
-  HIP_TRY(h, hipGetDeviceProperties(&prop, cfg->device));
-  const int ncu = prop.multiProcessorCount;
-  const int words = (ncu + 31) / 32;
-  // The split below is written for the unpartitioned MI355X: 256 CUs = 8 XCDs x 4 shader engines x 8 CUs, mask bit =
-  // 32 cu + 8 se + xcc (tools/xcc_probe.hip).  On any other device (a CPX / NPS partition, another part) the bit layout and the
-  // engine count are not known here: no CU masks, plain streams -- the filter chain then shares CUs with the bulk kernels
-  // (10-17 % slower, measured), which is a speed matter only.
-  const bool known_layout = ncu == 256;
-  if (known_layout && nres > 0 && nres < ncu / 2 && words <= 16) {
-    uint32_t mf[16] = {0}, mb[16] = {0};
-    for (int i = 0; i < ncu; ++i) (i < nres ? mf : mb)[i >> 5] |= 1u << (i & 31);
-    hipStream_t fs = nullptr, bs = nullptr;
-    if (hipExtStreamCreateWithCUMask(&fs, words, mf) == hipSuccess && hipExtStreamCreateWithCUMask(&bs, words, mb) == hipSuccess) {
-      h->fstream = fs;
-      h->bulk = bs;
-      h->reserved_cus = nres;
-      // The streaming kernels hold one 512-thread workgroup per CU (86-131 KB of LDS), and the dispatcher deals workgroups
-      // to the 32 shader engines (8 XCDs x 4) in equal shares whatever the mask has left each of them.  The filter's
-      // 8 CUs are CU 0 of engine 0 of every XCD (mask bit = 32 cu + 8 se + xcc, tools/xcc_probe.hip): those engines
-      // keep 7 CUs, so with more than 7 workgroups per engine one CU gets a second one and the kernel takes two
-      // rounds -- 231 / 317 us per block at d = 1e6 with 248 or 256 workgroups against 138 / 193 us with 224
-      // (tools/bulk_stream.hip; 124 / 172 us on the unmasked chip).  Hence (CUs per engine - 1) x 32.
-      const int n_engines = 32, per_engine = ncu / n_engines - (nres + n_engines - 1) / n_engines;
-      h->bulk_wgs = per_engine >= 1 ? per_engine * n_engines : 8;
-      if (h->bulk_wgs > 256) h->bulk_wgs = 256;
-      { const int v = h->sw.bulk_wgs_env; if (v >= 8 && v <= 256) h->bulk_wgs = (v / 8) * 8; }
-    } else {
-      (void)hipGetLastError();
-      if (fs) hipStreamDestroy(fs);
-      if (bs) hipStreamDestroy(bs);
-    }
-  }
-  if (!h->bulk) HIP_TRY(h, hipStreamCreateWithFlags(&h->bulk, hipStreamNonBlocking));
-  for (int i = 0; i < 4; ++i) {
-    HIP_TRY(h, hipEventCreateWithFlags(&h->evF[i], hipEventDisableTiming));
-    HIP_TRY(h, hipEventCreateWithFlags(&h->evA[i], hipEventDisableTiming));
-    HIP_TRY(h, hipEventCreateWithFlags(&h->evX[i], hipEventDisableTiming));
-  }
-  HIP_TRY(h, hipEventCreateWithFlags(&h->evS, hipEventDisableTiming));
-  HIP_TRY(h, hipEventCreateWithFlags(&h->evC, hipEventDisableTiming));
-  for (int i = 0; i < psmf_filter::kTimedRuns; ++i) { HIP_TRY(h, hipEventCreate(&h->evK0[i])); HIP_TRY(h, hipEventCreate(&h->evK1[i])); }
-  if (h->fstream && h->flags) {
-    // the device-flag hand-off and the chained filter launches need the two streams to run concurrently: probe it (a waiter on the filter stream, then the
-    // setter on the bulk stream; the waiter gives up after 50 ms)
-    int* dres = nullptr;
-    struct FreeOnExit { int** p; ~FreeOnExit() { if (*p) { hipFree(*p); *p = nullptr; } } } dres_guard{&dres};      // also on the HIP_TRY failure paths below
-    HIP_TRY(h, hipMalloc((void**)&dres, sizeof(int)));
-    HIP_TRY(h, hipMemset(dres, 0, sizeof(int)));
-    HIP_TRY(h, hipDeviceSynchronize());      // hipMemset is asynchronous on the null stream, the probe's streams are non-blocking: the zeroes (of dres and of h->flags above) first
-    hipLaunchKernelGGL(psmf::psmf_probe_wait_k, dim3(1), dim3(1), 0, h->fstream, h->flags + 7, 1LL, 5000000LL, dres);
-    hipLaunchKernelGGL(psmf::psmf_flag_set_k, dim3(1), dim3(1), 0, h->bulk, h->flags + 7, 1LL);
-    HIP_TRY(h, hipStreamSynchronize(h->fstream));
-    HIP_TRY(h, hipStreamSynchronize(h->bulk));
-    int res = 0;
-    HIP_TRY(h, hipMemcpy(&res, dres, sizeof(int), hipMemcpyDeviceToHost));
-    h->streams_concurrent = res == 1;
-  }
-  // function-local: no namespace-scope initialiser takes kernel addresses before the runtime has registered them
-  const size_t flds = psmf::blk_filter_lds_bytes(), flds2 = psmf::blk_filter2_lds_bytes(), flds3 = psmf::blk_filter3_lds_bytes();
-  const size_t alds = psmf::blk_apply_lds_bytes(), alds2 = psmf::blk_apply2_lds_bytes(), xlds2 = psmf::blk_xgram2_lds_bytes();
-  const struct { const void* fn; size_t bytes; } lds_kernels[] = {
-    {(const void*)psmf::psmf_blk_filter6, flds}, {(const void*)psmf::psmf_blk_filter6d, flds}, {(const void*)psmf::psmf_blk_filter7, flds},
-    {(const void*)psmf::psmf_blk_filter<8>, flds}, {(const void*)psmf::psmf_blk_filter<16>, flds}, {(const void*)psmf::psmf_blk_filter<32>, flds},
-    {(const void*)psmf::psmf_blk_apply_mfma<float>, alds}, {(const void*)psmf::psmf_blk_apply_mfma<double>, alds},
-    {(const void*)psmf::psmf_blk_filter3, flds3}, {(const void*)psmf::psmf_blk_filter3s, flds3}, {(const void*)psmf::psmf_blk_filter4, flds3},
-    {(const void*)psmf::psmf_blk_filter4s, flds3}, {(const void*)psmf::psmf_blk_filter5, flds3},
-    {(const void*)psmf::psmf_blk_xgram2<2>, xlds2}, {(const void*)psmf::psmf_blk_xgram2<3>, xlds2},
-    {(const void*)psmf::psmf_blk_apply2<2>, alds2}, {(const void*)psmf::psmf_blk_apply2<3>, alds2},
-    {(const void*)psmf::psmf_blk_filter2<8>, flds2}, {(const void*)psmf::psmf_blk_filter2<16>, flds2}, {(const void*)psmf::psmf_blk_filter2<32>, flds2},
-  };
-  for (const auto& k : lds_kernels) { const int rc = opt_in_lds(h, k.fn, k.bytes); if (rc) return rc; }
   return PSMF_OK;
 }
 
@@ -1632,39 +1063,6 @@ static void free_timing_save(TimingSave& s) {
   s = TimingSave();
 }
 
-static int time_block_kernels(psmf_filter* h, int which, int iters, int nb, const TimingSave& sv, float* avg_us) {
-  psmf::BlockParams b;
-  fill_block_params(h, b, h->sp.series_t0, nb);
-  launch_blk_gram(h, b);           // a valid K for the filter / apply measurements
-  launch_blk_filter(h, b);
-  auto one = [&]() {
-    if (which == 0) { HIP_TRY(h, hipMemcpyAsync(h->st, sv.st, sizeof(DevState), hipMemcpyDeviceToDevice, h->stream)); launch_blk_filter(h, b); }
-    else if (which == 1) {
-      // the per-block d-sized contraction: the cross-Gram for the next block (+ reduction) when the series holds
-      // two blocks, else the plain block Gram
-      if (h->T_cap >= 2 * (int64_t)nb) {
-        psmf::BlockParams x = b;
-        x.k1 = b.k0 + nb; x.nb1 = nb;
-        launch_blk_xgram(h, x, h->XG, h->stream);
-      } else {
-        launch_blk_gram(h, b);
-      }
-    }
-    else launch_blk_apply(h, b);
-    return (int)PSMF_OK;
-  };
-  int rc;
-  for (int i = 0; i < 2; ++i) { rc = one(); if (rc) return rc; }
-  HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
-  for (int i = 0; i < iters; ++i) { rc = one(); if (rc) return rc; }
-  HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
-  HIP_TRY(h, hipEventSynchronize(h->ev1));
-  float ms = 0.f;
-  HIP_TRY(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-  *avg_us = ms * 1000.f / iters;
-  return PSMF_OK;
-}
-
 static int time_step_kernels(psmf_filter* h, int which, int iters, float* avg_us) {
   {  // the sweep reads y_k / writes y_hat_k at the step counter: point it at a valid row of the series
     long long k0 = h->sp.series_t0;
@@ -1704,7 +1102,7 @@ int psmf_time_kernel(psmf_handle h, int which, int iters, float* avg_us) {
     if (serial_launches > h->T_cap) h->sp.mu_hist = nullptr;
     rc = save_for_timing(h, 1, h->sp.mu_hist ? serial_launches + 1 : 0, sv);
   }
-  if (!rc) rc = blocked ? time_block_kernels(h, which, iters, nb, sv, avg_us) : time_step_kernels(h, which, iters, avg_us);
+  if (!rc) rc = blocked ? time_block_kernels(h, which, iters, nb, sv.st, avg_us) : time_step_kernels(h, which, iters, avg_us);
   h->sp.mu_hist = hist;
   if (sv.complete) { const int rc2 = restore_after_timing(h, sv); if (!rc) rc = rc2; }     // (a failed measurement too leaves the state as it found it)
   free_timing_save(sv);
@@ -2267,7 +1665,6 @@ int psmf_comm_init_host(psmf_handle h, int nranks, int rank, psmf_allreduce_fn f
 
 }  // extern "C"
 
-#include "psmf_impute.hip"
 
 // psmf_impute_run beyond one workgroup's LDS (d > 512 or r > 16): the replicas one after the other on the masked per-step engine
 // of the large-d handle (psmf_masked.hip), float64 storage.  ExperimentImpute/PSMF.py:59-95, rPSMF.py:75-148: the prior mean of

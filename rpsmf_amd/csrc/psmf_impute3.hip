@@ -32,7 +32,7 @@
 // partial tiles; e^T e on the matrix cores).  psmf_impute_run picks this kernel when the shape allows (PSMF_IMPUTE_V3=0:
 // version 2).
 #pragma once
-#include "psmf_wave16.hip"     // wave_sweep16m: the single-wave sweep with the lane predicates as multipliers
+#include "psmf_impute2.hip"    // ImputeParams and the routines the two column loops share; wave_sweep16m through psmf_wave16.hip
 
 namespace psmf {
 

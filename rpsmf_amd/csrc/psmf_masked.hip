@@ -19,7 +19,7 @@
 // ExperimentImpute/common.py:79-94) are reduced on the device by psmf_masked_metrics_k; nothing d x n travels.
 #pragma once
 #include "psmf_kernels.hip"
-#include "psmf_blk3.hip"      // f64x4, readlane_f64
+#include "psmf_wave.h"        // f64x4, readlane_f64
 
 namespace psmf {
 

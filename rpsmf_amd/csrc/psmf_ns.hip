@@ -12,11 +12,10 @@
 // NS_S = 34 doubles (conflict-free A-operand reads, 2-way B-operand reads).  No barrier inside the
 // tile routines; the driver's barriers are shared by both halves of a 512-thread workgroup.
 #pragma once
-#include "psmf_device.h"
+#include "psmf_wave.h"      // f64x4, readlane_f64
 
 namespace psmf {
 
-typedef double f64x4 __attribute__((ext_vector_type(4)));
 constexpr int NS_S = 34;           // LDS row stride (doubles)
 constexpr int NS_N = 32;           // padded matrix size
 
@@ -100,10 +99,6 @@ __device__ __forceinline__ void ns_store_tile(double* sX, const f64x4 acc, const
   const int col = 16 * tj + (lane & 15);
 #pragma unroll
   for (int q = 0; q < 4; ++q) sX[(16 * ti + (lane >> 4) + 4 * q) * NS_S + col] = acc[q];
-}
-
-__device__ __forceinline__ double readlane_f64(double v, const int lane) {
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane), __builtin_amdgcn_readlane(__double2loint(v), lane));
 }
 
 // ------------------------------------------------------------------------------------------------------------

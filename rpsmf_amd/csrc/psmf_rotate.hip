@@ -10,7 +10,7 @@
 // workgroup, K in slabs of 16 through LDS.  One-off work per upload / download, not the per-step path: written for correctness
 // and a fair fraction of the float64 MFMA rate, not tuned further.
 #pragma once
-#include "psmf_blk3.hip"      // f64x4
+#include "psmf_wave.h"        // f64x4
 
 namespace psmf {
 

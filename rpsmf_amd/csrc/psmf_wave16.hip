@@ -9,7 +9,8 @@
 // (rpsmf_amd/build.py) so that the 256-thread kernels get their MFMAs with VGPR accumulators (left to itself the compiler, with 512
 // registers per wave on offer, puts them in AGPRs: 16 copies and a 16-cycle stall per pivot round).
 #pragma once
-#include "psmf_blk3.hip"      // readlane_f64, DPP sums, f64x4
+#include "psmf_wave.h"        // readlane_f64, DPP sums, f64x4
+#include "psmf_ns.hip"        // Sw16K, wave_sweep_tiles
 
 namespace psmf {
 

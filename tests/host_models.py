@@ -7,11 +7,11 @@ are exchanged, when, and that the replicated float64 r x r state stays bit-ident
   sharded_epoch_host            per-step engine: row sweep on the local rows, all-reduce of the r + 1 partial sums
                                 (h = C^T e, ee = e^T e) per timestep, tracked Gram (rpsmf_amd/csrc/psmf_kernels.hip)
   blocked_epoch_host            blocked engine, one block after the other: all-reduce of K = Z^T Z per block
-                                (psmf_capi.hip enqueue_block)
+                                (psmf_blocked.hip enqueue_block)
   blocked_pipelined_epoch_host  blocked engine as bench.py runs it: all-reduce of the first block's K, then of one
                                 cross-Gram XG = [Z_b | Y_{b+1}]^T Y_{b+1} per block, from which the next block's K is
-                                assembled with the tracked Gram (psmf_capi.hip enqueue_blocks_pipelined,
-                                psmf_block.hip assemble_K)
+                                assembled with the tracked Gram (psmf_blocked.hip enqueue_blocks_pipelined,
+                                psmf_block.h assemble_K)
 
 Exact time-blocking: within a block of B consecutive steps every innovation e_j lies in the span of
 Z = [C_{k0} | y_{k0+1} ... y_{k0+B}]  (d x (r+B)), so with K = Z^T Z the B steps run in coefficient space:

@@ -1,4 +1,4 @@
-"""The environment switches are stated once: `struct Switches` in rpsmf_amd/csrc/psmf_capi.hip is the native library's only reader of
+"""The environment switches are stated once: `struct Switches` in rpsmf_amd/csrc/psmf_host.h is the native library's only reader of
 the environment, DESIGN section 9 lists the same variables, and every one that selects a kernel or a schedule is named by a test.
 tests/test_hip_switches.py ("a fallback nobody runs rots") is only as good as the list of what exists.  CPU only: reads sources."""
 
@@ -23,10 +23,10 @@ def _read(path):
 
 
 def _switches_struct():
-    """(text before, the struct, text after) of psmf_capi.hip"""
-    text = _read(os.path.join(CSRC, "psmf_capi.hip"))
+    """(text before, the struct, text after) of psmf_host.h"""
+    text = _read(os.path.join(CSRC, "psmf_host.h"))
     m = re.search(r"^struct Switches \{\n.*?^\};\n", text, flags=re.S | re.M)
-    assert m, "struct Switches not found in psmf_capi.hip"
+    assert m, "struct Switches not found in psmf_host.h"
     return text[:m.start()], m.group(0), text[m.end():]
 
 
@@ -48,7 +48,7 @@ def test_switches_is_the_only_reader_of_the_environment():
     assert "getenv(" in struct
     assert "getenv(" not in before and "getenv(" not in after
     for f in sorted(os.listdir(CSRC)):
-        if f != "psmf_capi.hip":
+        if f != "psmf_host.h":
             assert "getenv(" not in _read(os.path.join(CSRC, f)), f"{f} reads the environment; that is struct Switches' job"
 
 

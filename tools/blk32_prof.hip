@@ -2,6 +2,7 @@
 //   hipcc -O3 --offload-arch=gfx950 -I include -o tools/bin/blk32_prof tools/blk32_prof.hip
 //   tools/bin/blk32_prof [r] [kind: 0 rw, 1 cos-phase, 4 fourier] [terms] [recursive] [dual: 1 = the two inversions side by side (random walk)]
 #define PSMF_BLK_STAMPS 1
+#include "../rpsmf_amd/csrc/psmf_block.hip"     // blk_filter_lds_bytes
 #include "../rpsmf_amd/csrc/psmf_blk32.hip"
 #include <cstdio>
 #include <vector>

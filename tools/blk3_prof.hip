@@ -1,6 +1,6 @@
 // GPU-box diagnostic: per-phase cycles of the two-group block filter (stamps via PSMF_BLK_STAMPS).
 #define PSMF_BLK_STAMPS 1
-#include "../rpsmf_amd/csrc/psmf_blk3.hip"
+#include "../rpsmf_amd/csrc/psmf_blk34.hip"
 #include <cstdio>
 #include <vector>
 #include <cmath>

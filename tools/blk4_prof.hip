@@ -2,7 +2,7 @@
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -I include -o tools/bin/blk4_prof tools/blk4_prof.hip
 //   [NS=0|1] [TOL=x] [Q=q] tools/bin/blk4_prof [r]
 #define PSMF_BLK_STAMPS 1
-#include "../rpsmf_amd/csrc/psmf_blk3.hip"
+#include "../rpsmf_amd/csrc/psmf_blk34.hip"
 #include <cstdio>
 #include <vector>
 #include <cmath>

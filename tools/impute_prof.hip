@@ -1,8 +1,7 @@
 // GPU-box diagnostic: per-phase s_memtime cycles of one column of the masked batched engine (config D shape:
 // d = 19, r = 10, 40 % missing), averaged over the columns of a run; 50 replicas in one launch as in bench.py.
 #define PSMF_IMPUTE_STAMPS 1
-#define PSMF_IMPUTE_KERNEL_ONLY 1
-#include "../rpsmf_amd/csrc/psmf_impute.hip"
+#include "../rpsmf_amd/csrc/psmf_impute3.hip"
 #include <cstdio>
 #include <vector>
 using namespace psmf;

@@ -1,11 +1,11 @@
 """GPU-box probe: per-step Newton-Schulz residuals of the last block of a filter4 run.  Needs the debug library:
-   hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -shared -DF4_DEBUG -I include -o tools/bin/libpsmf_dbg.so rpsmf_amd/csrc/psmf_capi.hip -L/opt/rocm/lib -lrccl"""
+   PSMF_CXXFLAGS=-DF4_DEBUG python -m rpsmf_amd.build
+(and the same PSMF_CXXFLAGS when this probe runs: the flags are part of the build id the library is checked against)"""
 import sys, os, ctypes as C
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np
 from rpsmf_amd import _capi
-_capi.LIB_PATH = os.path.join(ROOT, "tools", "bin", "libpsmf_dbg.so")
 import bench
 d, T, r = 20000, 440, 20
 q = float(sys.argv[1]) if len(sys.argv) > 1 else 10.0

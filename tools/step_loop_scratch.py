@@ -1,8 +1,8 @@
 """No GPU needed: resource lines and scratch-instruction counts inside the step loops of the role-specialised block filters, from
-the device assembly of the C-ABI translation unit -- the recipe of profiles/chain_carry_kernel_metadata.txt as a tool.
+the device assembly of the filter3 family's translation unit -- the recipe of profiles/chain_carry_kernel_metadata.txt as a tool.
 
-    hipcc <FLAGS of rpsmf_amd/build.py> -I include --save-temps --cuda-device-only -c rpsmf_amd/csrc/psmf_capi.hip -o capi_dev.o
-    python tools/step_loop_scratch.py psmf_capi-hip-amdgcn-amd-amdhsa-gfx950.s [kernel ...]
+    hipcc <FLAGS of rpsmf_amd/build.py> -I include --save-temps --cuda-device-only -c rpsmf_amd/csrc/psmf_filter34.hip -o filter34_dev.o
+    python tools/step_loop_scratch.py psmf_filter34-hip-amdgcn-amd-amdhsa-gfx950.s [kernel ...]
 
 A step loop = a back-edge range (label ... branch back to it) that holds the 10 s_barrier of one step (up to 12 where a tail was
 duplicated) and does not lie inside another such range; ranges that overlap (a rotated loop) count once.  The chain loop = the

@@ -1,6 +1,5 @@
 // GPU-box check of wave_sweep16m (psmf_impute3.hip): sweep of a random SPD matrix augmented with a column, against the host inverse.
-#define PSMF_IMPUTE_KERNEL_ONLY 1
-#include "../rpsmf_amd/csrc/psmf_impute.hip"
+#include "../rpsmf_amd/csrc/psmf_impute3.hip"
 #include <cstdio>
 #include <vector>
 #include <cmath>
