@@ -265,6 +265,17 @@ int psmf_geometry(psmf_handle h, int32_t* out7);
  * The same function decides what is launched (select_filter_kernel, psmf_blocked.hip).
  * (New: diagnostics for tests and bench.py -- the reference has one code path, pypsmf/psmf/psmf.py:90-102.) */
 int psmf_filter_kernel(psmf_handle h);
+/* The persistent per-step kernel's launch geometry for this handle (read-only): out5[0] = 1 if the handle's next run goes through
+ * psmf_pstep_k (the same function decides that at launch), out5[1] = row workgroups (the grid has one more: the hub),
+ * out5[2] = rows per row workgroup, out5[3] = row passes NP of the kernel instance (4, 8, 12; 16 at 33 <= r <= 48),
+ * out5[4] = compute units of the device.  out5[1..3] are 0 where the planner found no geometry at psmf_create.
+ * The planner takes r <= 48 (masked handles r <= 32) and d_local rows in 2048 / RPAD-row passes, RPAD = 8, 16, 32, 64 the padded
+ * rank: at most n_cu - 1 row workgroups of 12 passes (16 at RPAD = 64), and no more of them than the hub's fan-in sums -- 17 per
+ * segment, min(24, 256 / ceil((r + 1) / 2)) segments (RPAD = 64: 20 per segment, at most 12 segments).  On 256 compute units:
+ * d_local <= 783 360 / 391 680 / 195 840 at RPAD = 8 / 16 / 32; 122 880 at 33 <= r <= 41, 112 640 at r <= 45, 102 400 at
+ * r <= 48.  Every d_local below the bound has a geometry (the smallest NP whose workgroups fit both counts).
+ * (New: diagnostics for tests -- the reference has one code path, pypsmf/psmf/psmf.py:90-102.) */
+int psmf_step_plan(psmf_handle h, int32_t* out5);
 /* diagnostics of the blocked engine's r x r inversions since the last reset: out[0] = timesteps inverted by
  * Newton-Schulz refinement, out[1] = by the direct symmetric sweep, out[2] = Newton-Schulz iterations in
  * total, out[3] = failed Newton-Schulz attempts, out[4] / out[5] = summed in-kernel durations / gaps between

@@ -77,6 +77,7 @@ SIGNATURES = {
     "psmf_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
     "psmf_comm_abort": (C.c_int, [C.c_void_p]),
     "psmf_filter_kernel": (C.c_int, [C.c_void_p]),
+    "psmf_step_plan": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "psmf_filter_kernel_time": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.c_int]),
     "psmf_measure_copy_bandwidth": (C.c_int, [C.c_int, C.c_size_t, C.c_int, _dp]),
     "psmf_impute_run": (C.c_int, [C.POINTER(PsmfImputeConfig), _dp, _u8p, _u8p, _dp, _dp, _dp, _dp, _dp,
@@ -363,6 +364,13 @@ class DeviceFilter:
                 5: "psmf_blk_filter4", 6: "psmf_blk_filter4s", 7: "psmf_blk_filter5", 8: "psmf_blk_filter6", 9: "psmf_blk_filter6d", 10: "psmf_blk_filter7", 11: "psmf_pstep_k"}.get(self._lib.psmf_filter_kernel(self._h), "?")
         return dict(n_sweep_wg=g[0], rows_per_wg=g[1], row_stride=g[2], lanes_per_row=g[3], graph_chunk=g[4],
                     engine={1: "step", 2: "block"}.get(g[5], g[5]), block_steps=g[6], filter_kernel=kern)
+
+    def step_plan(self):
+        """The persistent per-step kernel's launch geometry (psmf_step_plan): whether the next run goes through it, row
+        workgroups, rows per workgroup, row passes NP of the instance (zeros where the planner found none), compute units."""
+        p = (C.c_int32 * 5)()
+        self._check(self._lib.psmf_step_plan(self._h, p))
+        return dict(usable=bool(p[0]), n_row_wg=int(p[1]), rows_per_wg=int(p[2]), np=int(p[3]), n_cu=int(p[4]))
 
     def counters(self, reset=False):
         c = (C.c_int64 * 8)()

@@ -1116,6 +1116,17 @@ int psmf_geometry(psmf_handle h, int32_t* out7) {
   return PSMF_OK;
 }
 
+int psmf_step_plan(psmf_handle h, int32_t* out5) {
+  if (!h || !out5) return PSMF_ERR_ARG;
+  if (set_device(h) != PSMF_OK) return PSMF_ERR_HIP;
+  int n_cu = 0;
+  HIP_TRY(h, hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, h->cfg.device));
+  out5[0] = pstep_usable(h) ? 1 : 0;
+  out5[1] = h->ps_ok ? h->ps_plan.n_row_wg : 0; out5[2] = h->ps_ok ? h->ps_plan.rows_per_wg : 0; out5[3] = h->ps_ok ? h->ps_plan.np : 0;
+  out5[4] = n_cu;
+  return PSMF_OK;
+}
+
 #ifdef F4_DEBUG
 // debug builds only (tools/probe_f4d.py): the scratch area the filter4 kernel writes its per-step residuals to
 int psmf_debug_read(psmf_handle h, double* out, int n) {

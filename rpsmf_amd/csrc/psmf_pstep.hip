@@ -925,6 +925,7 @@ __device__ __forceinline__ void pstep_hub(const PstepParams& q, char* smem) {
         if (v_) {
           const double pv = p.coef_update ? pscale * (0.5 * (sPp[a_] + sPp[at_])) : sPb[a_];      // (sL is being rewritten: Pbar of the step from its own image)
           const double pb = p.pbar_predict ? s_f[i_] * pv * s_f[j] + qs * sQ[a_] : pv;
+          if (!p.coef_update) sPp[a_] = pv;      // P of the step is its Pbar, which the next line overwrites: kept for DevState in the P+ image (no solve, nobody reads it)
           sPb[a_] = pb;
           part += sV[a_] * s_mub[i_];
           gp += sG[a_] * pb;
@@ -1058,7 +1059,7 @@ __device__ __forceinline__ void pstep_hub(const PstepParams& q, char* smem) {
       if (v_) {
         const int idx = i_ * r + j;
         st->V[idx] = sV[a_];
-        if (n_done > 0) st->P[idx] = p.coef_update ? pscale_last * (0.5 * (sPp[a_] + sPp[at_])) : sPb[a_];
+        if (n_done > 0) st->P[idx] = p.coef_update ? pscale_last * (0.5 * (sPp[a_] + sPp[at_])) : sPp[a_];      // (sPb is Pbar of the NEXT step by now)
         st->G[idx] = sG[a_];
         st->Q[idx] = sQ[a_];
         st->Pbar[idx] = sPb[a_];
@@ -1168,17 +1169,22 @@ bool pstep_plan(int d_local, int r, int n_cu, bool storage_f64, bool masked, Pst
   if (nwg > n_cu - 1) nwg = n_cu - 1;
   int rows = (d_local + nwg - 1) / nwg;
   int np = (rows + rpw - 1) / rpw;
-  if (np > (rpad > 32 ? PSTEP_NPMAX_BIG : PSTEP_NPMAX)) return false;
+  const int np_max = rpad > 32 ? PSTEP_NPMAX_BIG : PSTEP_NPMAX;
+  if (np > np_max) return false;
   (void)storage_f64;
   np = pstep_np_variant(rpad, np);       // the kernel instance runs exactly this many passes: fewer, fuller workgroups
-  rows = np * rpw;
-  nwg = (d_local + rows - 1) / rows;
-  {      // the hub's fan-in: (threads of its four fan-in waves / pairs of columns, at most 24) segments x PSTEP_FANIN_ROWS rows each
-    const int npair = ((r + 1 + 1) & ~1) / 2;
-    int S = (4 * 64) / npair;
-    const int cap = rpad > 32 ? 12 : 24;      // 3 x the lanes per column of the second level (pstep_hub: LPC)
-    if (S > cap) S = cap;
-    if (nwg > S * (rpad > 32 ? PSTEP_FANIN_ROWS_BIG : PSTEP_FANIN_ROWS)) return false;
+  // the hub's fan-in: (threads of its four fan-in waves / pairs of columns, at most 24) segments x PSTEP_FANIN_ROWS rows each
+  const int npair = ((r + 1 + 1) & ~1) / 2;
+  int S = (4 * 64) / npair;
+  const int cap = rpad > 32 ? 12 : 24;      // 3 x the lanes per column of the second level (pstep_hub: LPC)
+  if (S > cap) S = cap;
+  const int fanin = S * (rpad > 32 ? PSTEP_FANIN_ROWS_BIG : PSTEP_FANIN_ROWS);
+  for (;;) {      // more workgroups than the fan-in takes: the next variant (fewer, fuller workgroups still), while there is one
+    rows = np * rpw;
+    nwg = (d_local + rows - 1) / rows;
+    if (nwg <= fanin) break;
+    if (np >= np_max) return false;
+    np = pstep_np_variant(rpad, np + 1);
   }
   out->n_row_wg = nwg;
   out->rows_per_wg = rows;

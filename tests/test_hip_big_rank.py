@@ -154,6 +154,9 @@ def test_persistent_kernel_at_33_to_48_matches_the_launched_form(name, r, opts, 
                 f.run(a, b)
             if persistent and d >= 100_000:
                 assert f.geometry().get("filter_kernel") == "psmf_pstep_k"
+                sp = f.step_plan()
+                if sp["n_cu"] == 256:          # sixteen row passes: 196 row workgroups of 512 rows
+                    assert sp["usable"] and (sp["np"], sp["n_row_wg"], sp["rows_per_wg"]) == (16, 196, 512), sp
             s = f.get_state()
             s["yp"] = f.y_pred(0, T)
             out[persistent] = s
