@@ -162,13 +162,47 @@ int psmf_set_noise_rotation(psmf_handle h, const double* U, const double* lam);
 
 /* ---- series ---------------------------------------------------------------------------- */
 /* Y: nt x d_local time-major block holding y_{t0+1} .. y_{t0+nt}; T_total sizes the device
- * buffers on first use.  replaces the dict y[k] of (d,1) arrays passed to step (psmf.py:85-88) */
+ * buffers on first use (a ring handle, psmf_series_ring below: one chunk per call, T_total ignored).  replaces the dict y[k] of (d,1) arrays passed to step (psmf.py:85-88) */
 int psmf_upload_series(psmf_handle h, const void* Y, int dtype, int64_t t0, int64_t nt,
                        int64_t T_total);
 
 /* masked = 1: M: nt x d_local uint8, time-major like Y, 1 = observed, for the steps t0+1 .. t0+nt (after psmf_upload_series, which
  * sizes the buffer).  Where M = 0 the value of Y is never read.  replaces Mk = diag(M[:, t]) of ExperimentImpute/PSMF.py:62. */
 int psmf_upload_mask(psmf_handle h, const uint8_t* M, int64_t t0, int64_t nt);
+
+/* ---- series ring: a stream longer than the device buffers (or of unknown length) --------
+ * psmf_series_ring makes the series buffers of the handle -- Y, y_hat, the posterior-mean history and, masked handles, the mask
+ * and the (s, eta) history -- a ring of n_slots windows of `chunk` rows instead of T_total resident rows.  Call it before the
+ * first psmf_upload_series (PSMF_ERR_STATE after one); chunk >= 1, n_slots >= 2.  Row t of the stream (0-based; step k = t + 1)
+ * belongs to chunk t / chunk, and a chunk lives in slot (t / chunk) % n_slots at row offset t % chunk: uploading chunk c evicts
+ * chunk c - n_slots.  On a ring handle
+ *   psmf_upload_series / psmf_upload_mask  take rows of ONE chunk per call (PSMF_ERR_ARG across a chunk boundary; the rows of a
+ *       chunk in order; the last chunk of a stream may be short; the mask after the series rows it belongs to); T_total is
+ *       ignored.  The copy runs on a copy stream of the handle behind the last run that touched the slot's previous occupant, and
+ *       does not synchronise the compute stream: a chunk is uploaded while another one runs.  The call returns when the caller's
+ *       array has been read.  An array whose dtype differs from the storage type is converted on the device (psmf_cast_rows),
+ *       in a staging buffer of one chunk of float64 that the first such upload or download allocates.
+ *   psmf_run  may span chunks; it is cut at the chunk boundaries, waits (on the device) for the uploads of the slots it reads, and
+ *       goes on across a boundary exactly as between two psmf_run calls on a resident handle cut at the same steps -- the same
+ *       bits.  A step that is not resident is PSMF_ERR_STATE, names the step, and nothing of the call is launched.
+ *       Masked handles form the Gram of the NEXT step beside each step: for the same bits across a boundary the first mask row of
+ *       the next chunk has to be uploaded before the run that ends the chunk is called (with n_slots >= 3 that still overlaps);
+ *       otherwise the run re-prepares at the boundary like a fresh psmf_run.
+ *   psmf_download_y_pred, psmf_download_mu, psmf_sq_error, psmf_masked_metrics, psmf_download_step_scalars  take ranges in chunks
+ *       that are still resident (PSMF_ERR_STATE: "step k is no longer resident"), wait for the runs of those slots only, and do
+ *       not report a numeric failure of the run: psmf_sync does.  Row k of the mean history is kept with the chunk of step k;
+ *       the row a chunk starts from is the last row of its predecessor's slot and is rewritten when that slot is run again.
+ *       psmf_masked_metrics alone also waits for the compute stream: its second sum reads C, which every queued run rewrites,
+ *       so "the present C" is the C behind every run queued before the call, as on a resident handle.
+ *   psmf_set_schedules, psmf_set_q_matrix_schedule (indexed by step, not windowed), psmf_set_noise_rotation (its rotation would
+ *       have to run on the copy stream), psmf_time_kernel and PSMF_DYN_HOST handles are refused by name, PSMF_ERR_STATE.
+ * psmf_predict, psmf_predict_sq_error, psmf_project, psmf_get_state do not read the series and are unchanged.  Without this call a
+ * handle behaves as before.  (New: the reference's step() consumes a dict of observations one by one, psmf.py:85-88, and holds
+ * nothing on a device.) */
+int psmf_series_ring(psmf_handle h, int64_t chunk, int n_slots);
+/* Read-only (tests): out[0] = chunk, out[1] = n_slots (both 0 without a ring), out[2 + i] = the chunk slot i holds or -1;
+ * out has room for 2 + n_slots values. */
+int psmf_series_ring_info(psmf_handle h, int64_t* out);
 
 /* ---- the hot loop ---------------------------------------------------------------------- */
 /* for k in k_begin+1 .. k_end: inner(k, y_k)  entirely on the device

@@ -62,6 +62,8 @@ SIGNATURES = {
     "psmf_project": (C.c_int, [C.c_void_p, _dp, C.c_int64, _dp]),
     "psmf_predict_sq_error": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, _dp, _dp]),
     "psmf_upload_series": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64]),
+    "psmf_series_ring": (C.c_int, [C.c_void_p, C.c_int64, C.c_int]),
+    "psmf_series_ring_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "psmf_run": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64]),
     "psmf_sync": (C.c_int, [C.c_void_p]),
     "psmf_download_y_pred": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64]),
@@ -140,6 +142,17 @@ def _f64(a, shape=None):
     return a
 
 
+def ring_place(t, chunk, n_slots):
+    """Where row t (0-based; step k = t + 1) of a stream lives in a series ring of n_slots windows of `chunk` rows
+    (psmf_series_ring): (chunk index, slot, row of the series buffers, series_t0 of the chunk) with row = t - series_t0."""
+    t, chunk, n_slots = int(t), int(chunk), int(n_slots)
+    if t < 0 or chunk < 1 or n_slots < 2:
+        raise ValueError("ring_place: need t >= 0, chunk >= 1, n_slots >= 2")
+    c = t // chunk
+    slot = c % n_slots
+    return c, slot, slot * chunk + t % chunk, (c - slot) * chunk
+
+
 class DeviceFilter:
     """One device-resident filter (or row shard).  Thin, argument-checking wrapper of the C ABI."""
 
@@ -180,6 +193,8 @@ class DeviceFilter:
             self._h = C.c_void_p()
             raise (ValueError if rc == ERR_ARG else PsmfError)(f"psmf_create failed ({rc}): {msg}")
         self.T = 0
+        self.masked = int(masked)
+        self.ring = None               # (chunk, n_slots) once series_ring() has been called
 
     # -- plumbing
     def _check(self, rc):
@@ -250,6 +265,80 @@ class DeviceFilter:
         T_total = t0 + nt if T_total is None else int(T_total)
         self._check(self._lib.psmf_upload_series(self._h, Y.ctypes.data_as(C.c_void_p), dt, t0, nt, T_total))
         self.T = max(self.T, T_total)
+
+    # -- series ring
+    def series_ring(self, chunk, n_slots=2):
+        """Keep n_slots windows of `chunk` rows of the series on the device instead of the whole of it (psmf_series_ring): before
+        the first upload.  Uploads then take rows of one chunk per call, runs may span chunks, downloads reach resident chunks."""
+        self._check(self._lib.psmf_series_ring(self._h, int(chunk), int(n_slots)))
+        self.ring = (int(chunk), int(n_slots))
+
+    def series_ring_info(self):
+        """dict(chunk, n_slots, slots = the chunk index every slot holds, -1 for none)"""
+        n = self.ring[1] if self.ring else 0
+        v = (C.c_int64 * (2 + n))()
+        self._check(self._lib.psmf_series_ring_info(self._h, v))
+        return dict(chunk=int(v[0]), n_slots=int(v[1]), slots=[int(v[2 + i]) for i in range(n)])
+
+    def run_stream(self, chunks, k0=0, y_pred_dtype=None):
+        """Filter a stream chunk by chunk through the series ring: `chunks` is an iterable of (nt, d_local) arrays -- masked
+        handles: of (Y, M) pairs -- of `chunk` rows each (the last one may be shorter), the first of them starting at row k0, a
+        multiple of `chunk`.  A generator: after each chunk's run it yields (k_begin, k_end, y_hat), y_hat the (nt, d_local)
+        predictions of the chunk (y_pred_dtype: float64 or float32; None = the handle's storage type, which moves no more bytes
+        than the device holds) or None (store_y_pred=False).  A chunk's run is queued as soon as the chunk is uploaded, so chunk
+        j + 1 is uploaded while chunk j runs from the first chunk on; never more than n_slots chunks are on the device.  (A masked
+        handle forms the Gram of the next step beside each step, so a chunk's run is queued once the next chunk is uploaded:
+        that overlaps from n_slots = 3 on.)  A numeric failure of the run is raised when the stream ends."""
+        if self.ring is None:
+            raise ValueError("run_stream: call series_ring(chunk, n_slots) first")
+        chunk, n_slots = self.ring
+        k0 = int(k0)
+        if k0 < 0 or k0 % chunk:
+            raise ValueError(f"run_stream: k0 must be a non-negative multiple of the chunk ({chunk} rows), got {k0}")
+        if y_pred_dtype is None:
+            y_pred_dtype = np.float32 if self.storage == F32 else np.float64
+        return self._run_stream(iter(chunks), k0, chunk, n_slots, y_pred_dtype)
+
+    def _run_stream(self, it, k0, chunk, n_slots, yp_dtype):
+        spans = []                      # (k_begin, k_end) of every chunk uploaded so far
+        launched = yielded = 0
+        exhausted = short = False
+        while True:
+            while not exhausted and len(spans) - yielded < n_slots:      # a slot is free once its occupant has been yielded
+                item = next(it, None)
+                if item is None:
+                    exhausted = True
+                    break
+                if short:
+                    raise ValueError(f"run_stream: only the last chunk of a stream may have fewer than {chunk} rows")
+                Y, M = item if self.masked else (item, None)
+                Y = np.asarray(Y)
+                if Y.ndim != 2 or not 1 <= Y.shape[0] <= chunk:
+                    raise ValueError(f"run_stream: a chunk is (1 .. {chunk}, {self.d_local}), got {Y.shape}")
+                kb = k0 + len(spans) * chunk
+                self.upload_series(Y, kb)
+                if self.masked:
+                    if np.shape(M) != Y.shape:
+                        raise ValueError(f"run_stream: mask {np.shape(M)} against series {Y.shape}")
+                    self.upload_mask(M, kb)
+                short = Y.shape[0] < chunk
+                spans.append((kb, kb + Y.shape[0]))
+                launched = self._queue_runs(spans, launched, False)
+            launched = self._queue_runs(spans, launched, exhausted)
+            if yielded == launched:
+                break
+            kb, ke = spans[yielded]
+            yp = self.y_pred(kb, ke - kb, dtype=yp_dtype) if self.store_y_pred else None
+            yielded += 1
+            yield kb, ke, yp
+        self.sync()
+
+    def _queue_runs(self, spans, launched, exhausted):
+        """queue the run of every uploaded chunk; a masked handle's once the chunk behind it is uploaded (or the stream has ended)"""
+        while launched < len(spans) and (not self.masked or launched + 1 < len(spans) or exhausted):
+            self.run(*spans[launched], sync=False)
+            launched += 1
+        return launched
 
     def upload_mask(self, M, t0=0):
         """Observation mask of the steps t0+1 .. t0+nt (masked handles): (nt, d_local), nonzero = observed."""

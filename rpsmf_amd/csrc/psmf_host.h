@@ -130,6 +130,22 @@ struct psmf_filter {
   hipEvent_t evF[4] = {}, evA[4] = {}, evX[4] = {}, evS = nullptr;
   size_t scratch_bytes = 0;
   int64_t T_cap = 0;
+  // series ring (psmf_series_ring): the series buffers hold ring_slots windows of ring_chunk rows; chunk c of the stream lives in slot
+  // c % ring_slots and is run with sp.series_t0 = (c - slot) * ring_chunk.  ring_slots = 0: the whole series is resident.
+  struct RingSlot {
+    int64_t chunk = -1;          // chunk of the stream the slot holds (-1: none)
+    int64_t rows = 0, mrows = 0; // series / mask rows of it uploaded so far
+    hipEvent_t up = nullptr;     // the last upload into the slot (copy stream)
+    hipEvent_t run = nullptr;    // the last run that touched the slot (compute stream)
+    bool up_set = false, run_set = false;
+  };
+  int64_t ring_chunk = 0;
+  int ring_slots = 0;
+  int64_t ring_cur = -1;           // the chunk sp.series_t0 (and the histories' slot base) point at
+  std::vector<RingSlot> ring;
+  hipStream_t cstream = nullptr;   // the ring's copy stream: uploads, downloads, row conversion
+  void* ring_stage = nullptr;      // device staging of one chunk in the caller's element type (psmf_cast_rows converts from / into it)
+  bool ring_mg_stale = false;      // masked: the Gram formed one step ahead read a mask row that was not resident yet
   StepParams sp;
   hipGraph_t graph = nullptr;
   hipGraphExec_t gexec = nullptr;

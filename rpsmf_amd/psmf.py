@@ -561,7 +561,15 @@ class PSMFIter:
             out[k] = self._q_matrix(Q.get(k, Q[k1]))
         return out
 
-    def _ensure_device(self):
+    def _ensure_device(self, ring=None):
+        """The device handle: resident series buffers (step) or a series ring of `ring` = (chunk, n_slots) (step_stream).  A
+        handle of the other kind is closed and replaced: a ring cannot be taken off a handle, nor put on after an upload."""
+        if self._dev is not None and self._dev.ring != ring:
+            self._C[0]                  # (fetches a device-resident C before its handle goes)
+            self._dev.close()
+            self._dev, self._series_key, self._sched_key = None, None, (None, None)
+            if hasattr(self, "_qmat_key"):
+                self._qmat_key = None
         if self._dev is None:
             self._dev = _capi.DeviceFilter(self._d, self._r, **self._device_kwargs())
             if self._dense_noise() is not None:
@@ -569,6 +577,8 @@ class PSMFIter:
                 self._dev.set_noise_rotation(U, lam)
             elif self._row_noise() is not None:
                 self._dev.set_row_noise(self._row_noise())
+            if ring is not None:
+                self._dev.series_ring(*ring)
         return self._dev
 
     def _fetch_device(self, name, epoch):
@@ -655,6 +665,56 @@ class PSMFIter:
         self._dev.run(0, T)
         self._after_device_epoch(self._pull_state(T), T)
         self._verify_recognised_nonlinearity(self._theta[i - 1], T)
+
+    def step_stream(self, chunks, chunk, n_slots=2, i=1, keep_y_pred=False):
+        """One pass over a stream that need not fit on the device, nor have a known length: `chunks` is an iterable of
+        (nt, d) time-major arrays of `chunk` observations each (the last may be shorter), y_1 first.  What step() does -- epoch
+        reset, state onto the device, the fused time loop, state back -- with the series going through a ring of n_slots chunks
+        (DeviceFilter.run_stream): chunk j + 1 is uploaded while chunk j is filtered.  The recursive classes keep their in-loop
+        optimiser (and take no epoch index).  `_y_pred` and the mean history are not kept beyond the last step unless
+        keep_y_pred=True collects the predictions on the host.  Returns T, the number of observations filtered."""
+        if self.backend != "hip":
+            raise NotImplementedError('step_stream: backend="numpy" steps through a dict of observations; use step()')
+        if self._host_stepped():
+            raise NotImplementedError("step_stream: host-stepped callables (a nonlinearity or learning-rate schedule evaluated on "
+                                      "the host, one device step at a time) are not streamed; use step()")
+        if self._dense_noise() is not None:
+            raise NotImplementedError("step_stream: a non-diagonal R keeps the series rotated on the device; use step()")
+        t_max = max([k for D in (self._R, self._Q) if isinstance(D, dict) for k in D] + [0])
+        _rho, _Q, rho_s, q_s = self._device_rho_q(t_max)
+        if rho_s is not None or q_s is not None or getattr(self, "_q_matrix_sched", False):
+            raise NotImplementedError("step_stream: R / Q schedules that vary with k are indexed by step and not windowed; use step()")
+        recursive = hasattr(type(self), "_step_hip_recursive")
+        self.step_reset()
+        dev = self._ensure_device(ring=(int(chunk), int(n_slots)))
+        self._series_key = None
+        if recursive:
+            self._theta, i = {0: self._theta[0]}, 1
+        theta0, mu0 = self._theta[i - 1], np.asarray(self._mu[0], dtype=float).reshape(-1, 1)
+        self._push_state(i, t_max)
+        dev.zero_gradsum()
+        if recursive and self.optim == "adam":
+            dev.set_adam(self.adam_m.reshape(-1), self.adam_v.reshape(-1))
+        kept, T = {}, 0
+        for kb, ke, yp in dev.run_stream(chunks):
+            T = ke
+            if keep_y_pred and yp is not None:
+                for k in range(kb, ke):
+                    kept[k + 1] = yp[k - kb].reshape(-1, 1)
+        s = self._pull_state(T)
+        self._mu = _StateDict({T: s["mu"].reshape(-1, 1)})
+        self._y_pred = kept
+        if recursive:
+            self._theta[T] = s["theta"].reshape(np.asarray(self.theta0).shape)
+        self._after_device_epoch(s, T)
+        fn = getattr(self._nl, "recognised_from", None)
+        if fn is not None and T >= 1:       # (the mean history is not kept: the recognised family is re-checked at step 1 only)
+            from .modes import nonlinearity_mismatch
+
+            if nonlinearity_mismatch(fn, self._nl, theta0, mu0, 1):
+                raise RuntimeError(f"the nonlinearity {getattr(fn, '__name__', fn)!r} was recognised as {type(self._nl).__name__} on probe "
+                                   "inputs but differs from it at step 1 of this stream.  Construct with recognise=False.")
+        return T
 
     def _q_for_step(self, k, Q_running):
         """Q entering P_bar of step k: PSMFIter reads Q[k] (psmf.py:115); rPSMFIter its running Q_{k-1} (rpsmf.py:123)."""
