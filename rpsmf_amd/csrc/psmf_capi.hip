@@ -4,7 +4,6 @@
 #include "psmf_host.h"
 #include "psmf_kernels.hip"
 #include "psmf_masked.hip"
-#include "psmf_ring.hip"       // psmf_cast_rows: row conversion of the series ring
 #include "psmf_rotate.hip"
 #include "psmf_wave16.hip"     // solve_block_wave: the per-step engine's solve block
 
@@ -16,7 +15,6 @@
 #include <limits>
 #include <mutex>
 #include <string>
-#include <type_traits>
 #include <vector>
 
 thread_local std::string g_create_error;
@@ -212,12 +210,6 @@ int enqueue_weighted_gram(psmf_filter* h) {
   return PSMF_OK;
 }
 
-void destroy_graph(psmf_filter* h) {
-  if (h->gexec) { hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }
-  if (h->graph) { hipGraphDestroy(h->graph); h->graph = nullptr; }
-  h->chunk = 0;
-}
-
 int build_graph(psmf_filter* h, int chunk) {
   destroy_graph(h);
   HIP_TRY(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
@@ -231,6 +223,35 @@ int build_graph(psmf_filter* h, int chunk) {
   HIP_TRY(h, hipGraphInstantiate(&h->gexec, h->graph, nullptr, nullptr, 0));
   h->chunk = chunk;
   return PSMF_OK;
+}
+
+// O[M x N] = A[M x K] B[K x N] on the handle's stream (psmf_rotate.hip); the caller synchronises
+template <typename TA, typename TB, typename TO>
+int rot_gemm(psmf_filter* h, const TA* A, long long a_i, long long a_k, const TB* B, long long b_k, long long b_j, TO* O, long long o_i,
+             long long M, long long N, long long K) {
+  if (M <= 0 || N <= 0 || K <= 0) return PSMF_OK;
+  if (!A || !B || !O || (M + psmf::ROT_T - 1) / psmf::ROT_T > 65535) return fail(h, PSMF_ERR_ARG, "rotation: bad operand");
+  dim3 grid((unsigned)((N + psmf::ROT_T - 1) / psmf::ROT_T), (unsigned)((M + psmf::ROT_T - 1) / psmf::ROT_T));
+  hipLaunchKernelGGL((psmf::psmf_rot_gemm<TA, TB, TO>), grid, dim3(256), 0, h->stream, A, a_i, a_k, B, b_k, b_j, O, o_i, (int)M, (int)N, (int)K);
+  HIP_TRY(h, hipGetLastError());
+  return PSMF_OK;
+}
+
+// the dictionary (d x rp, storage type): dst = U^T src (fwd) or U src (back)
+int rot_dict(psmf_filter* h, const void* src, void* dst, bool fwd) {
+  const long long d = h->cfg.d_local, rp = h->geo.rp, r = h->cfg.r;
+  const long long ai = fwd ? 1 : d, ak = fwd ? d : 1;
+  return by_storage(h, [&](auto t) { return rot_gemm(h, (const double*)h->rotU, ai, ak, (const decltype(t)*)src, rp, 1LL, (decltype(t)*)dst, rp, d, r, d); });
+}
+
+}  // namespace
+
+// what the series unit (psmf_series.hip) calls besides run_steps: the captured graph holds buffer addresses, the scratch and
+// rotation buffers belong to the handle, and the rotation kernel is launched here
+void destroy_graph(psmf_filter* h) {
+  if (h->gexec) { hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }
+  if (h->graph) { hipGraphDestroy(h->graph); h->graph = nullptr; }
+  h->chunk = 0;
 }
 
 int ensure_scratch(psmf_filter* h, size_t bytes) {
@@ -253,18 +274,6 @@ int ensure_rot_tmp(psmf_filter* h, size_t bytes) {
   return PSMF_OK;
 }
 
-// O[M x N] = A[M x K] B[K x N] on the handle's stream (psmf_rotate.hip); the caller synchronises
-template <typename TA, typename TB, typename TO>
-int rot_gemm(psmf_filter* h, const TA* A, long long a_i, long long a_k, const TB* B, long long b_k, long long b_j, TO* O, long long o_i,
-             long long M, long long N, long long K) {
-  if (M <= 0 || N <= 0 || K <= 0) return PSMF_OK;
-  if (!A || !B || !O || (M + psmf::ROT_T - 1) / psmf::ROT_T > 65535) return fail(h, PSMF_ERR_ARG, "rotation: bad operand");
-  dim3 grid((unsigned)((N + psmf::ROT_T - 1) / psmf::ROT_T), (unsigned)((M + psmf::ROT_T - 1) / psmf::ROT_T));
-  hipLaunchKernelGGL((psmf::psmf_rot_gemm<TA, TB, TO>), grid, dim3(256), 0, h->stream, A, a_i, a_k, B, b_k, b_j, O, o_i, (int)M, (int)N, (int)K);
-  HIP_TRY(h, hipGetLastError());
-  return PSMF_OK;
-}
-
 // rows of X (n x d, storage type, row stride d) times U (fwd: into rotated coordinates) or U^T (back), out of place: src -> dst
 int rot_rows(psmf_filter* h, const void* src, void* dst, long long n, bool fwd) {
   const long long d = h->cfg.d_local;
@@ -272,12 +281,7 @@ int rot_rows(psmf_filter* h, const void* src, void* dst, long long n, bool fwd) 
   return by_storage(h, [&](auto t) { return rot_gemm(h, (const decltype(t)*)src, d, 1LL, (const double*)h->rotU, bk, bj, (decltype(t)*)dst, d, n, d, d); });
 }
 
-// the dictionary (d x rp, storage type): dst = U^T src (fwd) or U src (back)
-int rot_dict(psmf_filter* h, const void* src, void* dst, bool fwd) {
-  const long long d = h->cfg.d_local, rp = h->geo.rp, r = h->cfg.r;
-  const long long ai = fwd ? 1 : d, ak = fwd ? d : 1;
-  return by_storage(h, [&](auto t) { return rot_gemm(h, (const double*)h->rotU, ai, ak, (const decltype(t)*)src, rp, 1LL, (decltype(t)*)dst, rp, d, r, d); });
-}
+namespace {
 
 void compute_geometry(const psmf_config& c, Geometry& g, const int sweep_nt = 512) {
   g.vec = c.storage == PSMF_F64 ? 2 : 4;
@@ -374,11 +378,6 @@ void update_ns_policy(psmf_filter* h) {
   const bool benign = h->q_iso && h->q_last > 0.0 && h->p_diag_max <= 1e3 * h->q_last;
   if (!h->sw.ns_far_set) { const double f = benign ? 0.9 : 0.3; h->sp.ns_far2 = f * f; }
   if (!h->sw.ns_skip_set) h->sp.ns_skip_n = benign ? 1 : 3;
-}
-
-int set_device(psmf_handle h) {
-  HIP_TRY(h, hipSetDevice(h->cfg.device));
-  return PSMF_OK;
 }
 
 template <typename T>
@@ -572,181 +571,6 @@ void fill_step_params(psmf_filter* h) {
   sp.lr = cfg->adam_lr; sp.lr_end = cfg->adam_lr_end; sp.lr_steps = cfg->adam_lr_steps;
   sp.b1 = cfg->adam_b1; sp.b2 = cfg->adam_b2;
 }
-
-// ---- series ring (psmf_series_ring) ------------------------------------------------------------------------------------------
-// Chunk c of the stream lives in slot c % ring_slots; step t (0-based) of it in row slot * ring_chunk + t % ring_chunk of the series
-// buffers, which is row t - series_t0 with series_t0 = (c - slot) * ring_chunk: what the kernels index by.
-int64_t ring_t0(const psmf_filter* h, int64_t c) { return (c - c % h->ring_slots) * h->ring_chunk; }
-
-// The histories a step writes one row AHEAD of the series row it reads -- the posterior mean of step k in row k, the persistent
-// kernel's (s, eta) of the next step -- get chunk + 1 rows per slot, so that a slot's last row is not the first row of its
-// neighbour (which may hold a chunk that has not been read back yet): the slot's base is moved by `slot` rows.
-void ring_point(const psmf_filter* h, StepParams& sp, int64_t c) {
-  const int64_t slot = c % h->ring_slots;
-  sp.series_t0 = ring_t0(h, c);
-  sp.mu_hist = h->mu_hist + (size_t)slot * h->cfg.r;
-  if (h->sc_hist) sp.sc_hist = h->sc_hist + 2 * (size_t)slot;
-}
-
-// is row `off` (0-based, within its chunk) of chunk c on the device?  mask: of the observation mask instead of the series
-bool ring_has(const psmf_filter* h, int64_t c, int64_t off, bool mask = false) {
-  const psmf_filter::RingSlot& s = h->ring[(size_t)(c % h->ring_slots)];
-  return s.chunk == c && off < (mask ? s.mrows : s.rows);
-}
-
-// the steps [t0, t0 + nt) cut at the chunk boundaries; every piece must be resident (PSMF_ERR_STATE names the first step that is not)
-struct RingPiece { int64_t c, t0, nt; int slot; };
-int ring_pieces(psmf_filter* h, const char* who, int64_t t0, int64_t nt, bool need_mask, std::vector<RingPiece>& out) {
-  out.clear();
-  for (int64_t t = t0; t < t0 + nt;) {
-    const int64_t c = t / h->ring_chunk, end = (c + 1) * h->ring_chunk < t0 + nt ? (c + 1) * h->ring_chunk : t0 + nt;
-    for (int pass = 0; pass < (need_mask ? 2 : 1); ++pass) {
-      const psmf_filter::RingSlot& s = h->ring[(size_t)(c % h->ring_slots)];
-      const int64_t have = s.chunk == c ? (pass ? s.mrows : s.rows) : 0;
-      if (have < end - c * h->ring_chunk) {
-        const int64_t miss = s.chunk == c && c * h->ring_chunk + have > t ? c * h->ring_chunk + have : t;
-        const bool evicted = s.chunk > c;
-        return fail(h, PSMF_ERR_STATE, std::string(who) + ": step " + std::to_string(miss + 1) + (evicted ? " is no longer resident" : " is not resident") +
-                                       (pass ? " (observation mask)" : "") + " in the series ring");
-      }
-    }
-    out.push_back({c, t, end - t, (int)(c % h->ring_slots)});
-    t = end;
-  }
-  return PSMF_OK;
-}
-
-// the copy stream behind the runs that touched the slots of these pieces (and behind nothing else)
-int ring_wait_runs(psmf_filter* h, const std::vector<RingPiece>& pcs) {
-  for (const RingPiece& pc : pcs) {
-    const psmf_filter::RingSlot& s = h->ring[(size_t)pc.slot];
-    if (s.run_set) HIP_TRY(h, hipStreamWaitEvent(h->cstream, s.run, 0));
-  }
-  return PSMF_OK;
-}
-
-// n elements src -> dst with a change of element type on the copy stream (head: psmf_cast_rows)
-template <typename TS, typename TD>
-void launch_cast(psmf_filter* h, const TS* src, TD* dst, size_t n, int head) {
-  size_t grid = (n / 4 + psmf::CAST_NT - 1) / psmf::CAST_NT;
-  if (grid < 1) grid = 1;
-  if (grid > 2048) grid = 2048;
-  hipLaunchKernelGGL((psmf::psmf_cast_rows<TS, TD>), dim3((unsigned)grid), dim3(psmf::CAST_NT), 0, h->cstream, src, dst, n, head);
-}
-
-// rows of the caller (host, element type dtype) -> dev (storage type), or back, through the staging buffer where the types differ;
-// asynchronous on the copy stream, the caller spins on it
-int ring_copy_rows(psmf_filter* h, void* host, int dtype, void* dev, size_t n, bool upload) {
-  const size_t es = h->elem(), hs = dtype == PSMF_F64 ? 8 : 4;
-  if (n == 0) return PSMF_OK;
-  if (hs == es) {
-    if (upload) HIP_TRY(h, hipMemcpyAsync(dev, host, n * es, hipMemcpyHostToDevice, h->cstream));
-    else HIP_TRY(h, hipMemcpyAsync(host, dev, n * es, hipMemcpyDeviceToHost, h->cstream));
-    return PSMF_OK;
-  }
-  if (!h->ring_stage)      // one chunk of float64, and room to shift it to the rows' alignment: only streams of the other type pay for it
-    HIP_TRY(h, hipMalloc(&h->ring_stage, (size_t)h->ring_chunk * h->cfg.d_local * 8 + 16));
-  const int head = psmf::cast_head(dev, es);
-  char* stage = (char*)h->ring_stage + (size_t)psmf::cast_shift(head, hs) * hs;
-  if (upload) {
-    HIP_TRY(h, hipMemcpyAsync(stage, host, n * hs, hipMemcpyHostToDevice, h->cstream));
-    if (es == 4) launch_cast(h, (const double*)stage, (float*)dev, n, head);
-    else launch_cast(h, (const float*)stage, (double*)dev, n, head);
-    HIP_TRY(h, hipGetLastError());
-  } else {
-    if (es == 4) launch_cast(h, (const float*)dev, (double*)stage, n, head);
-    else launch_cast(h, (const double*)dev, (float*)stage, n, head);
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(host, stage, n * hs, hipMemcpyDeviceToHost, h->cstream));
-  }
-  return PSMF_OK;
-}
-
-// psmf_upload_series / psmf_upload_mask on a ring handle: rows [t0, t0 + nt) of ONE chunk into its slot, on the copy stream, behind
-// the last run that touched the slot's previous occupant; the compute stream is not synchronised.  Returns when the caller's array
-// has been read.
-int ring_upload(psmf_filter* h, const char* who, const void* src, int dtype, bool mask, int64_t t0, int64_t nt) {
-  if (nt == 0) return PSMF_OK;
-  const int64_t c = t0 / h->ring_chunk, off = t0 - c * h->ring_chunk;
-  if ((t0 + nt - 1) / h->ring_chunk != c)
-    return fail(h, PSMF_ERR_ARG, std::string(who) + ": the rows cross a chunk boundary of the series ring (one chunk of " + std::to_string(h->ring_chunk) + " rows per call)");
-  const int slot = (int)(c % h->ring_slots);
-  psmf_filter::RingSlot& s = h->ring[(size_t)slot];
-  if (mask && (s.chunk != c || s.rows < off + nt)) return fail(h, PSMF_ERR_STATE, std::string(who) + ": upload the series rows of the chunk first");
-  const int64_t have = s.chunk == c ? (mask ? s.mrows : s.rows) : 0;
-  if (off > have) return fail(h, PSMF_ERR_ARG, std::string(who) + ": the rows of a chunk are uploaded in order (rows " + std::to_string(have) + " .. " + std::to_string(off) + " of the chunk are missing)");
-  if (s.run_set) HIP_TRY(h, hipStreamWaitEvent(h->cstream, s.run, 0));      // the previous occupant's last reader / writer
-  const size_t dl = h->cfg.d_local, row = (size_t)slot * h->ring_chunk + off;
-  int rc = PSMF_OK;
-  if (mask) {
-    HIP_TRY(h, hipMemcpyAsync(h->mask + row * dl, src, (size_t)nt * dl, hipMemcpyHostToDevice, h->cstream));
-    // the masked Gram is formed one step ahead: the last step of the last slot reads the row behind it, which is this one
-    if (row == 0) HIP_TRY(h, hipMemcpyAsync(h->mask + (size_t)h->ring_slots * h->ring_chunk * dl, src, dl, hipMemcpyHostToDevice, h->cstream));
-  } else {
-    rc = ring_copy_rows(h, const_cast<void*>(src), dtype, (char*)h->Y + row * dl * h->elem(), (size_t)nt * dl, true);
-    if (rc) return rc;
-  }
-  HIP_TRY(h, hipEventRecord(s.up, h->cstream));
-  s.up_set = true;
-  HIP_TRY(h, spin_stream(h->cstream));
-  if (s.chunk != c) { s.chunk = c; s.rows = 0; s.mrows = 0; }
-  if (mask) { if (off + nt > s.mrows) s.mrows = off + nt; h->have_mask = true; }
-  else if (off + nt > s.rows) s.rows = off + nt;
-  return PSMF_OK;
-}
-
-int run_steps(psmf_filter* h, int64_t k_begin, int64_t k_end);
-
-// psmf_run on a ring handle: cut at the chunk boundaries, every piece with the series_t0 of its slot.  Nothing is launched unless
-// every piece is resident.  Across a boundary the run simply goes on (k_done == k_begin: no prepare()); the posterior mean is copied
-// into the slot's start row as prepare() does, which is what makes the wrap from the last slot to slot 0 right.
-int ring_run(psmf_filter* h, int64_t k_begin, int64_t k_end) {
-  std::vector<RingPiece> pcs;
-  int rc = ring_pieces(h, "psmf_run", k_begin, k_end - k_begin, h->cfg.masked != 0, pcs);
-  if (rc) return rc;
-  const int r = h->cfg.r;
-  for (const RingPiece& pc : pcs) {
-    psmf_filter::RingSlot& s = h->ring[(size_t)pc.slot];
-    const int64_t t0 = ring_t0(h, pc.c), pe = pc.t0 + pc.nt;
-    if (pc.c != h->ring_cur) {
-      ring_point(h, h->sp, pc.c);
-      h->ring_cur = pc.c;
-      // The captured launches carry the parameter block: capture again.  A replay of the old graph may still be running (runs are
-      // queued without a sync), and an executable graph is not destroyed under a replay: wait for it first.  Only a launched
-      // handle with pieces of 256 steps and more has one, and the slot this piece reads was uploaded behind that replay anyway.
-      if (h->gexec) HIP_TRY(h, spin_stream(h->stream));
-      destroy_graph(h);
-    }
-    if (s.up_set) HIP_TRY(h, hipStreamWaitEvent(h->stream, s.up, 0));
-    bool ahead = true;         // masked: is the mask row of step pe + 1, whose Gram the piece's last step forms, where the kernel reads it?
-    if (h->cfg.masked) {
-      const int64_t cn = pe / h->ring_chunk;
-      ahead = ring_has(h, cn, pe - cn * h->ring_chunk, true);
-      const psmf_filter::RingSlot& sn = h->ring[(size_t)(cn % h->ring_slots)];
-      if (ahead && sn.up_set) HIP_TRY(h, hipStreamWaitEvent(h->stream, sn.up, 0));
-    }
-    if (h->ring_mg_stale && h->k_done == pc.t0) h->need_prep = true;      // that Gram was formed from a row not uploaded yet: start over here
-    if (!h->need_prep && h->k_done == pc.t0 && pc.t0 == pc.c * h->ring_chunk && h->mu_hist)
-      HIP_TRY(h, hipMemcpyAsync(h->sp.mu_hist + (size_t)(pc.t0 - t0) * r, h->st->mu, r * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    rc = run_steps(h, pc.t0, pe);
-    if (rc) return rc;
-    h->ring_mg_stale = !ahead;
-    HIP_TRY(h, hipEventRecord(s.run, h->stream));
-    s.run_set = true;
-  }
-  return PSMF_OK;
-}
-
-void ring_destroy(psmf_filter* h) {
-  if (h->cstream) hipStreamSynchronize(h->cstream);
-  for (auto& s : h->ring) { if (s.up) hipEventDestroy(s.up); if (s.run) hipEventDestroy(s.run); }
-  h->ring.clear();
-  if (h->ring_stage) hipFree(h->ring_stage);
-  if (h->cstream) hipStreamDestroy(h->cstream);
-  h->cstream = nullptr; h->ring_stage = nullptr;
-}
-
-const char* kRingRefused = " is not available on a handle with a series ring (psmf_series_ring)";
 
 }  // namespace
 
@@ -971,149 +795,6 @@ int psmf_get_state(psmf_handle h, double* C, double* V, double* P, double* Q, do
   return PSMF_OK;
 }
 
-int psmf_upload_series(psmf_handle h, const void* Y, int dtype, int64_t t0, int64_t nt, int64_t T_total) {
-  if (!h || !Y || nt < 0 || t0 < 0) return fail(h, PSMF_ERR_ARG, "psmf_upload_series: bad argument");
-  if (dtype != PSMF_F32 && dtype != PSMF_F64) return fail(h, PSMF_ERR_ARG, "psmf_upload_series: dtype");
-  int rc = set_device(h);
-  if (rc) return rc;
-  if (h->ring_slots) return ring_upload(h, "psmf_upload_series", Y, dtype, false, t0, nt);      // (T_total plays no part)
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  const size_t dl = h->cfg.d_local, es = h->elem();
-  if (T_total < t0 + nt) T_total = t0 + nt;
-  if (!h->Y || T_total > h->T_cap) {
-    if (h->Y && t0 != 0) return fail(h, PSMF_ERR_STATE, "psmf_upload_series: buffer would grow mid-series; pass T_total on the first block");
-    destroy_graph(h);   // graph nodes hold the old buffer addresses
-    if (h->Y) HIP_TRY(h, hipFree(h->Y));
-    if (h->YP) HIP_TRY(h, hipFree(h->YP));
-    if (h->mu_hist) HIP_TRY(h, hipFree(h->mu_hist));
-    h->Y = h->YP = nullptr;
-    h->mu_hist = nullptr;
-    if (h->cfg.masked) {
-      if (h->mask) HIP_TRY(h, hipFree(h->mask));
-      if (h->sc_hist) HIP_TRY(h, hipFree(h->sc_hist));
-      h->mask = nullptr; h->sc_hist = nullptr; h->have_mask = false;
-      HIP_TRY(h, hipMalloc((void**)&h->mask, (size_t)T_total * dl));
-      HIP_TRY(h, hipMalloc((void**)&h->sc_hist, (size_t)T_total * 2 * sizeof(double)));
-      HIP_TRY(h, hipMemset(h->sc_hist, 0, (size_t)T_total * 2 * sizeof(double)));
-      h->sp.mask = h->mask;
-      h->sp.mg = h->mg;
-      h->sp.mg_tr = h->mg + (h->cfg.r * h->cfg.r + 1) + 1;
-      h->sp.mg_ntr = (h->cfg.r * h->cfg.r + 1 + 63) / 64;
-      h->sp.sc_hist = h->sc_hist;
-      h->sp.mask_rows = (int)T_total;
-    }
-    HIP_TRY(h, hipMalloc(&h->Y, (size_t)T_total * dl * es));
-    if (h->cfg.store_y_pred) HIP_TRY(h, hipMalloc(&h->YP, (size_t)T_total * dl * es));
-    HIP_TRY(h, hipMalloc((void**)&h->mu_hist, (size_t)(T_total + 1) * h->cfg.r * sizeof(double)));
-    h->sp.mu_hist = h->mu_hist;
-    h->T_cap = T_total;
-    h->sp.Y = h->Y;
-    h->sp.YP = h->YP;
-    h->sp.store_yp = h->cfg.store_y_pred ? 1 : 0;
-    h->sp.series_t0 = 0;
-  }
-  char* dst = (char*)h->Y + (size_t)t0 * dl * es;
-  const size_t n = (size_t)nt * dl;
-  if ((dtype == PSMF_F64) == (h->cfg.storage == PSMF_F64)) {
-    HIP_TRY(h, hipMemcpy(dst, Y, n * es, hipMemcpyHostToDevice));
-  } else {
-    const size_t blk = (size_t)1 << 24;
-    rc = by_storage(h, [&](auto t) {      // t: the storage type; the caller's array is of the other one
-      using TD = decltype(t);
-      using TS = std::conditional_t<sizeof(TD) == 8, float, double>;
-      std::vector<TD> buf(n < blk ? n : blk);
-      const TS* src = (const TS*)Y;
-      for (size_t a = 0; a < n; a += blk) {
-        const size_t m = n - a < blk ? n - a : blk;
-        for (size_t i = 0; i < m; ++i) buf[i] = (TD)src[a + i];
-        HIP_TRY(h, hipMemcpy(dst + a * sizeof(TD), buf.data(), m * sizeof(TD), hipMemcpyHostToDevice));
-      }
-      return (int)PSMF_OK;
-    });
-    if (rc) return rc;
-  }
-  if (h->rotU && n) {                    // non-diagonal R: the handle keeps the rows y^T U
-    rc = ensure_rot_tmp(h, n * es);
-    if (rc) return rc;
-    HIP_TRY(h, hipMemcpyAsync(h->rot_tmp, dst, n * es, hipMemcpyDeviceToDevice, h->stream));
-    rc = rot_rows(h, h->rot_tmp, dst, nt, true);
-    if (rc) return rc;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-  }
-  return PSMF_OK;
-}
-
-// the buffers, the copy stream and the events of a ring; on an error the caller frees what exists
-static int ring_alloc(psmf_filter* h, int64_t chunk, int n_slots) {
-  const size_t dl = h->cfg.d_local, es = h->elem(), rows = (size_t)n_slots * chunk;
-  // What a step touches one row ahead of the series row it reads: the mask (read: the Gram of the next step) gets one row behind
-  // the last slot, a copy of slot 0's first; the mean and (s, eta) histories (written) get chunk + 1 rows per slot (ring_point).
-  if (h->cfg.masked) {
-    HIP_TRY(h, hipMalloc((void**)&h->mask, (rows + 1) * dl));
-    HIP_TRY(h, hipMemsetAsync(h->mask, 0, (rows + 1) * dl, h->stream));
-    HIP_TRY(h, hipMalloc((void**)&h->sc_hist, (rows + n_slots) * 2 * sizeof(double)));
-    HIP_TRY(h, hipMemsetAsync(h->sc_hist, 0, (rows + n_slots) * 2 * sizeof(double), h->stream));
-    h->sp.mask = h->mask;
-    h->sp.mg = h->mg;
-    h->sp.mg_tr = h->mg + (h->cfg.r * h->cfg.r + 1) + 1;
-    h->sp.mg_ntr = (h->cfg.r * h->cfg.r + 1 + 63) / 64;
-    h->sp.sc_hist = h->sc_hist;
-    h->sp.mask_rows = (int)(rows + 1);
-  }
-  HIP_TRY(h, hipMalloc(&h->Y, rows * dl * es));
-  HIP_TRY(h, hipMemsetAsync(h->Y, 0, rows * dl * es, h->stream));
-  if (h->cfg.store_y_pred) HIP_TRY(h, hipMalloc(&h->YP, rows * dl * es));
-  HIP_TRY(h, hipMalloc((void**)&h->mu_hist, (rows + n_slots) * h->cfg.r * sizeof(double)));
-  HIP_TRY(h, hipStreamCreateWithFlags(&h->cstream, hipStreamNonBlocking));
-  h->ring.assign((size_t)n_slots, psmf_filter::RingSlot());
-  for (auto& s : h->ring) {
-    HIP_TRY(h, hipEventCreateWithFlags(&s.up, hipEventDisableTiming));
-    HIP_TRY(h, hipEventCreateWithFlags(&s.run, hipEventDisableTiming));
-  }
-  HIP_TRY(h, hipStreamSynchronize(h->stream));      // the zero-fills
-  h->sp.mu_hist = h->mu_hist;
-  h->sp.Y = h->Y;
-  h->sp.YP = h->YP;
-  h->sp.store_yp = h->cfg.store_y_pred ? 1 : 0;
-  h->sp.series_t0 = 0;
-  return PSMF_OK;
-}
-
-int psmf_series_ring(psmf_handle h, int64_t chunk, int n_slots) {
-  if (!h || chunk < 1 || n_slots < 2 || chunk > (int64_t)1 << 30 || (int64_t)n_slots * chunk > (int64_t)1 << 30)
-    return fail(h, PSMF_ERR_ARG, "psmf_series_ring: need chunk >= 1, n_slots >= 2 and n_slots * chunk <= 2^30 rows");
-  if (h->Y) return fail(h, PSMF_ERR_STATE, "psmf_series_ring: call it before the first psmf_upload_series (the series buffers exist already)");
-  if (h->cfg.dyn_kind == PSMF_DYN_HOST) return fail(h, PSMF_ERR_STATE, std::string("host-stepped dynamics (PSMF_DYN_HOST, psmf_step_host)") + kRingRefused);
-  if (h->sched) return fail(h, PSMF_ERR_STATE, std::string("psmf_set_schedules") + kRingRefused + ": the schedules are not windowed");
-  if (h->qmat) return fail(h, PSMF_ERR_STATE, std::string("psmf_set_q_matrix_schedule") + kRingRefused + ": the schedule is not windowed");
-  if (h->rotU) return fail(h, PSMF_ERR_STATE, std::string("psmf_set_noise_rotation") + kRingRefused + ": the rotation of the rows would have to run on the copy stream");
-  int rc = set_device(h);
-  if (rc) return rc;
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  destroy_graph(h);
-  rc = ring_alloc(h, chunk, n_slots);
-  if (rc) {      // leave the handle as it was: without series buffers, so that the call can be made again
-    for (void** p : {(void**)&h->Y, (void**)&h->YP, (void**)&h->mask, (void**)&h->sc_hist, (void**)&h->mu_hist})
-      if (*p) { (void)hipFree(*p); *p = nullptr; }
-    h->sp.Y = h->sp.YP = nullptr; h->sp.mask = nullptr; h->sp.sc_hist = nullptr; h->sp.mu_hist = nullptr;
-    ring_destroy(h);
-    return rc;
-  }
-  h->T_cap = (int64_t)n_slots * chunk;
-  h->ring_chunk = chunk;
-  h->ring_slots = n_slots;
-  h->need_prep = true;
-  return PSMF_OK;
-}
-
-int psmf_series_ring_info(psmf_handle h, int64_t* out) {
-  if (!h || !out) return PSMF_ERR_ARG;
-  out[0] = h->ring_chunk;
-  out[1] = h->ring_slots;
-  for (int i = 0; i < h->ring_slots; ++i) out[2 + i] = h->ring[(size_t)i].chunk;
-  return PSMF_OK;
-}
-
 int psmf_run(psmf_handle h, int64_t k_begin, int64_t k_end) {
   if (!h) return PSMF_ERR_ARG;
   if (!h->have_state) return fail(h, PSMF_ERR_STATE, "psmf_run: set_state (C, V, P, mu) first");
@@ -1130,8 +811,6 @@ int psmf_run(psmf_handle h, int64_t k_begin, int64_t k_end) {
 }
 
 }  // extern "C"
-
-namespace {
 
 // the steps k_begin + 1 .. k_end of a checked psmf_run, all read at k - sp.series_t0 (a ring handle: one piece of it)
 int run_steps(psmf_filter* h, int64_t k_begin, int64_t k_end) {
@@ -1199,8 +878,6 @@ int run_steps(psmf_filter* h, int64_t k_begin, int64_t k_end) {
   }
   return PSMF_OK;
 }
-
-}  // namespace
 
 extern "C" {
 
@@ -1433,91 +1110,6 @@ int psmf_filter_kernel_time(psmf_handle h, int64_t* launches, double* total_ms, 
   return PSMF_OK;
 }
 
-int psmf_download_y_pred(psmf_handle h, void* out, int dtype, int64_t t0, int64_t nt) {
-  if (!h || !out) return PSMF_ERR_ARG;
-  if (!h->YP) return fail(h, PSMF_ERR_STATE, "psmf_download_y_pred: handle was created with store_y_pred = 0");
-  if (t0 < 0 || nt < 0 || (!h->ring_slots && t0 + nt > h->T_cap)) return fail(h, PSMF_ERR_ARG, "psmf_download_y_pred: range");
-  if (dtype != PSMF_F32 && dtype != PSMF_F64) return fail(h, PSMF_ERR_ARG, "psmf_download_y_pred: dtype");
-  if (h->ring_slots) {       // behind the runs of these chunks only; conversion, where the types differ, on the device
-    int rc = set_device(h);
-    if (rc) return rc;
-    std::vector<RingPiece> pcs;
-    rc = ring_pieces(h, "psmf_download_y_pred", t0, nt, false, pcs);
-    if (!rc) rc = ring_wait_runs(h, pcs);
-    for (size_t i = 0; i < pcs.size() && !rc; ++i) {
-      const size_t dl = h->cfg.d_local, row = (size_t)(pcs[i].t0 - ring_t0(h, pcs[i].c));
-      rc = ring_copy_rows(h, (char*)out + (size_t)(pcs[i].t0 - t0) * dl * (dtype == PSMF_F64 ? 8 : 4), dtype, (char*)h->YP + row * dl * h->elem(), (size_t)pcs[i].nt * dl, false);
-      if (!rc) HIP_TRY(h, spin_stream(h->cstream));      // (the staging buffer serves the next piece)
-    }
-    return rc;
-  }
-  int rc = psmf_sync(h);
-  if (rc) return rc;
-  const size_t dl = h->cfg.d_local, es = h->elem(), n = (size_t)nt * dl;
-  const char* src = (const char*)h->YP + (size_t)t0 * dl * es;
-  if (h->rotU && n) {                    // non-diagonal R: y_hat = U (U^T y_hat)
-    rc = ensure_rot_tmp(h, n * es);
-    if (rc) return rc;
-    rc = rot_rows(h, src, h->rot_tmp, nt, false);
-    if (rc) return rc;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    src = (const char*)h->rot_tmp;
-  }
-  if ((dtype == PSMF_F64) == (h->cfg.storage == PSMF_F64)) {
-    HIP_TRY(h, hipMemcpy(out, src, n * es, hipMemcpyDeviceToHost));
-  } else if (h->cfg.storage == PSMF_F32) {
-    std::vector<float> buf(n);
-    HIP_TRY(h, hipMemcpy(buf.data(), src, n * 4, hipMemcpyDeviceToHost));
-    double* o = (double*)out;
-    for (size_t i = 0; i < n; ++i) o[i] = (double)buf[i];
-  } else {
-    std::vector<double> buf(n);
-    HIP_TRY(h, hipMemcpy(buf.data(), src, n * 8, hipMemcpyDeviceToHost));
-    float* o = (float*)out;
-    for (size_t i = 0; i < n; ++i) o[i] = (float)buf[i];
-  }
-  return PSMF_OK;
-}
-
-int psmf_download_mu(psmf_handle h, double* out, int64_t k0, int64_t nk) {
-  if (!h || !out) return PSMF_ERR_ARG;
-  if (!h->mu_hist) return fail(h, PSMF_ERR_STATE, "psmf_download_mu: no series uploaded yet");
-  if (k0 < 0 || nk < 0 || (!h->ring_slots && k0 + nk > h->T_cap + 1)) return fail(h, PSMF_ERR_ARG, "psmf_download_mu: range");
-  if (h->ring_slots) {
-    // row k (the state after step k) is kept with the chunk of step k; the mean a chunk starts from is also the first row of
-    // the chunk's own slot, and is read from there where the predecessor has left the ring
-    int rc = set_device(h);
-    if (rc) return rc;
-    const int r = h->cfg.r;
-    std::vector<int64_t> rows((size_t)nk);
-    std::vector<char> wait((size_t)h->ring_slots, 0);
-    for (int64_t k = k0; k < k0 + nk; ++k) {
-      int64_t c = (k > 0 ? k - 1 : 0) / h->ring_chunk;
-      if (!ring_has(h, c, k > 0 ? k - 1 - c * h->ring_chunk : 0)) {
-        const int64_t c2 = k / h->ring_chunk;
-        if (k != c2 * h->ring_chunk || !ring_has(h, c2, 0)) return fail(h, PSMF_ERR_STATE, "psmf_download_mu: step " + std::to_string(k) + " is no longer resident in the series ring");
-        c = c2;
-      }
-      rows[(size_t)(k - k0)] = k - ring_t0(h, c) + c % h->ring_slots;      // (chunk + 1 rows per slot: ring_point)
-      wait[(size_t)(c % h->ring_slots)] = 1;
-    }
-    for (size_t i = 0; i < wait.size(); ++i)
-      if (wait[i] && h->ring[i].run_set) HIP_TRY(h, hipStreamWaitEvent(h->cstream, h->ring[i].run, 0));
-    for (int64_t a = 0; a < nk;) {        // contiguous rows in one copy
-      int64_t b = a + 1;
-      while (b < nk && rows[(size_t)b] == rows[(size_t)b - 1] + 1) ++b;
-      HIP_TRY(h, hipMemcpyAsync(out + (size_t)a * r, h->mu_hist + (size_t)rows[(size_t)a] * r, (size_t)(b - a) * r * sizeof(double), hipMemcpyDeviceToHost, h->cstream));
-      a = b;
-    }
-    HIP_TRY(h, spin_stream(h->cstream));
-    return PSMF_OK;
-  }
-  int rc = psmf_sync(h);
-  if (rc) return rc;
-  HIP_TRY(h, hipMemcpy(out, h->mu_hist + (size_t)k0 * h->cfg.r, (size_t)nk * h->cfg.r * sizeof(double), hipMemcpyDeviceToHost));
-  return PSMF_OK;
-}
-
 int psmf_predict(psmf_handle h, int64_t T, int64_t n_pred, double* out) {
   if (!h || !out || n_pred < 0) return PSMF_ERR_ARG;
   if (n_pred == 0) return PSMF_OK;
@@ -1580,72 +1172,13 @@ int psmf_predict_sq_error(psmf_handle h, int64_t T, int64_t n_pred, const double
   int rc = psmf_predict(h, T, n_pred, yp.data());      // leaves the roll-out in the scratch buffer: [mu_pred | y_hat]
   if (rc) return rc;
   const size_t off = (size_t)n_pred * h->cfg.r;
-  const int grid = 1024;
-  rc = ensure_scratch(h, (off + 2 * n + grid) * sizeof(double));      // (may move the buffer: upload the roll-out again)
+  rc = ensure_scratch(h, (off + 2 * n + kSqErrorParts) * sizeof(double));      // (may move the buffer: upload the roll-out again)
   if (rc) return rc;
   double* dyp = h->scratch + off;
   double* dyt = dyp + n;
-  double* part = dyt + n;
   HIP_TRY(h, hipMemcpy(dyp, yp.data(), n * sizeof(double), hipMemcpyHostToDevice));
   HIP_TRY(h, hipMemcpy(dyt, Y_true, n * sizeof(double), hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(psmf::psmf_sq_error_k<double>, dim3(grid), dim3(psmf::WG), 0, h->stream, (const double*)dyp, (const double*)dyt, n, part);
-  HIP_TRY(h, hipGetLastError());
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  std::vector<double> hp(grid);
-  HIP_TRY(h, hipMemcpy(hp.data(), part, grid * sizeof(double), hipMemcpyDeviceToHost));
-  double a = 0.0;
-  for (int i = 0; i < grid; ++i) a += hp[i];
-  *out = a;
-  return PSMF_OK;
-}
-
-int psmf_sq_error(psmf_handle h, int64_t t0, int64_t nt, double* out) {
-  if (!h || !out) return PSMF_ERR_ARG;
-  if (!h->YP || !h->Y) return fail(h, PSMF_ERR_STATE, "psmf_sq_error: needs store_y_pred and an uploaded series");
-  if (t0 < 0 || nt < 0 || (!h->ring_slots && t0 + nt > h->T_cap)) return fail(h, PSMF_ERR_ARG, "psmf_sq_error: range");
-  int rc = set_device(h);
-  if (rc) return rc;
-  const int grid = 1024;
-  if (h->ring_slots) {       // chunk by chunk on the copy stream, behind the runs of these chunks only
-    std::vector<RingPiece> pcs;
-    rc = ring_pieces(h, "psmf_sq_error", t0, nt, false, pcs);
-    if (!rc) rc = ring_wait_runs(h, pcs);
-    if (rc) return rc;
-    rc = ensure_scratch(h, grid * sizeof(double));      // (only reductions the host waits for use it: none is in flight)
-    if (rc) return rc;
-    double* part_d = h->scratch;
-    std::vector<double> part(grid);
-    double a = 0.0;
-    for (size_t i = 0; i < pcs.size() && !rc; ++i) {
-      const size_t dl = h->cfg.d_local, off = (size_t)(pcs[i].t0 - ring_t0(h, pcs[i].c)) * dl, n = (size_t)pcs[i].nt * dl;
-      by_storage(h, [&](auto t) {
-        hipLaunchKernelGGL(psmf::psmf_sq_error_k<decltype(t)>, dim3(grid), dim3(psmf::WG), 0, h->cstream,
-                           (const decltype(t)*)h->YP + off, (const decltype(t)*)h->Y + off, n, part_d);
-      });
-      hipError_t e = hipGetLastError();
-      if (e == hipSuccess) e = hipMemcpyAsync(part.data(), part_d, grid * sizeof(double), hipMemcpyDeviceToHost, h->cstream);
-      if (e == hipSuccess) e = spin_stream(h->cstream);
-      if (e != hipSuccess) rc = fail(h, PSMF_ERR_HIP, std::string("psmf_sq_error: ") + hipGetErrorString(e));
-      for (int q = 0; q < grid && !rc; ++q) a += part[q];
-    }
-    *out = a;
-    return rc;
-  }
-  rc = ensure_scratch(h, grid * sizeof(double));
-  if (rc) return rc;
-  const size_t dl = h->cfg.d_local, n = (size_t)nt * dl, off = (size_t)t0 * dl;
-  by_storage(h, [&](auto t) {
-    hipLaunchKernelGGL(psmf::psmf_sq_error_k<decltype(t)>, dim3(grid), dim3(psmf::WG), 0, h->stream,
-                       (const decltype(t)*)h->YP + off, (const decltype(t)*)h->Y + off, n, h->scratch);
-  });
-  HIP_TRY(h, hipGetLastError());
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  std::vector<double> part(grid);
-  HIP_TRY(h, hipMemcpy(part.data(), h->scratch, grid * sizeof(double), hipMemcpyDeviceToHost));
-  double a = 0.0;
-  for (int i = 0; i < grid; ++i) a += part[i];
-  *out = a;
-  return PSMF_OK;
+  return sq_error_sum(h, h->stream, PSMF_F64, dyp, dyt, n, dyt + n, out);
 }
 
 int psmf_comm_unique_id(void* id_out) {
@@ -1891,106 +1424,12 @@ int psmf_device_pci_bus_id(int device, char* buf, int len) {
 }
 
 /* ---- masked filter on the large-d handle (psmf_masked.hip) ------------------------------------------------------------- */
-int psmf_upload_mask(psmf_handle h, const uint8_t* M, int64_t t0, int64_t nt) {
-  if (!h || !M || t0 < 0 || nt < 0) return fail(h, PSMF_ERR_ARG, "psmf_upload_mask: bad argument");
-  if (!h->cfg.masked) return fail(h, PSMF_ERR_STATE, "psmf_upload_mask: the handle was created with masked = 0");
-  if (!h->mask || (!h->ring_slots && t0 + nt > h->T_cap)) return fail(h, PSMF_ERR_STATE, "psmf_upload_mask: upload the series first (it sizes the mask buffer)");
-  int rc = set_device(h);
-  if (rc) return rc;
-  if (h->ring_slots) return ring_upload(h, "psmf_upload_mask", M, 0, true, t0, nt);
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  HIP_TRY(h, hipMemcpy(h->mask + (size_t)t0 * h->cfg.d_local, M, (size_t)nt * h->cfg.d_local, hipMemcpyHostToDevice));
-  h->have_mask = true;
-  return PSMF_OK;
-}
-
 int psmf_set_step_size(psmf_handle h, double gam) {
   if (!h || !(gam >= 0.0)) return fail(h, PSMF_ERR_ARG, "psmf_set_step_size: bad argument");
   int rc = set_device(h);
   if (rc) return rc;
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   HIP_TRY(h, hipMemcpy(&h->st->sgd_gamma, &gam, sizeof(double), hipMemcpyHostToDevice));
-  return PSMF_OK;
-}
-
-// the sums of psmf_masked_metrics over the steps t0+1 .. t0+nt, read at t - sp.series_t0, on `stream`; waits for it
-static int masked_metrics_rows(psmf_filter* h, const StepParams& sp, hipStream_t stream, const uint8_t* Mmiss, int64_t t0, int64_t nt, double sig, double* out4) {
-  const size_t dl = h->cfg.d_local, nb = (size_t)nt * dl;
-  if (h->mmiss_cap < nb) {
-    if (h->mmiss) HIP_TRY(h, hipFree(h->mmiss));
-    h->mmiss = nullptr; h->mmiss_cap = 0;
-    HIP_TRY(h, hipMalloc((void**)&h->mmiss, nb));
-    h->mmiss_cap = nb;
-  }
-  HIP_TRY(h, hipMemcpy(h->mmiss, Mmiss, nb, hipMemcpyHostToDevice));
-  const int gx = (int)((dl + psmf::WG - 1) / psmf::WG);
-  int gy = (int)((2048 + gx - 1) / gx);                  // ~2 k workgroups in all
-  if (gy > nt) gy = (int)nt;
-  if (gy < 1) gy = 1;
-  const int chunk = (int)((nt + gy - 1) / gy);
-  gy = (int)((nt + chunk - 1) / chunk);
-  int rc = ensure_scratch(h, (size_t)gx * gy * 4 * sizeof(double));
-  if (rc) return rc;
-  const size_t lds = (size_t)32 * h->cfg.r * sizeof(double);
-  by_storage(h, [&](auto t) {
-    hipLaunchKernelGGL(psmf::psmf_masked_metrics_k<decltype(t)>, dim3(gx, gy), dim3(psmf::WG), lds, stream, sp, (const uint8_t*)h->mask,
-                       (const uint8_t*)h->mmiss, (const double*)sp.sc_hist, (long long)t0, (int)nt, chunk, sig, h->cfg.robust, h->scratch);
-  });
-  HIP_TRY(h, hipGetLastError());
-  std::vector<double> part((size_t)gx * gy * 4);
-  HIP_TRY(h, hipMemcpyAsync(part.data(), h->scratch, part.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-  HIP_TRY(h, spin_stream(stream));
-  for (int q = 0; q < 4; ++q) out4[q] = 0.0;
-  for (size_t b = 0; b < (size_t)gx * gy; ++b)
-    for (int q = 0; q < 4; ++q) out4[q] += part[b * 4 + q];       // fixed order
-  return PSMF_OK;
-}
-
-int psmf_masked_metrics(psmf_handle h, const uint8_t* Mmiss, int64_t t0, int64_t nt, double sig, double* out4) {
-  if (!h || !Mmiss || !out4 || t0 < 0 || nt < 1) return fail(h, PSMF_ERR_ARG, "psmf_masked_metrics: bad argument");
-  if (!h->cfg.masked || !h->have_mask || !h->YP || (!h->ring_slots && t0 + nt > h->T_cap)) return fail(h, PSMF_ERR_STATE, "psmf_masked_metrics: needs a masked handle that has run over these steps");
-  if (h->ring_slots) {       // chunk by chunk, each with its slot's series_t0
-    int rc = set_device(h);
-    if (rc) return rc;
-    std::vector<RingPiece> pcs;
-    rc = ring_pieces(h, "psmf_masked_metrics", t0, nt, true, pcs);
-    // The second sum reads the live C, which every queued run rewrites: unlike the downloads, this entry point waits for the
-    // compute stream -- C is the C behind every run queued before the call, as on a resident handle.
-    if (!rc) rc = psmf_sync(h);
-    if (!rc) rc = ring_wait_runs(h, pcs);
-    for (int q = 0; q < 4; ++q) out4[q] = 0.0;
-    for (size_t i = 0; i < pcs.size() && !rc; ++i) {
-      StepParams sp = h->sp;
-      ring_point(h, sp, pcs[i].c);
-      double o4[4];
-      rc = masked_metrics_rows(h, sp, h->cstream, Mmiss + (size_t)(pcs[i].t0 - t0) * h->cfg.d_local, pcs[i].t0, pcs[i].nt, sig, o4);
-      for (int q = 0; q < 4 && !rc; ++q) out4[q] += o4[q];
-    }
-    return rc;
-  }
-  int rc = psmf_sync(h);
-  if (rc) return rc;
-  return masked_metrics_rows(h, h->sp, h->stream, Mmiss, t0, nt, sig, out4);
-}
-
-int psmf_download_step_scalars(psmf_handle h, double* out, int64_t t0, int64_t nt) {
-  if (!h || !out || t0 < 0 || nt < 0) return fail(h, PSMF_ERR_ARG, "psmf_download_step_scalars: bad argument");
-  if (!h->cfg.masked || !h->sc_hist || (!h->ring_slots && t0 + nt > h->T_cap)) return fail(h, PSMF_ERR_STATE, "psmf_download_step_scalars: needs a masked handle with an uploaded series");
-  if (h->ring_slots) {
-    int rc = set_device(h);
-    if (rc) return rc;
-    std::vector<RingPiece> pcs;
-    rc = ring_pieces(h, "psmf_download_step_scalars", t0, nt, false, pcs);
-    if (!rc) rc = ring_wait_runs(h, pcs);
-    if (rc) return rc;
-    for (const RingPiece& pc : pcs)
-      HIP_TRY(h, hipMemcpyAsync(out + 2 * (size_t)(pc.t0 - t0), h->sc_hist + 2 * (size_t)(pc.t0 - ring_t0(h, pc.c) + pc.slot), (size_t)pc.nt * 2 * sizeof(double), hipMemcpyDeviceToHost, h->cstream));
-    HIP_TRY(h, spin_stream(h->cstream));
-    return PSMF_OK;
-  }
-  int rc = psmf_sync(h);
-  if (rc) return rc;
-  HIP_TRY(h, hipMemcpy(out, h->sc_hist + 2 * (size_t)t0, (size_t)nt * 2 * sizeof(double), hipMemcpyDeviceToHost));
   return PSMF_OK;
 }
 

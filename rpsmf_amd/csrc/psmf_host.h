@@ -1,5 +1,5 @@
-// Host side of libpsmf_hip.so, shared by its translation units (psmf_capi.hip, psmf_blocked.hip, psmf_filter34.hip, psmf_impute.hip):
-// the handle, the switch table, the error helpers and the few host functions that cross unit boundaries.  A kernel is launched --
+// Host side of libpsmf_hip.so, shared by its translation units (psmf_capi.hip, psmf_series.hip, psmf_blocked.hip, psmf_filter34.hip,
+// psmf_impute.hip): the handle, the switch table, the error helpers and the few host functions that cross unit boundaries.  A kernel is launched --
 // and its LDS opt-in is made -- only in the unit that defines it (the rule of psmf_pstep.h); across units only these functions are called.
 #pragma once
 #include "../../include/psmf_hip.h"
@@ -218,6 +218,11 @@ double host_now_ms() {
   return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
 }
 
+int set_device(psmf_handle h) {
+  HIP_TRY(h, hipSetDevice(h->cfg.device));
+  return PSMF_OK;
+}
+
 int opt_in_lds(psmf_filter* h, const void* fn, size_t bytes) {
   HIP_TRY(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
   return PSMF_OK;
@@ -231,10 +236,24 @@ int opt_in_lds(psmf_filter* h, const void* fn, size_t bytes) {
 enum FilterKernel { FK_STEP = 0, FK_GENERAL = 1, FK_FILTER2 = 2, FK_FILTER3 = 3, FK_FILTER3S = 4, FK_FILTER4 = 5, FK_FILTER4S = 6,
                     FK_FILTER5 = 7, FK_FILTER6 = 8, FK_FILTER6D = 9, FK_FILTER7 = 10, FK_PSTEP = 11 };
 
+// what the entry points that a ring handle refuses say (psmf_capi.hip) and psmf_series_ring says of what it refuses (psmf_series.hip)
+inline constexpr char kRingRefused[] = " is not available on a handle with a series ring (psmf_series_ring)";
+
+constexpr int kSqErrorParts = 1024;      // workgroups of psmf_sq_error_k = partial sums that sq_error_sum reads back
+
 // ---- host functions that cross unit boundaries ----
 // psmf_capi.hip
 int all_reduce_sum(psmf_filter* h, double* buf, size_t count, hipStream_t s);
 bool pstep_usable(const psmf_filter* h);
+int run_steps(psmf_filter* h, int64_t k_begin, int64_t k_end);      // the steps of a checked psmf_run, read at k - sp.series_t0
+void destroy_graph(psmf_filter* h);
+int ensure_scratch(psmf_filter* h, size_t bytes);
+int ensure_rot_tmp(psmf_filter* h, size_t bytes);
+int rot_rows(psmf_filter* h, const void* src, void* dst, long long n, bool fwd);
+// psmf_series.hip: the series buffers (resident or a ring), their uploads, downloads and reductions
+int ring_run(psmf_filter* h, int64_t k_begin, int64_t k_end);      // psmf_run on a ring handle
+void ring_destroy(psmf_filter* h);
+int sq_error_sum(psmf_filter* h, hipStream_t stream, int storage, const void* yp, const void* y, size_t n, double* part_d, double* acc);
 int impute_run_large(const psmf_impute_config* cfg, const double* YorgInt, const uint8_t* M, const uint8_t* Mmiss, double* C, double* X,
                      const double* V, const double* P, const double* Q, double rho, double* Epred, double* Efull, double* inside,
                      double* Yrec, double* YrecL, double* YrecH, int32_t* status, float* elapsed_ms);

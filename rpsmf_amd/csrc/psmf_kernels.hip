@@ -904,20 +904,4 @@ __global__ __launch_bounds__(WG) void psmf_copy_k(const float4* __restrict__ src
   for (; i < n16; i += stride) dst[i] = src[i];
 }
 
-// sum of squared prediction errors over a block of steps (tracking.py:63-76 norms)
-template <typename T>
-__global__ __launch_bounds__(WG) void psmf_sq_error_k(const T* __restrict__ YP, const T* __restrict__ Y, size_t n,
-                                                      double* __restrict__ part) {
-  __shared__ double s4[4];
-  double a = 0.0;
-  for (size_t i = (size_t)blockIdx.x * WG + threadIdx.x; i < n; i += (size_t)gridDim.x * WG) {
-    const double dlt = (double)YP[i] - (double)Y[i];
-    a += dlt * dlt;
-  }
-  a = wave_sum(a);
-  if ((threadIdx.x & 63) == 0) s4[threadIdx.x >> 6] = a;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = (s4[0] + s4[1]) + (s4[2] + s4[3]);
-}
-
 }  // namespace psmf

@@ -16,7 +16,7 @@
 // (masked_prep_block, psmf_kernels.hip; block 0 publishes them and the step's (s, eta) for the bands) -- (-> all-reduce of r + 1
 // doubles) -> psmf_serial_mgram: the serial stage of the step in block 0 and, beside it, the masked Gram of the NEXT step in the other
 // blocks -> psmf_mgram_reduce (-> all-reduce of r^2 + 1 doubles).  The metrics of a pass (RMSE of the predictions and of C X over the held-out entries, coverage of the bands:
-// ExperimentImpute/common.py:79-94) are reduced on the device by psmf_masked_metrics_k; nothing d x n travels.
+// ExperimentImpute/common.py:79-94) are reduced on the device by psmf_masked_metrics_k (psmf_series_kernels.hip); nothing d x n travels.
 #pragma once
 #include "psmf_kernels.hip"
 #include "psmf_wave.h"        // f64x4, readlane_f64
@@ -226,59 +226,6 @@ __global__ __launch_bounds__(64) void psmf_mgram_trace(const double* __restrict_
   if (e < r * r) { const int i = e / r, j = e - i * r; tp = mg[e] * (0.5 * (Pbar[e] + Pbar[j * r + i])); }
   tp = wave_sum(tp);
   if (threadIdx.x == 0) tpart[blockIdx.x] = tp;
-}
-
-// Metrics of a pass over the held-out entries (Mmiss = 1) of this handle's rows, steps t0 .. t0 + nt:
-//   part[blk][0] = sum (y_hat - y)^2        (Epred^2 * count, PSMF.py:88)       y_hat = the stored (unmasked) predictions
-//   part[blk][1] = sum (c_i . x_t - y)^2    (Efull^2 * count, PSMF.py:86-89)    final C of the pass, x_t = mu_hist[t + 1]
-//   part[blk][2] = number of entries strictly inside their band (common.py:87-94)
-//   part[blk][3] = number of held-out entries
-// grid = (row blocks, time chunks); a thread owns one row (its C row in registers) and walks its chunk of steps.
-template <typename T>
-__global__ __launch_bounds__(WG) void psmf_masked_metrics_k(StepParams p, const uint8_t* __restrict__ mask, const uint8_t* __restrict__ mmiss,
-                                                            const double* __restrict__ sc_hist, long long t0, int nt, int chunk, double sig,
-                                                            int robust, double* __restrict__ part) {
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  double* s_x = reinterpret_cast<double*>(smem_raw);          // TC x r rows of the mean history
-  __shared__ double s_red[4][4];
-  const int tid = threadIdx.x, r = p.r, rp = p.rp, d_local = p.d_local;
-  const int row = blockIdx.x * WG + tid;
-  const bool on = row < d_local;
-  const T* __restrict__ C = reinterpret_cast<const T*>(p.C);
-  const T* __restrict__ Y = reinterpret_cast<const T*>(p.Y);
-  const T* __restrict__ YP = reinterpret_cast<const T*>(p.YP);
-  double c[RM];
-  for (int l = 0; l < r; ++l) c[l] = on ? (double)C[(size_t)row * rp + l] : 0.0;
-  double a_pred = 0.0, a_full = 0.0, a_in = 0.0, a_cnt = 0.0;
-  const int tb = blockIdx.y * chunk, te = min(tb + chunk, nt);
-  constexpr int TC = 32;
-  for (int q0 = tb; q0 < te; q0 += TC) {
-    const int nq = min(TC, te - q0);
-    __syncthreads();
-    for (int idx = tid; idx < nq * r; idx += WG) s_x[idx] = p.mu_hist[(size_t)(t0 + q0 + 1 - p.series_t0) * r + idx];   // row t + 1 = x_t
-    __syncthreads();
-    if (on) {
-      for (int q = 0; q < nq; ++q) {
-        const size_t t = (size_t)(t0 + q0 + q - p.series_t0);
-        const size_t at = t * d_local + row;
-        if (mmiss[(size_t)(q0 + q) * d_local + row]) {
-          const double y = (double)Y[at], yh = (double)YP[at];
-          double dot = 0.0;
-          for (int l = 0; l < r; ++l) dot += c[l] * s_x[q * r + l];
-          const double s = sc_hist[2 * t], eta = sc_hist[2 * t + 1];
-          const double band = sig * sqrt(robust ? (mask[at] ? s : 0.0) + eta : s + eta);
-          a_pred += (yh - y) * (yh - y);
-          a_full += (dot - y) * (dot - y);
-          a_in += (y < yh + band && yh - band < y) ? 1.0 : 0.0;
-          a_cnt += 1.0;
-        }
-      }
-    }
-  }
-  a_pred = wave_sum(a_pred); a_full = wave_sum(a_full); a_in = wave_sum(a_in); a_cnt = wave_sum(a_cnt);
-  if ((tid & 63) == 0) { s_red[tid >> 6][0] = a_pred; s_red[tid >> 6][1] = a_full; s_red[tid >> 6][2] = a_in; s_red[tid >> 6][3] = a_cnt; }
-  __syncthreads();
-  if (tid < 4) part[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 4 + tid] = (s_red[0][tid] + s_red[1][tid]) + (s_red[2][tid] + s_red[3][tid]);
 }
 
 }  // namespace psmf
