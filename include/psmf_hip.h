@@ -167,7 +167,11 @@ int psmf_upload_series(psmf_handle h, const void* Y, int dtype, int64_t t0, int6
                        int64_t T_total);
 
 /* masked = 1: M: nt x d_local uint8, time-major like Y, 1 = observed, for the steps t0+1 .. t0+nt (after psmf_upload_series, which
- * sizes the buffer).  Where M = 0 the value of Y is never read.  replaces Mk = diag(M[:, t]) of ExperimentImpute/PSMF.py:62. */
+ * sizes the buffer).  Where M = 0 the value of Y is never read.  replaces Mk = diag(M[:, t]) of ExperimentImpute/PSMF.py:62.
+ * A resident (non-ring) handle takes the mask in order: the rows may arrive in pieces, each piece starting at or before the end
+ * of what has been uploaded so far (rows behind a gap do not count), and psmf_run refuses with PSMF_ERR_ARG a step range that ends
+ * beyond the rows uploaded so (the buffer is not cleared when it is allocated).  The masked Gram is formed one step ahead; rows
+ * uploaded after a run that stopped in front of them are taken up by the next run, which then prepares again. */
 int psmf_upload_mask(psmf_handle h, const uint8_t* M, int64_t t0, int64_t nt);
 
 /* ---- series ring: a stream longer than the device buffers (or of unknown length) --------

@@ -805,6 +805,9 @@ int psmf_run(psmf_handle h, int64_t k_begin, int64_t k_end) {
   if (h->qmat && k_end >= h->qmat_n) return fail(h, PSMF_ERR_ARG, "psmf_run: step range beyond the Q_k matrix schedule");
   if (h->cfg.nonuniform_R && !h->sp.rho_rows) return fail(h, PSMF_ERR_STATE, "psmf_run: psmf_set_row_noise first (nonuniform_R = 1)");
   if (h->cfg.masked && !h->have_mask) return fail(h, PSMF_ERR_STATE, "psmf_run: psmf_upload_mask first (masked = 1)");
+  // the mask buffer is not cleared when it is allocated: a step beyond the uploaded rows would filter with whatever the memory held
+  if (h->cfg.masked && !h->ring_slots && k_end > h->mask_hi)
+    return fail(h, PSMF_ERR_ARG, "psmf_run: step range beyond the uploaded mask (psmf_upload_mask covers the steps 1 .. " + std::to_string((long long)h->mask_hi) + ")");
   int rc = set_device(h);
   if (rc) return rc;
   return h->ring_slots ? ring_run(h, k_begin, k_end) : run_steps(h, k_begin, k_end);

@@ -96,6 +96,7 @@ struct psmf_filter {
   double* mg = nullptr;        // r*r + 1: masked Gram and observed count of the current step, summed over workgroups (and ranks)
   double* sc_hist = nullptr;   // T_cap x 2: (s_k, eta_k) of every step -- the bands are formed from them
   bool have_mask = false;
+  int64_t mask_hi = 0;         // resident series: the mask has been uploaded for the series rows [0, mask_hi)
   double* sched = nullptr;     // rho_k | q_k schedules, sched_n doubles each (psmf_set_schedules)
   int64_t sched_n = 0;
   double* qmat = nullptr;      // Q_k matrices, (qmat_n + 1) x r x r (psmf_set_q_matrix_schedule)

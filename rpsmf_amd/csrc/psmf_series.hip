@@ -183,6 +183,7 @@ void series_free(psmf_filter* h) {
     if (*p) { (void)hipFree(*p); *p = nullptr; }
   h->sp.Y = h->sp.YP = nullptr; h->sp.mask = nullptr; h->sp.sc_hist = nullptr; h->sp.mu_hist = nullptr;
   h->have_mask = false;
+  h->mask_hi = 0;
 }
 
 // Y, YP, the mask, sc_hist and mu_hist for `rows` series rows, and the StepParams fields that point at them.  What a step touches
@@ -314,6 +315,12 @@ int series_upload(psmf_filter* h, const char* who, const void* src, int dtype, b
     HIP_TRY(h, hipStreamSynchronize(h->stream));
   }
   if (mask) h->have_mask = true;
+  if (mask && !h->ring_slots) {
+    if (t0 <= h->mask_hi && t0 + nt > h->mask_hi) h->mask_hi = t0 + nt;      // (rows behind a gap do not count)
+    // the masked Gram is formed one step ahead: the run that ended at k_done has formed the Gram of step k_done + 1 from mask row
+    // k_done.  When that row arrives (or changes) now, the next run must prepare again and form it from what was uploaded.
+    if (nt > 0 && t0 <= h->k_done && h->k_done < t0 + nt) h->need_prep = true;
+  }
   return PSMF_OK;
 }
 
