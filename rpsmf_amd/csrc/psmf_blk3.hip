@@ -377,19 +377,41 @@ struct F3Ctl {
 };
 
 // residual norms of the iteration whose columns sit in dump parity `par` -> done / failed (uniform over the workgroup)
-#define F3_DECIDE()                                                                                        \
+// The decision reads seven words of L.nrm.  Read where each is compared they made a chain of dependent LDS round trips (the four
+// norms | wait | the tolerance | wait | compare, and again for the far bound and the quarter tolerance on the other exits); here
+// they come in as ONE group of reads -- f3_norms_read, issued with whatever else the phase reads from LDS -- and F3_DECIDE_FROM
+// compares registers: same values, same comparisons.
+struct F3Nrm {
+  f64x2 nx, ny, tf;       // norms of the X pair | of the Y pair | ns_tol2, ns_far2
+  double tq;              // ns_tol2 / 4
+};
+__device__ __forceinline__ F3Nrm f3_norms_read(const double* nrm, const int par) {
+  const f64x2* n2 = reinterpret_cast<const f64x2*>(nrm);      // (16-byte aligned: blk_filter3_body's carve)
+  F3Nrm nd;
+  nd.nx = n2[par * 2];
+  nd.ny = n2[par * 2 + 1];
+  nd.tf = n2[4];
+  nd.tq = nrm[10];
+  return nd;
+}
+#define F3_DECIDE_FROM(nd_)                                                                                \
   do {                                                                                                     \
-    const double nx_ = L.nrm[par * 4 + 0] + L.nrm[par * 4 + 1];                                            \
-    const double ny_ = L.nrm[par * 4 + 2] + L.nrm[par * 4 + 3];                                            \
+    const double nx_ = (nd_).nx[0] + (nd_).nx[1];                                                          \
+    const double ny_ = (nd_).ny[0] + (nd_).ny[1];                                                          \
     const double worst_ = fmax(nx_, ny_);                                                                  \
     ++ctl.c_it;                                                                                            \
     /* the thresholds are read from LDS beside the norms (L.nrm[8..10]): as kernel arguments they were kept in VGPRs,   */ \
     /* spilled, and reloaded from scratch in front of every one of these comparisons (scratch_load; s_waitcnt vmcnt(0)) */ \
-    if (worst_ < L.nrm[8]) done = true;           /* ||R|| below the tolerance BEFORE the update just made */ \
-    else if (!(worst_ < L.nrm[9]) || it == F3_MAXIT - 1) failed = true;   /* start too far or not converging */   \
+    if (worst_ < (nd_).tf[0]) done = true;        /* ||R|| below the tolerance BEFORE the update just made */ \
+    else if (!(worst_ < (nd_).tf[1]) || it == F3_MAXIT - 1) failed = true;   /* start too far or not converging */ \
     /* ||R_next||_F <= (||R||_F + ||M (Xc - Xa)||) ||R||_F: one more iteration is the last, no check needed */   \
-    else last = worst_ * worst_ < L.nrm[10];                                                               \
+    else last = worst_ * worst_ < (nd_).tq;                                                                \
     if (F3_KNOCK & 1) { done = false; failed = false; last = true; }      /* always exactly two iterations */ \
+  } while (0)
+#define F3_DECIDE()                                                                                        \
+  do {                                                                                                     \
+    const F3Nrm nd_d_ = f3_norms_read(L.nrm, par);                                                         \
+    F3_DECIDE_FROM(nd_d_);                                                                                 \
   } while (0)
 
 // The direct symmetric sweep of both matrices on all 8 waves (half X: image X, half Y: image Y), in place in
@@ -574,8 +596,27 @@ __device__ __forceinline__ void f3_ns_program(const BlockParams& b, const F3Blk&
     double Mf[16], Xn[8];
     double hrow[8], wrow[8], h_j = 0.0, mub_j = 0.0, kap_k = 0.0;     // operands of phase F, loaded in phase 2
     int par = 0;
+    // One group of LDS reads behind B1: the three scalars and the operands of the start predictor (read whether or not it
+    // runs: the addresses are always valid).  M is built under the latency of the predictor's operands; read inside the
+    // predictor's branch they waited for kappa's round trip first and M for theirs.
+    const double kap_in = L.sc[F3_KAPPA], iom_in = L.sc[F3_IOM], iq_in = L.sc[F3_IQ];
+    f64x2 ab = {0.0, 0.0}, al64[4], be64[4];
+    f32x4s al32[2], be32[2];
+    f32x2s abp0, abp1;
+    if (F3_PREDICT) {
+      ab = *reinterpret_cast<const f64x2*>(L.sab + 2 * (32 * inv + 16 * C + lcol));
+      const float* f32b = L.s32 + 128 * inv;
+      al32[0] = *reinterpret_cast<const f32x4s*>(f32b + 8 * lrow); al32[1] = *reinterpret_cast<const f32x4s*>(f32b + 8 * lrow + 4);
+      be32[0] = *reinterpret_cast<const f32x4s*>(f32b + 32 + 8 * lrow); be32[1] = *reinterpret_cast<const f32x4s*>(f32b + 32 + 8 * lrow + 4);
+      abp0 = *reinterpret_cast<const f32x2s*>(f32b + 64 + 2 * pcol); abp1 = *reinterpret_cast<const f32x2s*>(f32b + 64 + 2 * (16 + pcol));
+      const f64x2* alp = reinterpret_cast<const f64x2*>(L.sal + 32 * inv + 8 * lrow);
+      const f64x2* bep = reinterpret_cast<const f64x2*>(L.sbe + 32 * inv + 8 * lrow);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { al64[e] = alp[e]; be64[e] = bep[e]; }
+      __builtin_amdgcn_sched_barrier(0);      // (the scheduler otherwise moves the reads behind the M build, to where they are waited for)
+    }
     {
-      const double kap = L.sc[F3_KAPPA], iom = L.sc[F3_IOM], iq = L.sc[F3_IQ];
+      const double kap = kap_in, iom = iom_in, iq = iq_in;
       kap_k = kap;
       const double ib = isY ? 1.0 / p.beta : 1.0, dq = isY ? iq : 0.0;
       // M = Lbar + kappa G with Lbar = (I / qw - W / qw^2) / omega, qw = the q that W was formed with; Y: M / beta + I / q
@@ -594,6 +635,14 @@ __device__ __forceinline__ void f3_ns_program(const BlockParams& b, const F3Blk&
             else Mf[e] = m;
           }
     }
+    if (F3_PREDICT) {
+      // (M pinned in front of the predictor, the operands in front of its branch: neither sinks behind the other's wait)
+#pragma unroll
+      for (int e = 0; e < 16; e += 8)
+        asm volatile("" : "+v"(Mf[e]), "+v"(Mf[e + 1]), "+v"(Mf[e + 2]), "+v"(Mf[e + 3]), "+v"(Mf[e + 4]), "+v"(Mf[e + 5]), "+v"(Mf[e + 6]), "+v"(Mf[e + 7]));
+      asm volatile("" : "+v"(ab), "+v"(al32[0]), "+v"(al32[1]), "+v"(be32[0]), "+v"(be32[1]), "+v"(abp0), "+v"(abp1),
+                        "+v"(al64[0]), "+v"(al64[1]), "+v"(al64[2]), "+v"(al64[3]), "+v"(be64[0]), "+v"(be64[1]), "+v"(be64[2]), "+v"(be64[3]));
+    }
     if (F3_PREDICT && try_ns && smw_ok && (p.ns_predict & 4)) {
       // Start of the iteration ("start predictor"): M_k differs from M_{k-1} by the rank-2 change of G
       // (h w^T + w h^T) / N + (ee / N^2) w w^T  -- downdated exactly, Sherman-Morrison-Woodbury with a = Z h, b = Z w left by
@@ -601,17 +650,7 @@ __device__ __forceinline__ void f3_ns_program(const BlockParams& b, const F3Blk&
       // kappa_k / kappa_{k-1} on everything (kappa G dominates M):  Z_0 = (kappa_{k-1} / kappa_k) (Z - alpha a^T - beta b^T).
       // Leaves ||I - M Z_0|| ~ 1e-4 .. 1e-3 where the plain start Z leaves 1e-2 .. 1e-1 (and > 1 through the first ~400 steps).
       const double sc = kap_prev * fast_rcp(kap_k);
-      const f64x2 ab = *reinterpret_cast<const f64x2*>(L.sab + 2 * (32 * inv + 16 * C + lcol));
       const double aj = ab[0], bj = ab[1];
-      const float* f32b = L.s32 + 128 * inv;
-      const f32x4s al32[2] = {*reinterpret_cast<const f32x4s*>(f32b + 8 * lrow), *reinterpret_cast<const f32x4s*>(f32b + 8 * lrow + 4)};
-      const f32x4s be32[2] = {*reinterpret_cast<const f32x4s*>(f32b + 32 + 8 * lrow), *reinterpret_cast<const f32x4s*>(f32b + 32 + 8 * lrow + 4)};
-      const f32x2s abp0 = *reinterpret_cast<const f32x2s*>(f32b + 64 + 2 * pcol), abp1 = *reinterpret_cast<const f32x2s*>(f32b + 64 + 2 * (16 + pcol));
-      const f64x2* alp = reinterpret_cast<const f64x2*>(L.sal + 32 * inv + 8 * lrow);
-      const f64x2* bep = reinterpret_cast<const f64x2*>(L.sbe + 32 * inv + 8 * lrow);
-      f64x2 al64[4], be64[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { al64[e] = alp[e]; be64[e] = bep[e]; }
       const float scf = (float)sc;
       // (the identity padding of r < 32 keeps its ones: alpha, a vanish there, only the scale has to be kept off it)
       const bool pc0 = FULL == 0 || (FULL == 2 ? pcol < rt : true), pc1 = FULL == 0 || (FULL == 2 ? false : pcol < rt);
@@ -640,16 +679,12 @@ __device__ __forceinline__ void f3_ns_program(const BlockParams& b, const F3Blk&
     bool done = false, failed = !try_ns, last = false;
     int it = 0;
     fetch_late = false;              // converged: the partner's final column is only needed by the NEXT step -> its phase 0
-    if (try_ns) {
-      F3_FETCH_PARTNER(0);           // issued with the norms' reads: one LDS round trip for both (harmless if the start failed:
-      F3_DECIDE();                   //  the sweep path reloads the operands)
-      if (!done && !failed) {
-        if (!(F3_KNOCK & 256)) F3_ITERATE(1);
-        par = 1;
-        it = 1;
-        if (last) { done = true; fetch_late = true; ++ctl.c_it; }
-      }
-    }
+    // One group of LDS reads behind B2: the partner's column, the norms and thresholds of the decision, and the operands of the
+    // Gram update and of phase F.  The update runs under their latency and in front of the decision -- which is uniform, and on
+    // which nothing in the update depends: G changes exactly once per step whichever exit the decision takes.  (The reads are
+    // unconditional: without a start nothing compares the norms, and the sweep path reloads the operands.)
+    F3_FETCH_PARTNER(0);
+    const F3Nrm nd0 = f3_norms_read(L.nrm, 0);
     {
       // G_k = G_{k-1} + (h w^T + w h^T) / N + ee w w^T / N^2   (tracked Gram)
       //     = G_{k-1} + u w^T + w hn^T,  u = h / N + (ee / N^2) w,  hn = h / N:  two FMAs per element
@@ -657,21 +692,39 @@ __device__ __forceinline__ void f3_ns_program(const BlockParams& b, const F3Blk&
       const double e2 = ee * iN * iN;
       double hcol[2], wcol[2], hn[2];
 #pragma unroll
-      for (int tj = 0; tj < 2; ++tj) { hcol[tj] = L.h[16 * tj + lcol]; wcol[tj] = L.w[16 * tj + lcol]; hn[tj] = hcol[tj] * iN; }
+      for (int tj = 0; tj < 2; ++tj) { hcol[tj] = L.h[16 * tj + lcol]; wcol[tj] = L.w[16 * tj + lcol]; }
+#pragma unroll
+      for (int ti = 0; ti < 2; ++ti)
+#pragma unroll
+        for (int qq = 0; qq < 4; ++qq) { hrow[ti * 4 + qq] = L.h[16 * ti + lrow + 4 * qq]; wrow[ti * 4 + qq] = L.w[16 * ti + lrow + 4 * qq]; }
+      mub_j = L.mub[16 * C + lcol];
+#pragma unroll
+      for (int tj = 0; tj < 2; ++tj) hn[tj] = hcol[tj] * iN;
 #pragma unroll
       for (int ti = 0; ti < 2; ++ti)
 #pragma unroll
         for (int qq = 0; qq < 4; ++qq) {
-          const double hi = L.h[16 * ti + lrow + 4 * qq], wi = L.w[16 * ti + lrow + 4 * qq];
+          const double hi = hrow[ti * 4 + qq], wi = wrow[ti * 4 + qq];
           const double ui = hi * iN + e2 * wi;
 #pragma unroll
           for (int tj = 0; tj < 2; ++tj)
             if (!(F3_KNOCK & 16)) G[(ti * 2 + tj) * 4 + qq] += ui * wcol[tj] + wi * hn[tj];
-          hrow[ti * 4 + qq] = hi;
-          wrow[ti * 4 + qq] = wi;
         }
       h_j = hcol[C];
-      mub_j = L.mub[16 * C + lcol];
+    }
+    // (left to itself the compiler sinks the update behind the stores of phase F, where nothing waits, and the decision's reads
+    //  are then all that stands between B2 and the branch: the values are pinned here)
+#pragma unroll
+    for (int e = 0; e < 16; e += 8)
+      asm volatile("" : "+v"(G[e]), "+v"(G[e + 1]), "+v"(G[e + 2]), "+v"(G[e + 3]), "+v"(G[e + 4]), "+v"(G[e + 5]), "+v"(G[e + 6]), "+v"(G[e + 7]));
+    if (try_ns) {
+      F3_DECIDE_FROM(nd0);
+      if (!done && !failed) {
+        if (!(F3_KNOCK & 256)) F3_ITERATE(1);
+        par = 1;
+        it = 1;
+        if (last) { done = true; fetch_late = true; ++ctl.c_it; }
+      }
     }
     BLK_T(3);
     // =============================== further iterations (only when the outcome is not known yet) ===============================
@@ -999,14 +1052,8 @@ __device__ __forceinline__ void f3_v_program(const BlockParams& b, const F3Blk& 
     // =============================== phase 2 ===============================
     bool done = false, failed = !try_ns, last = false;
     int it = 0;
-    if (try_ns) {
-      F3_DECIDE();
-      if (!done && !failed) {
-        par = 1;
-        it = 1;
-        if (last) done = true;
-      }
-    }
+    // as in f3_ns_program: the decision's words are read with the operands of the rank-1 update, the update runs, then the decision
+    const F3Nrm nd0 = f3_norms_read(L.nrm, 0);
     if (F3_KNOCK & 128) {
     } else if (isV3) {
       const int c = lane & 31, hf = lane >> 5;
@@ -1030,6 +1077,17 @@ __device__ __forceinline__ void f3_v_program(const BlockParams& b, const F3Blk& 
       const double wjn = wj * invN;
 #pragma unroll
       for (int t = 0; t < 16; ++t) pr[t] = vscale * (pr[t] - L.w[16 * hf + t] * wjn);   // psmf.py:135-138
+    }
+#pragma unroll
+    for (int t = 0; t < (isV0 ? 16 : 32); t += 8)       // (pinned in front of the decision, see f3_ns_program)
+      asm volatile("" : "+v"(pr[t]), "+v"(pr[t + 1]), "+v"(pr[t + 2]), "+v"(pr[t + 3]), "+v"(pr[t + 4]), "+v"(pr[t + 5]), "+v"(pr[t + 6]), "+v"(pr[t + 7]));
+    if (try_ns) {
+      F3_DECIDE_FROM(nd0);
+      if (!done && !failed) {
+        par = 1;
+        it = 1;
+        if (last) done = true;
+      }
     }
     if (poll && lane == 0) L.hand[1] = (poll_ab == 0 && poll_xg >= L.hand[0]) ? 1 : 0;
     BLK_T(3);
