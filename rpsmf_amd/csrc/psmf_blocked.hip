@@ -301,15 +301,15 @@ int init_blocked(psmf_filter* h) {
   // B = 64 - r timesteps per block, at most 48: the role-specialised filter kernel and the streaming bulk kernels stage
   // up to three 16-column tiles of a series block (r < 16 would otherwise give blocks of 49..63)
   h->block_steps = psmf::RB - cfg->r < 48 ? psmf::RB - cfg->r : 48;
-  HIP_TRY(h, hipMalloc((void**)&h->Kpart, (size_t)psmf::BLK_GRAM_WG * psmf::RB * psmf::RB * sizeof(double)));
-  HIP_TRY(h, hipMalloc((void**)&h->Kmat, (size_t)psmf::RB * psmf::RB * sizeof(double)));
-  HIP_TRY(h, hipMalloc((void**)&h->Acoef, (size_t)2 * psmf::RB * psmf::RM * sizeof(double)));
-  HIP_TRY(h, hipMalloc((void**)&h->Bcoef, (size_t)2 * psmf::RB * psmf::RB * sizeof(double)));
+  ALLOC_TRY(h, h->Kpart.alloc((size_t)psmf::BLK_GRAM_WG * psmf::RB * psmf::RB * sizeof(double)));
+  ALLOC_TRY(h, h->Kmat.alloc((size_t)psmf::RB * psmf::RB * sizeof(double)));
+  ALLOC_TRY(h, h->Acoef.alloc((size_t)2 * psmf::RB * psmf::RM * sizeof(double)));
+  ALLOC_TRY(h, h->Bcoef.alloc((size_t)2 * psmf::RB * psmf::RB * sizeof(double)));
   HIP_TRY(h, hipMemset(h->Bcoef, 0, (size_t)2 * psmf::RB * psmf::RB * sizeof(double)));
-  HIP_TRY(h, hipMalloc((void**)&h->XGpart, (size_t)psmf::BLK_GRAM_WG * (psmf::RB + psmf::XGB) * psmf::XGB * sizeof(double)));
-  HIP_TRY(h, hipMalloc((void**)&h->XG, (size_t)2 * (psmf::RB + psmf::XGB) * psmf::XGB * sizeof(double)));
+  ALLOC_TRY(h, h->XGpart.alloc((size_t)psmf::BLK_GRAM_WG * (psmf::RB + psmf::XGB) * psmf::XGB * sizeof(double)));
+  ALLOC_TRY(h, h->XG.alloc((size_t)2 * (psmf::RB + psmf::XGB) * psmf::XGB * sizeof(double)));
   HIP_TRY(h, hipMemset(h->XG, 0, (size_t)2 * (psmf::RB + psmf::XGB) * psmf::XGB * sizeof(double)));   // the all-reduce covers entries no kernel writes
-  HIP_TRY(h, hipMalloc((void**)&h->flags, 8 * sizeof(long long)));
+  ALLOC_TRY(h, h->flags.alloc(8 * sizeof(long long)));
   HIP_TRY(h, hipMemset(h->flags, 0, 8 * sizeof(long long)));
   // The filter chain is one workgroup on the critical path; the bulk kernels (cross-Gram, apply) run
   // beside it and would be co-scheduled onto its CU, stretching it by 10-17 % (measured).  Partition the
@@ -327,10 +327,10 @@ int init_blocked(psmf_filter* h) {
   if (known_layout && nres > 0 && nres < ncu / 2 && words <= 16) {
     uint32_t mf[16] = {0}, mb[16] = {0};
     for (int i = 0; i < ncu; ++i) (i < nres ? mf : mb)[i >> 5] |= 1u << (i & 31);
-    hipStream_t fs = nullptr, bs = nullptr;
-    if (hipExtStreamCreateWithCUMask(&fs, words, mf) == hipSuccess && hipExtStreamCreateWithCUMask(&bs, words, mb) == hipSuccess) {
-      h->fstream = fs;
-      h->bulk = bs;
+    Stream fs, bs;
+    if (hipExtStreamCreateWithCUMask(fs.put(), words, mf) == hipSuccess && hipExtStreamCreateWithCUMask(bs.put(), words, mb) == hipSuccess) {
+      h->fstream = std::move(fs);
+      h->bulk = std::move(bs);
       h->reserved_cus = nres;
       // The streaming kernels hold one 512-thread workgroup per CU (86-131 KB of LDS), and the dispatcher deals workgroups
       // to the 32 shader engines (8 XCDs x 4) in equal shares whatever the mask has left each of them.  The filter's
@@ -343,26 +343,23 @@ int init_blocked(psmf_filter* h) {
       if (h->bulk_wgs > 256) h->bulk_wgs = 256;
       { const int v = h->sw.bulk_wgs_env; if (v >= 8 && v <= 256) h->bulk_wgs = (v / 8) * 8; }
     } else {
-      (void)hipGetLastError();
-      if (fs) hipStreamDestroy(fs);
-      if (bs) hipStreamDestroy(bs);
+      (void)hipGetLastError();      // (plain streams below; fs, bs release what was created)
     }
   }
-  if (!h->bulk) HIP_TRY(h, hipStreamCreateWithFlags(&h->bulk, hipStreamNonBlocking));
+  if (!h->bulk) HIP_TRY(h, hipStreamCreateWithFlags(h->bulk.put(), hipStreamNonBlocking));
   for (int i = 0; i < 4; ++i) {
-    HIP_TRY(h, hipEventCreateWithFlags(&h->evF[i], hipEventDisableTiming));
-    HIP_TRY(h, hipEventCreateWithFlags(&h->evA[i], hipEventDisableTiming));
-    HIP_TRY(h, hipEventCreateWithFlags(&h->evX[i], hipEventDisableTiming));
+    HIP_TRY(h, hipEventCreateWithFlags(h->evF[i].put(), hipEventDisableTiming));
+    HIP_TRY(h, hipEventCreateWithFlags(h->evA[i].put(), hipEventDisableTiming));
+    HIP_TRY(h, hipEventCreateWithFlags(h->evX[i].put(), hipEventDisableTiming));
   }
-  HIP_TRY(h, hipEventCreateWithFlags(&h->evS, hipEventDisableTiming));
-  HIP_TRY(h, hipEventCreateWithFlags(&h->evC, hipEventDisableTiming));
-  for (int i = 0; i < psmf_filter::kTimedRuns; ++i) { HIP_TRY(h, hipEventCreate(&h->evK0[i])); HIP_TRY(h, hipEventCreate(&h->evK1[i])); }
+  HIP_TRY(h, hipEventCreateWithFlags(h->evS.put(), hipEventDisableTiming));
+  HIP_TRY(h, hipEventCreateWithFlags(h->evC.put(), hipEventDisableTiming));
+  for (int i = 0; i < psmf_filter::kTimedRuns; ++i) { HIP_TRY(h, hipEventCreate(h->evK0[i].put())); HIP_TRY(h, hipEventCreate(h->evK1[i].put())); }
   if (h->fstream && h->flags) {
     // the device-flag hand-off and the chained filter launches need the two streams to run concurrently: probe it (a waiter on the filter stream, then the
     // setter on the bulk stream; the waiter gives up after 50 ms)
-    int* dres = nullptr;
-    struct FreeOnExit { int** p; ~FreeOnExit() { if (*p) { hipFree(*p); *p = nullptr; } } } dres_guard{&dres};      // also on the HIP_TRY failure paths below
-    HIP_TRY(h, hipMalloc((void**)&dres, sizeof(int)));
+    Dev<int> dres;
+    ALLOC_TRY(h, dres.alloc(sizeof(int)));
     HIP_TRY(h, hipMemset(dres, 0, sizeof(int)));
     HIP_TRY(h, hipDeviceSynchronize());      // hipMemset is asynchronous on the null stream, the probe's streams are non-blocking: the zeroes (of dres and of h->flags above) first
     hipLaunchKernelGGL(psmf::psmf_probe_wait_k, dim3(1), dim3(1), 0, h->fstream, h->flags + 7, 1LL, 5000000LL, dres);

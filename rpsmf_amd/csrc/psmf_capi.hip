@@ -143,7 +143,7 @@ int enqueue_gram_into(psmf_filter* h, double* Gout, const DevState* wst, const d
   const int rows = (h->cfg.d_local + kGramWG - 1) / kGramWG;
   by_storage(h, [&](auto t) {
     hipLaunchKernelGGL(psmf::psmf_gram_partial<decltype(t)>, dim3(kGramWG), dim3(psmf::WG), 0, h->stream,
-                       (const decltype(t)*)h->C, h->cfg.d_local, r, h->geo.rp, rows, h->gpart, wst, rho_rows);
+                       h->C.as<const decltype(t)>(), h->cfg.d_local, r, h->geo.rp, rows, h->gpart, wst, rho_rows);
   });
   hipLaunchKernelGGL(psmf::psmf_gram_reduce, dim3((r * r + 255) / 256), dim3(256), 0, h->stream,
                      (const double*)h->gpart, kGramWG, r * r, Gout);
@@ -255,22 +255,12 @@ void destroy_graph(psmf_filter* h) {
 }
 
 int ensure_scratch(psmf_filter* h, size_t bytes) {
-  if (h->scratch_bytes >= bytes) return PSMF_OK;
-  if (h->scratch) HIP_TRY(h, hipFree(h->scratch));
-  h->scratch = nullptr;
-  h->scratch_bytes = 0;
-  HIP_TRY(h, hipMalloc((void**)&h->scratch, bytes));
-  h->scratch_bytes = bytes;
+  ALLOC_TRY(h, h->scratch.reserve(bytes));
   return PSMF_OK;
 }
 
 int ensure_rot_tmp(psmf_filter* h, size_t bytes) {
-  if (h->rot_tmp_bytes >= bytes) return PSMF_OK;
-  if (h->rot_tmp) HIP_TRY(h, hipFree(h->rot_tmp));
-  h->rot_tmp = nullptr;
-  h->rot_tmp_bytes = 0;
-  HIP_TRY(h, hipMalloc(&h->rot_tmp, bytes));
-  h->rot_tmp_bytes = bytes;
+  ALLOC_TRY(h, h->rot_tmp.reserve(bytes));
   return PSMF_OK;
 }
 
@@ -323,7 +313,7 @@ void update_solve_dual(psmf_filter* h) {
 // Persistent kernels spin on device flags: two of them resident at once (two handles of one process on one device) could each
 // hold compute units the other needs.  They are serialised per device with an event chain.
 std::mutex g_ps_mutex;
-hipEvent_t g_ps_event[64] = {};
+hipEvent_t g_ps_event[64] = {};      // raw on purpose, never destroyed: an owning static would call into a runtime that is already torn down at exit
 
 int launch_pstep(psmf_filter* h, int64_t k_begin, int64_t n) {
   while (n > 0) {
@@ -337,11 +327,11 @@ int launch_pstep(psmf_filter* h, int64_t k_begin, int64_t n) {
     q.rows_per_wg = h->ps_plan.rows_per_wg;
     q.np = h->ps_plan.np;
     q.ncol2 = h->ps_plan.ncol2;
-    q.flags = reinterpret_cast<unsigned*>(h->ps_comm);
-    q.pkt = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(h->ps_comm) + h->ps_plan.off_pkt);
-    q.part = reinterpret_cast<double*>(reinterpret_cast<char*>(h->ps_comm) + h->ps_plan.off_part);
+    q.flags = h->ps_comm.as<unsigned>();
+    q.pkt = reinterpret_cast<unsigned long long*>(h->ps_comm.as<char>() + h->ps_plan.off_pkt);
+    q.part = reinterpret_cast<double*>(h->ps_comm.as<char>() + h->ps_plan.off_part);
     if (h->cfg.masked) {
-      char* base = reinterpret_cast<char*>(h->ps_comm);
+      char* base = h->ps_comm.as<char>();
       q.masked = 1;
       q.nge = h->ps_plan.nge;
       q.slice_len = h->ps_plan.slice_len;
@@ -486,19 +476,19 @@ int choose_engine(psmf_filter* h) {
 int alloc_common(psmf_filter* h) {
   const psmf_config* cfg = &h->cfg;
   HIP_TRY(h, hipSetDevice(cfg->device));
-  HIP_TRY(h, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-  HIP_TRY(h, hipEventCreate(&h->ev0));
-  HIP_TRY(h, hipEventCreate(&h->ev1));
-  HIP_TRY(h, hipHostMalloc((void**)&h->err_host, sizeof(int), hipHostMallocMapped));
-  HIP_TRY(h, hipHostGetDevicePointer((void**)&h->err_host_dev, h->err_host, 0));
-  HIP_TRY(h, hipMalloc((void**)&h->st, sizeof(DevState)));
+  HIP_TRY(h, hipStreamCreateWithFlags(h->stream.put(), hipStreamNonBlocking));
+  HIP_TRY(h, hipEventCreate(h->ev0.put()));
+  HIP_TRY(h, hipEventCreate(h->ev1.put()));
+  HIP_TRY(h, hipHostMalloc(h->err_host.put(), sizeof(int), hipHostMallocMapped));
+  HIP_TRY(h, hipHostGetDevicePointer((void**)&h->err_host_dev, h->err_host.get(), 0));
+  ALLOC_TRY(h, h->st.alloc(sizeof(DevState)));
   HIP_TRY(h, hipMemset(h->st, 0, sizeof(DevState)));
-  HIP_TRY(h, hipMalloc(&h->C, (size_t)cfg->d_local * h->geo.rp * h->elem()));
-  HIP_TRY(h, hipMalloc((void**)&h->partials, (size_t)h->geo.n_sweep_wg * h->geo.ps * sizeof(double)));
-  HIP_TRY(h, hipMalloc((void**)&h->gpart, (size_t)((cfg->masked || cfg->nonuniform_R) ? 256 : kGramWG) * (cfg->r * cfg->r + 1) * sizeof(double)));
-  if (cfg->masked) HIP_TRY(h, hipMalloc((void**)&h->mg, (size_t)(cfg->r * cfg->r + 2 + (cfg->r * cfg->r + 64) / 64 + 1) * sizeof(double)));     // Gram, count | trace shares
+  ALLOC_TRY(h, h->C.alloc((size_t)cfg->d_local * h->geo.rp * h->elem()));
+  ALLOC_TRY(h, h->partials.alloc((size_t)h->geo.n_sweep_wg * h->geo.ps * sizeof(double)));
+  ALLOC_TRY(h, h->gpart.alloc((size_t)((cfg->masked || cfg->nonuniform_R) ? 256 : kGramWG) * (cfg->r * cfg->r + 1) * sizeof(double)));
+  if (cfg->masked) ALLOC_TRY(h, h->mg.alloc((size_t)(cfg->r * cfg->r + 2 + (cfg->r * cfg->r + 64) / 64 + 1) * sizeof(double)));     // Gram, count | trace shares
   h->th_cap = (size_t)(cfg->n_theta > psmf::RM ? cfg->n_theta : psmf::RM);
-  HIP_TRY(h, hipMalloc((void**)&h->thbuf, 4 * h->th_cap * sizeof(double)));
+  ALLOC_TRY(h, h->thbuf.alloc(4 * h->th_cap * sizeof(double)));
   HIP_TRY(h, hipMemset(h->thbuf, 0, 4 * h->th_cap * sizeof(double)));
   return PSMF_OK;
 }
@@ -512,9 +502,9 @@ int init_pstep(psmf_filter* h) {
     HIP_TRY(h, hipGetDeviceProperties(&prop, cfg->device));
     if (psmf::pstep_plan(cfg->d_local, cfg->r, prop.multiProcessorCount, cfg->storage == PSMF_F64, cfg->masked == 1, &h->ps_plan)) {
       HIP_TRY(h, psmf::pstep_init());
-      HIP_TRY(h, hipMalloc(&h->ps_comm, h->ps_plan.total_bytes));
+      ALLOC_TRY(h, h->ps_comm.alloc(h->ps_plan.total_bytes));
       HIP_TRY(h, hipMemset(h->ps_comm, 0, h->ps_plan.total_bytes));
-      if (h->sw.pstep_prof) { HIP_TRY(h, hipMalloc((void**)&h->ps_prof, 64 * sizeof(long long))); HIP_TRY(h, hipMemset(h->ps_prof, 0, 64 * sizeof(long long))); }
+      if (h->sw.pstep_prof) { ALLOC_TRY(h, h->ps_prof.alloc(64 * sizeof(long long))); HIP_TRY(h, hipMemset(h->ps_prof, 0, 64 * sizeof(long long))); }
       h->ps_ok = true;
     }
   }
@@ -572,6 +562,20 @@ void fill_step_params(psmf_filter* h) {
   sp.b1 = cfg->adam_b1; sp.b2 = cfg->adam_b2;
 }
 
+// PSMF_PSTEP_PROF=1 with a -DPSTEP_PROF build: the per-phase clock sums of the last launch, at psmf_destroy
+void print_pstep_prof(psmf_filter* h) {
+  long long pf[64];
+  if (!h->ps_prof || hipMemcpy(pf, h->ps_prof, sizeof(pf), hipMemcpyDeviceToHost) != hipSuccess || h->ps_prof_steps <= 0) return;
+  fprintf(stderr, "[pstep prof] cycles per timestep over the last launch (%lld steps), d_local %d r %d:\n", h->ps_prof_steps, h->cfg.d_local, h->cfg.r);
+  const char* grp[3] = {"hub workers", "solve wave ", "row wg 0   "};
+  const int base[3] = {0, 16, 24}, cnt[3] = {11, 3, 8};
+  for (int g = 0; g < 3; ++g) {
+    fprintf(stderr, "  %s:", grp[g]);
+    for (int i = 0; i < cnt[g]; ++i) fprintf(stderr, " %7.0f", (double)pf[base[g] + i] / (double)h->ps_prof_steps);
+    fprintf(stderr, "\n");
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -616,62 +620,12 @@ int psmf_create(psmf_handle* out, const psmf_config* cfg) {
 void psmf_destroy(psmf_handle h) {
   if (!h) return;
   hipSetDevice(h->cfg.device);
-  if (h->stream) hipStreamSynchronize(h->stream);
+  for (hipStream_t s : {h->stream.get(), h->bulk.get(), h->fstream.get(), h->cstream.get()})
+    if (s) hipStreamSynchronize(s);
+  print_pstep_prof(h);
   destroy_graph(h);
-  ring_destroy(h);
   if (h->comm) ncclCommDestroy(h->comm);
-  if (h->st) hipFree(h->st);
-  if (h->C) hipFree(h->C);
-  if (h->Y) hipFree(h->Y);
-  if (h->YP) hipFree(h->YP);
-  if (h->partials) hipFree(h->partials);
-  if (h->ps_prof) {
-    long long pf[64];
-    if (hipMemcpy(pf, h->ps_prof, sizeof(pf), hipMemcpyDeviceToHost) == hipSuccess && h->ps_prof_steps > 0) {
-      fprintf(stderr, "[pstep prof] cycles per timestep over the last launch (%lld steps), d_local %d r %d:\n", h->ps_prof_steps, h->cfg.d_local, h->cfg.r);
-      const char* grp[3] = {"hub workers", "solve wave ", "row wg 0   "};
-      const int base[3] = {0, 16, 24}, cnt[3] = {11, 3, 8};
-      for (int g = 0; g < 3; ++g) {
-        fprintf(stderr, "  %s:", grp[g]);
-        for (int i = 0; i < cnt[g]; ++i) fprintf(stderr, " %7.0f", (double)pf[base[g] + i] / (double)h->ps_prof_steps);
-        fprintf(stderr, "\n");
-      }
-    }
-    hipFree(h->ps_prof);
-  }
-  if (h->ps_comm) hipFree(h->ps_comm);
-  if (h->gpart) hipFree(h->gpart);
-  if (h->mu_hist) hipFree(h->mu_hist);
-  if (h->thbuf) hipFree(h->thbuf);
-  if (h->sched) hipFree(h->sched);
-  if (h->qmat) hipFree(h->qmat);
-  if (h->rho_rows) hipFree(h->rho_rows);
-  if (h->rotU) hipFree(h->rotU);
-  if (h->rot_tmp) hipFree(h->rot_tmp);
-  if (h->mask) hipFree(h->mask);
-  if (h->mmiss) hipFree(h->mmiss);
-  if (h->mg) hipFree(h->mg);
-  if (h->sc_hist) hipFree(h->sc_hist);
-  if (h->Kpart) hipFree(h->Kpart);
-  if (h->Kmat) hipFree(h->Kmat);
-  if (h->Acoef) hipFree(h->Acoef);
-  if (h->Bcoef) hipFree(h->Bcoef);
-  if (h->XGpart) hipFree(h->XGpart);
-  if (h->XG) hipFree(h->XG);
-  if (h->flags) hipFree(h->flags);
-  for (int i = 0; i < 4; ++i) { if (h->evF[i]) hipEventDestroy(h->evF[i]); if (h->evA[i]) hipEventDestroy(h->evA[i]); if (h->evX[i]) hipEventDestroy(h->evX[i]); }
-  if (h->evS) hipEventDestroy(h->evS);
-  if (h->evC) hipEventDestroy(h->evC);
-  if (h->host_buf) hipHostFree(h->host_buf);
-  for (int i = 0; i < psmf_filter::kTimedRuns; ++i) { if (h->evK0[i]) hipEventDestroy(h->evK0[i]); if (h->evK1[i]) hipEventDestroy(h->evK1[i]); }
-  if (h->bulk) { hipStreamSynchronize(h->bulk); hipStreamDestroy(h->bulk); }
-  if (h->fstream) { hipStreamSynchronize(h->fstream); hipStreamDestroy(h->fstream); }
-  if (h->scratch) hipFree(h->scratch);
-  if (h->ev0) hipEventDestroy(h->ev0);
-  if (h->ev1) hipEventDestroy(h->ev1);
-  if (h->err_host) hipHostFree(h->err_host);
-  if (h->stream) hipStreamDestroy(h->stream);
-  delete h;
+  delete h;      // every buffer, event and stream: the members release themselves
 }
 
 int psmf_set_state(psmf_handle h, const double* C, const double* V, const double* P, const double* Q,
@@ -941,51 +895,43 @@ int psmf_run_timed(psmf_handle h, int64_t k_begin, int64_t k_end, float* ms) {
 // psmf_time_kernel launches a step's kernels at the FIRST steps of the uploaded series whatever the handle has run so far: they
 // overwrite the y_hat rows and the posterior means recorded for those steps, which the caller reads after a run
 // (psmf_download_y_pred, psmf_sq_error, psmf_download_mu).  These records are saved and restored with the state.
-struct StepRecords {
-  void* yp = nullptr; double* mu = nullptr;
-  size_t yp_bytes = 0, mu_bytes = 0;
-};
+struct StepRecords { Dev<void> yp; Dev<double> mu; };
 
 static int save_step_records(psmf_filter* h, int64_t yp_rows, int64_t mu_rows, StepRecords& s) {
   if (yp_rows > h->T_cap) yp_rows = h->T_cap;
   if (mu_rows > h->T_cap + 1) mu_rows = h->T_cap + 1;
   if (h->YP && yp_rows > 0) {
-    s.yp_bytes = (size_t)yp_rows * h->cfg.d_local * h->elem();
-    HIP_TRY(h, hipMalloc(&s.yp, s.yp_bytes));
-    HIP_TRY(h, hipMemcpy(s.yp, h->YP, s.yp_bytes, hipMemcpyDeviceToDevice));
+    ALLOC_TRY(h, s.yp.alloc((size_t)yp_rows * h->cfg.d_local * h->elem()));
+    HIP_TRY(h, hipMemcpy(s.yp, h->YP, s.yp.bytes(), hipMemcpyDeviceToDevice));
   }
   if (h->mu_hist && mu_rows > 0) {
-    s.mu_bytes = (size_t)mu_rows * h->cfg.r * sizeof(double);
-    HIP_TRY(h, hipMalloc((void**)&s.mu, s.mu_bytes));
-    HIP_TRY(h, hipMemcpy(s.mu, h->mu_hist, s.mu_bytes, hipMemcpyDeviceToDevice));
+    ALLOC_TRY(h, s.mu.alloc((size_t)mu_rows * h->cfg.r * sizeof(double)));
+    HIP_TRY(h, hipMemcpy(s.mu, h->mu_hist, s.mu.bytes(), hipMemcpyDeviceToDevice));
   }
   return PSMF_OK;
 }
 
-static int restore_step_records(psmf_filter* h, StepRecords& s) {
-  if (s.yp) { HIP_TRY(h, hipMemcpy(h->YP, s.yp, s.yp_bytes, hipMemcpyDeviceToDevice)); HIP_TRY(h, hipFree(s.yp)); s.yp = nullptr; }
-  if (s.mu) { HIP_TRY(h, hipMemcpy(h->mu_hist, s.mu, s.mu_bytes, hipMemcpyDeviceToDevice)); HIP_TRY(h, hipFree(s.mu)); s.mu = nullptr; }
+static int restore_step_records(psmf_filter* h, const StepRecords& s) {
+  if (s.yp) HIP_TRY(h, hipMemcpy(h->YP, s.yp, s.yp.bytes(), hipMemcpyDeviceToDevice));
+  if (s.mu) HIP_TRY(h, hipMemcpy(h->mu_hist, s.mu, s.mu.bytes(), hipMemcpyDeviceToDevice));
   return PSMF_OK;
 }
 
 // Everything psmf_time_kernel's launches mutate: C, the DevState, theta with its gradient sums and Adam moments (the filter
-// kernels and the serial stage step them too), and the step records above.
+// kernels and the serial stage step them too), and the step records above.  The copies are released with the object.
 struct TimingSave {
-  void* C = nullptr; DevState* st = nullptr; double* th = nullptr;
-  size_t cbytes = 0, thbytes = 0;
+  Dev<void> C; Dev<DevState> st; Dev<double> th;
   StepRecords rec;
   bool complete = false;
 };
 
 static int save_for_timing(psmf_filter* h, int64_t yp_rows, int64_t mu_rows, TimingSave& s) {
-  s.cbytes = (size_t)h->cfg.d_local * h->geo.rp * h->elem();
-  s.thbytes = 4 * h->th_cap * sizeof(double);
-  HIP_TRY(h, hipMalloc(&s.C, s.cbytes));
-  HIP_TRY(h, hipMalloc((void**)&s.st, sizeof(DevState)));
-  HIP_TRY(h, hipMalloc((void**)&s.th, s.thbytes));
-  HIP_TRY(h, hipMemcpy(s.C, h->C, s.cbytes, hipMemcpyDeviceToDevice));
+  ALLOC_TRY(h, s.C.alloc((size_t)h->cfg.d_local * h->geo.rp * h->elem()));
+  ALLOC_TRY(h, s.st.alloc(sizeof(DevState)));
+  ALLOC_TRY(h, s.th.alloc(4 * h->th_cap * sizeof(double)));
+  HIP_TRY(h, hipMemcpy(s.C, h->C, s.C.bytes(), hipMemcpyDeviceToDevice));
   HIP_TRY(h, hipMemcpy(s.st, h->st, sizeof(DevState), hipMemcpyDeviceToDevice));
-  HIP_TRY(h, hipMemcpy(s.th, h->thbuf, s.thbytes, hipMemcpyDeviceToDevice));
+  HIP_TRY(h, hipMemcpy(s.th, h->thbuf, s.th.bytes(), hipMemcpyDeviceToDevice));
   int rc = save_step_records(h, yp_rows, mu_rows, s.rec);
   if (rc) return rc;
   HIP_TRY(h, hipDeviceSynchronize());      // (device-to-device copies on the null stream are not ordered against the handle's non-blocking stream)
@@ -993,17 +939,12 @@ static int save_for_timing(psmf_filter* h, int64_t yp_rows, int64_t mu_rows, Tim
   return PSMF_OK;
 }
 
-static int restore_after_timing(psmf_filter* h, TimingSave& s) {
+static int restore_after_timing(psmf_filter* h, const TimingSave& s) {
   HIP_TRY(h, hipStreamSynchronize(h->stream));
-  HIP_TRY(h, hipMemcpy(h->C, s.C, s.cbytes, hipMemcpyDeviceToDevice));
+  HIP_TRY(h, hipMemcpy(h->C, s.C, s.C.bytes(), hipMemcpyDeviceToDevice));
   HIP_TRY(h, hipMemcpy(h->st, s.st, sizeof(DevState), hipMemcpyDeviceToDevice));
-  HIP_TRY(h, hipMemcpy(h->thbuf, s.th, s.thbytes, hipMemcpyDeviceToDevice));
+  HIP_TRY(h, hipMemcpy(h->thbuf, s.th, s.th.bytes(), hipMemcpyDeviceToDevice));
   return restore_step_records(h, s.rec);
-}
-
-static void free_timing_save(TimingSave& s) {
-  (void)hipFree(s.C); (void)hipFree(s.st); (void)hipFree(s.th); (void)hipFree(s.rec.yp); (void)hipFree(s.rec.mu);
-  s = TimingSave();
 }
 
 static int time_step_kernels(psmf_filter* h, int which, int iters, float* avg_us) {
@@ -1033,7 +974,7 @@ int psmf_time_kernel(psmf_handle h, int which, int iters, float* avg_us) {
   const bool blocked = h->engine == 2;
   if (!blocked && h->need_prep) { rc = prepare(h, h->k_done); if (rc) return rc; }
   HIP_TRY(h, hipStreamSynchronize(h->stream));
-  // Save everything the kernels mutate; from here on there is one way out, which puts it back and frees the copies.
+  // Save everything the kernels mutate; from here on there is one way out, which puts it back (the copies go with sv).
   TimingSave sv;
   double* const hist = h->sp.mu_hist;
   const int nb = (int)(h->T_cap < h->block_steps ? h->T_cap : h->block_steps);
@@ -1049,7 +990,6 @@ int psmf_time_kernel(psmf_handle h, int which, int iters, float* avg_us) {
   if (!rc) rc = blocked ? time_block_kernels(h, which, iters, nb, sv.st, avg_us) : time_step_kernels(h, which, iters, avg_us);
   h->sp.mu_hist = hist;
   if (sv.complete) { const int rc2 = restore_after_timing(h, sv); if (!rc) rc = rc2; }     // (a failed measurement too leaves the state as it found it)
-  free_timing_save(sv);
   return rc;
 }
 
@@ -1148,13 +1088,13 @@ int psmf_project(psmf_handle h, const double* mu, int64_t n_pred, double* out) {
   const size_t lds = (size_t)64 * r * sizeof(double);
   by_storage(h, [&](auto t) {
     hipLaunchKernelGGL(psmf::psmf_predict_rows<decltype(t)>, dim3(grid), dim3(psmf::WG), lds, h->stream,
-                       (const decltype(t)*)h->C, dl, r, h->geo.rp, (const double*)dmu, (int)n_pred, dout);
+                       h->C.as<const decltype(t)>(), dl, r, h->geo.rp, (const double*)dmu, (int)n_pred, dout);
   });
   HIP_TRY(h, hipGetLastError());
   if (h->rotU) {                         // non-diagonal R: C here is U^T C -- rotate the projections back
     rc = ensure_rot_tmp(h, obytes);
     if (rc) return rc;
-    rc = rot_gemm(h, (const double*)dout, (long long)dl, 1LL, (const double*)h->rotU, 1LL, (long long)dl, (double*)h->rot_tmp, (long long)dl,
+    rc = rot_gemm(h, (const double*)dout, (long long)dl, 1LL, (const double*)h->rotU, 1LL, (long long)dl, h->rot_tmp.as<double>(), (long long)dl,
                   (long long)n_pred, (long long)dl, (long long)dl);
     if (rc) return rc;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -1208,8 +1148,8 @@ int psmf_comm_init(psmf_handle h, int nranks, int rank, const void* unique_id) {
     // Connect now: the first collective of each message size sets up its channels (seconds on 8 GPUs), and in the pipelined
     // block engine a filter kernel would be polling for its result meanwhile.  Same sizes, same streams as the engines use.
     const size_t xg_elems = (size_t)(psmf::RB + psmf::XGB) * psmf::XGB;
-    double* tmp = nullptr;
-    HIP_TRY(h, hipMalloc(&tmp, xg_elems * sizeof(double)));
+    Dev<double> tmp;
+    ALLOC_TRY(h, tmp.alloc(xg_elems * sizeof(double)));
     HIP_TRY(h, hipMemsetAsync(tmp, 0, xg_elems * sizeof(double), h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     const size_t sizes[4] = {(size_t)h->cfg.r + 1, (size_t)h->cfg.r * h->cfg.r, (size_t)psmf::RB * psmf::RB, xg_elems};
@@ -1218,12 +1158,11 @@ int psmf_comm_init(psmf_handle h, int nranks, int rank, const void* unique_id) {
       if (!streams[si]) continue;
       for (int zi = 0; zi < 4; ++zi) {
         const ncclResult_t e = ncclAllReduce(tmp, tmp, sizes[zi], ncclDouble, ncclSum, h->comm, streams[si]);
-        if (e != ncclSuccess) { hipFree(tmp); return fail(h, PSMF_ERR_RCCL, std::string("warm-up all-reduce: ") + ncclGetErrorString(e)); }
+        if (e != ncclSuccess) return fail(h, PSMF_ERR_RCCL, std::string("warm-up all-reduce: ") + ncclGetErrorString(e));
       }
       const hipError_t he = hipStreamSynchronize(streams[si]);
-      if (he != hipSuccess) { hipFree(tmp); return fail(h, PSMF_ERR_HIP, std::string("warm-up all-reduce: ") + hipGetErrorString(he)); }
+      if (he != hipSuccess) return fail(h, PSMF_ERR_HIP, std::string("warm-up all-reduce: ") + hipGetErrorString(he));
     }
-    hipFree(tmp);
   }
   h->use_coll = nranks > 1 || h->sw.force_collective;
   h->sp.external_reduce = (h->use_coll || h->sp.tail_reduce) ? 1 : 0;
@@ -1259,7 +1198,7 @@ int psmf_set_row_noise(psmf_handle h, const double* rho_rows, double rho_mean) {
   int rc = set_device(h);
   if (rc) return rc;
   HIP_TRY(h, hipStreamSynchronize(h->stream));
-  if (!h->rho_rows) HIP_TRY(h, hipMalloc((void**)&h->rho_rows, (size_t)h->cfg.d_local * sizeof(double)));
+  ALLOC_TRY(h, h->rho_rows.reserve((size_t)h->cfg.d_local * sizeof(double)));
   HIP_TRY(h, hipMemcpy(h->rho_rows, rho_rows, (size_t)h->cfg.d_local * sizeof(double), hipMemcpyHostToDevice));
   h->sp.rho_rows = h->rho_rows;
   h->sp.rho_mean = rho_mean;
@@ -1305,7 +1244,7 @@ int psmf_set_noise_rotation(psmf_handle h, const double* U, const double* lam) {
   }
   int rc = psmf_set_row_noise(h, lam, tr / (double)d);
   if (rc) return rc;
-  if (!h->rotU) HIP_TRY(h, hipMalloc((void**)&h->rotU, d * d * sizeof(double)));
+  ALLOC_TRY(h, h->rotU.reserve(d * d * sizeof(double)));
   HIP_TRY(h, hipMemcpy(h->rotU, U, d * d * sizeof(double), hipMemcpyHostToDevice));
   return PSMF_OK;
 }
@@ -1318,7 +1257,7 @@ int psmf_set_schedules(psmf_handle h, const double* rho_k, const double* q_k, in
   int rc = set_device(h);
   if (rc) return rc;
   HIP_TRY(h, hipStreamSynchronize(h->stream));
-  if (h->sched) { HIP_TRY(h, hipFree(h->sched)); h->sched = nullptr; }
+  h->sched.reset();
   h->sched_n = 0;
   h->sp.rho_sched = h->sp.q_sched = nullptr;
   if ((rho_k || q_k) && n > 0) {
@@ -1327,7 +1266,7 @@ int psmf_set_schedules(psmf_handle h, const double* rho_k, const double* q_k, in
     std::vector<double> buf((size_t)2 * (n + 1), 1.0);
     if (rho_k) { memcpy(buf.data(), rho_k, (size_t)n * sizeof(double)); buf[n] = rho_k[n - 1]; }
     if (q_k) { memcpy(buf.data() + n + 1, q_k, (size_t)n * sizeof(double)); buf[2 * n + 1] = q_k[n - 1]; }
-    HIP_TRY(h, hipMalloc((void**)&h->sched, buf.size() * sizeof(double)));
+    ALLOC_TRY(h, h->sched.alloc(buf.size() * sizeof(double)));
     HIP_TRY(h, hipMemcpy(h->sched, buf.data(), buf.size() * sizeof(double), hipMemcpyHostToDevice));
     h->sched_n = n;
     if (rho_k) h->sp.rho_sched = h->sched;
@@ -1352,13 +1291,13 @@ int psmf_set_q_matrix_schedule(psmf_handle h, const double* Q_k, int64_t n) {
   int rc = set_device(h);
   if (rc) return rc;
   HIP_TRY(h, hipStreamSynchronize(h->stream));
-  if (h->qmat) { HIP_TRY(h, hipFree(h->qmat)); h->qmat = nullptr; }
+  h->qmat.reset();
   h->qmat_n = 0;
   h->sp.q_mat = nullptr;
   if (Q_k && n > 0) {
     // n + 1 matrices, the last one repeated (as in psmf_set_schedules: the serial stage prepares one step ahead)
     const size_t rr = (size_t)h->cfg.r * h->cfg.r;
-    HIP_TRY(h, hipMalloc((void**)&h->qmat, (size_t)(n + 1) * rr * sizeof(double)));
+    ALLOC_TRY(h, h->qmat.alloc((size_t)(n + 1) * rr * sizeof(double)));
     HIP_TRY(h, hipMemcpy(h->qmat, Q_k, (size_t)n * rr * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(h->qmat + (size_t)n * rr, Q_k + (size_t)(n - 1) * rr, rr * sizeof(double), hipMemcpyHostToDevice));
     h->qmat_n = n;
@@ -1441,16 +1380,16 @@ int psmf_measure_copy_bandwidth(int device, size_t bytes, int iters, double* gbp
   psmf_handle h = nullptr;       // errors go to the create-error slot
   HIP_TRY(h, hipSetDevice(device));
   const size_t n16 = bytes / 16;
-  void *src = nullptr, *dst = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  hipStream_t s = nullptr;
-  HIP_TRY(h, hipMalloc(&src, n16 * 16));
-  HIP_TRY(h, hipMalloc(&dst, n16 * 16));
+  Dev<float4> src, dst;
+  Event e0, e1;
+  Stream s;
+  ALLOC_TRY(h, src.alloc(n16 * 16));
+  ALLOC_TRY(h, dst.alloc(n16 * 16));
   HIP_TRY(h, hipMemset(src, 1, n16 * 16));
   HIP_TRY(h, hipDeviceSynchronize());
-  HIP_TRY(h, hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  HIP_TRY(h, hipEventCreate(&e0));
-  HIP_TRY(h, hipEventCreate(&e1));
+  HIP_TRY(h, hipStreamCreateWithFlags(s.put(), hipStreamNonBlocking));
+  HIP_TRY(h, hipEventCreate(e0.put()));
+  HIP_TRY(h, hipEventCreate(e1.put()));
   // four 16-byte vectors per thread (measured on MI355X, 1 GiB: 4.1 TB/s with 4 workgroups per CU, 5.0 with one workgroup
   // per 16 KiB; 4 GiB: 5.5 TB/s)
   size_t gsz = n16 / ((size_t)psmf::WG * 4);
@@ -1466,7 +1405,6 @@ int psmf_measure_copy_bandwidth(int device, size_t bytes, int iters, double* gbp
   float ms = 0.f;
   HIP_TRY(h, hipEventElapsedTime(&ms, e0, e1));
   *gbps = 2.0 * (double)(n16 * 16) * iters / (ms * 1e-3) / 1e9;     // read + write
-  hipEventDestroy(e0); hipEventDestroy(e1); hipStreamDestroy(s); hipFree(src); hipFree(dst);
   return PSMF_OK;
 }
 
@@ -1476,7 +1414,7 @@ int psmf_comm_init_host(psmf_handle h, int nranks, int rank, psmf_allreduce_fn f
   if (h->comm) return fail(h, PSMF_ERR_STATE, "psmf_comm_init_host: the handle already has an RCCL communicator");
   int rc = set_device(h);
   if (rc) return rc;
-  if (!h->host_buf) HIP_TRY(h, hipHostMalloc((void**)&h->host_buf, psmf_filter::kHostBufElems * sizeof(double), hipHostMallocDefault));
+  if (!h->host_buf) HIP_TRY(h, hipHostMalloc(h->host_buf.put(), psmf_filter::kHostBufElems * sizeof(double), hipHostMallocDefault));
   h->host_fn = fn;
   h->host_ctx = ctx;
   h->nranks = nranks;

@@ -4,6 +4,7 @@
 #pragma once
 #include "../../include/psmf_hip.h"
 #include "psmf_block.h"       // BlockParams
+#include "psmf_own.h"         // Event, Stream, Dev<T>, Pinned<T>: what owns a device resource
 #include "psmf_pstep.h"       // persistent per-step engine: its kernels are a translation unit of their own (psmf_pstep.hip)
 
 #include <rccl/rccl.h>
@@ -72,80 +73,76 @@ struct Switches {
   int copy_grid = as_int("PSMF_COPY_GRID", 0);           // grid of the copy-bandwidth probe (0, unset: sized from the buffer)
 };
 
+// Every device resource of a handle is a member of an owning type (psmf_own.h) and is released when the handle is deleted.
+// psmf_destroy waits for all of the handle's streams first, so the order in which the members release is immaterial.  StepParams /
+// BlockParams carry raw copies of the pointers into the kernels: they are set where the buffer is allocated.
 struct psmf_filter {
   psmf_config cfg;
   Geometry geo;
   Switches sw;
-  hipStream_t stream = nullptr;
-  DevState* st = nullptr;
-  void* C = nullptr;
-  void* Y = nullptr;
-  void* YP = nullptr;
-  double* partials = nullptr;
-  double* gpart = nullptr;
-  double* thbuf = nullptr;     // theta | gradsum | adam_m | adam_v, th_cap doubles each
+  Stream stream;
+  Dev<DevState> st;
+  Dev<void> C, Y, YP;
+  Dev<double> partials, gpart;
+  Dev<double> thbuf;           // theta | gradsum | adam_m | adam_v, th_cap doubles each
   size_t th_cap = 0;
-  double* rho_rows = nullptr;  // d_local per-row diag(R) (cfg.nonuniform_R)
-  double* rotU = nullptr;      // d x d: eigenvectors of a non-diagonal R in its columns (psmf_set_noise_rotation); series, C, y_hat are kept rotated
-  void* rot_tmp = nullptr;     // staging of a rotation (the GEMM is out of place)
-  size_t rot_tmp_bytes = 0;
+  Dev<double> rho_rows;        // d_local per-row diag(R) (cfg.nonuniform_R)
+  Dev<double> rotU;            // d x d: eigenvectors of a non-diagonal R in its columns (psmf_set_noise_rotation); series, C, y_hat are kept rotated
+  Dev<void> rot_tmp;           // staging of a rotation (the GEMM is out of place); grows on demand
   // masked filter (cfg.masked, psmf_masked.hip)
-  uint8_t* mask = nullptr;     // T_cap x d_local observation mask (psmf_upload_mask)
-  uint8_t* mmiss = nullptr;    // staging of the held-out mask for psmf_masked_metrics (mmiss_cap bytes)
-  size_t mmiss_cap = 0;
-  double* mg = nullptr;        // r*r + 1: masked Gram and observed count of the current step, summed over workgroups (and ranks)
-  double* sc_hist = nullptr;   // T_cap x 2: (s_k, eta_k) of every step -- the bands are formed from them
+  Dev<uint8_t> mask;           // T_cap x d_local observation mask (psmf_upload_mask)
+  Dev<uint8_t> mmiss;          // staging of the held-out mask for psmf_masked_metrics; grows on demand
+  Dev<double> mg;              // r*r + 1: masked Gram and observed count of the current step, summed over workgroups (and ranks)
+  Dev<double> sc_hist;         // T_cap x 2: (s_k, eta_k) of every step -- the bands are formed from them
   bool have_mask = false;
   int64_t mask_hi = 0;         // resident series: the mask has been uploaded for the series rows [0, mask_hi)
-  double* sched = nullptr;     // rho_k | q_k schedules, sched_n doubles each (psmf_set_schedules)
+  Dev<double> sched;           // rho_k | q_k schedules, sched_n doubles each (psmf_set_schedules)
   int64_t sched_n = 0;
-  double* qmat = nullptr;      // Q_k matrices, (qmat_n + 1) x r x r (psmf_set_q_matrix_schedule)
+  Dev<double> qmat;            // Q_k matrices, (qmat_n + 1) x r x r (psmf_set_q_matrix_schedule)
   int64_t qmat_n = 0;
-  double* mu_hist = nullptr;   // (T_cap + 1) x r
-  hipStream_t fstream = nullptr;   // blocked engine, pipelined: the filter chain's own stream, pinned to reserved CUs (or nullptr)
+  Dev<double> mu_hist;         // (T_cap + 1) x r
+  Stream fstream;                  // blocked engine, pipelined: the filter chain's own stream, pinned to reserved CUs (or empty)
   bool streams_concurrent = false;           // the filter stream's kernels run concurrently with the bulk stream's (probed at creation)
   // HIP-event timing of the chained filter launches (one per run): a ring of event pairs, read out at the next sync
   static constexpr int kTimedRuns = 256;
-  hipEvent_t evK0[kTimedRuns] = {}, evK1[kTimedRuns] = {};
-  hipEvent_t evC = nullptr;        // end of the chained filter launch: orders the handle's main stream (host reads of DevState) after it
+  Event evK0[kTimedRuns], evK1[kTimedRuns];
+  Event evC;                       // end of the chained filter launch: orders the handle's main stream (host reads of DevState) after it
   int evk_pending = 0;
   double kernel_ms_sum = 0.0;
   long long kernel_launches = 0;
   int reserved_cus = 0;
   int bulk_wgs = 256;          // workgroups of the streaming bulk kernels (one per CU of the bulk stream: a 257th would wait for a whole round)
-  double* scratch = nullptr;   // sq-error partials / predict staging
+  Dev<double> scratch;         // sq-error partials / predict staging; grows on demand
   // blocked engine
   int engine = 1;              // 1 per-step, 2 blocked
   int block_steps = 0;         // B = RB - r
   bool q_iso = false;          // Q = q I with q > 0 as last uploaded (two-group block filter applies)
   double q_last = 0.0, p_diag_max = 0.0;      // Q[0][0] and max_i P[i][i] as last uploaded: the give-up policy of the Newton-Schulz starts (update_ns_policy)
-  double* Kpart = nullptr;
-  double* Kmat = nullptr;
-  double* Acoef = nullptr;     // 2 x RB x RM   (ping-pong across pipelined blocks)
-  double* Bcoef = nullptr;     // 2 x RB x RB
-  double* XGpart = nullptr;    // BLK_GRAM_WG x (RB + XGB) x XGB
-  double* XG = nullptr;        // 2 x (RB + XGB) x XGB
-  long long* flags = nullptr;  // device-flag hand-off of the pipelined blocks (psmf_block.hip): xg_seq, filt_seq, abort
+  Dev<double> Kpart, Kmat;
+  Dev<double> Acoef;           // 2 x RB x RM   (ping-pong across pipelined blocks)
+  Dev<double> Bcoef;           // 2 x RB x RB
+  Dev<double> XGpart;          // BLK_GRAM_WG x (RB + XGB) x XGB
+  Dev<double> XG;              // 2 x (RB + XGB) x XGB
+  Dev<long long> flags;        // device-flag hand-off of the pipelined blocks (psmf_block.hip): xg_seq, filt_seq, abort
   long long seq_next = 1;      // sequence number of the next block to be enqueued
-  hipStream_t bulk = nullptr;  // Gram / cross-Gram / apply of the pipelined blocked engine
-  hipEvent_t evF[4] = {}, evA[4] = {}, evX[4] = {}, evS = nullptr;
-  size_t scratch_bytes = 0;
+  Stream bulk;                 // Gram / cross-Gram / apply of the pipelined blocked engine
+  Event evF[4], evA[4], evX[4], evS;
   int64_t T_cap = 0;
   // series ring (psmf_series_ring): the series buffers hold ring_slots windows of ring_chunk rows; chunk c of the stream lives in slot
   // c % ring_slots and is run with sp.series_t0 = (c - slot) * ring_chunk.  ring_slots = 0: the whole series is resident.
   struct RingSlot {
     int64_t chunk = -1;          // chunk of the stream the slot holds (-1: none)
     int64_t rows = 0, mrows = 0; // series / mask rows of it uploaded so far
-    hipEvent_t up = nullptr;     // the last upload into the slot (copy stream)
-    hipEvent_t run = nullptr;    // the last run that touched the slot (compute stream)
+    Event up;                    // the last upload into the slot (copy stream)
+    Event run;                   // the last run that touched the slot (compute stream)
     bool up_set = false, run_set = false;
   };
   int64_t ring_chunk = 0;
   int ring_slots = 0;
   int64_t ring_cur = -1;           // the chunk sp.series_t0 (and the histories' slot base) point at
   std::vector<RingSlot> ring;
-  hipStream_t cstream = nullptr;   // the ring's copy stream: uploads, downloads, row conversion
-  void* ring_stage = nullptr;      // device staging of one chunk in the caller's element type (psmf_cast_rows converts from / into it)
+  Stream cstream;                  // the ring's copy stream: uploads, downloads, row conversion
+  Dev<void> ring_stage;            // device staging of one chunk in the caller's element type (psmf_cast_rows converts from / into it)
   bool ring_mg_stale = false;      // masked: the Gram formed one step ahead read a mask row that was not resident yet
   StepParams sp;
   hipGraph_t graph = nullptr;
@@ -154,8 +151,8 @@ struct psmf_filter {
   // persistent per-step engine (psmf_pstep.hip): geometry of a launch and its communication block (flags | packet | partial rows)
   psmf::PstepPlan ps_plan = {};
   bool ps_ok = false;
-  void* ps_comm = nullptr;
-  long long* ps_prof = nullptr;    // PSMF_PSTEP_PROF=1 with a -DPSTEP_PROF build: per-phase clock sums of the last launch, printed at psmf_destroy
+  Dev<void> ps_comm;
+  Dev<long long> ps_prof;          // PSMF_PSTEP_PROF=1 with a -DPSTEP_PROF build: per-phase clock sums of the last launch, printed at psmf_destroy
   long long ps_prof_steps = 0;
   long long ps_launches = 0;
   bool have_state = false;
@@ -167,11 +164,11 @@ struct psmf_filter {
   // host-mediated collective (psmf_comm_init_host): the sum-all-reduce goes through a caller-supplied function
   psmf_allreduce_fn host_fn = nullptr;
   void* host_ctx = nullptr;
-  double* host_buf = nullptr;      // pinned staging buffer, kHostBufElems doubles
+  Pinned<double> host_buf;         // pinned staging buffer, kHostBufElems doubles
   static constexpr size_t kHostBufElems = 8192;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  int* err_host = nullptr;     // pinned, device-mapped: a one-thread kernel publishes the device error flag here
-  int* err_host_dev = nullptr;
+  Event ev0, ev1;
+  Pinned<int> err_host;        // pinned, device-mapped: a one-thread kernel publishes the device error flag here
+  int* err_host_dev = nullptr; // the device address of err_host
   std::string err;
   size_t elem() const { return cfg.storage == PSMF_F64 ? 8 : 4; }
 };
@@ -183,12 +180,15 @@ int fail(psmf_handle h, int code, const std::string& msg) {
   return code;
 }
 
-#define HIP_TRY(h, expr)                                                                   \
+#define HIP_TRY_AS(h, what, expr)                                                          \
   do {                                                                                     \
     hipError_t e_ = (expr);                                                                \
     if (e_ != hipSuccess)                                                                  \
-      return fail(h, PSMF_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));    \
+      return fail(h, PSMF_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e_));     \
   } while (0)
+#define HIP_TRY(h, expr) HIP_TRY_AS(h, #expr, expr)
+// alloc / reserve of an owning buffer: the message names the HIP call behind them as well
+#define ALLOC_TRY(h, expr) HIP_TRY_AS(h, std::string(kAllocCall) + " in " #expr, expr)
 
 #define NCCL_TRY(h, expr)                                                                  \
   do {                                                                                     \
@@ -253,7 +253,6 @@ int ensure_rot_tmp(psmf_filter* h, size_t bytes);
 int rot_rows(psmf_filter* h, const void* src, void* dst, long long n, bool fwd);
 // psmf_series.hip: the series buffers (resident or a ring), their uploads, downloads and reductions
 int ring_run(psmf_filter* h, int64_t k_begin, int64_t k_end);      // psmf_run on a ring handle
-void ring_destroy(psmf_filter* h);
 int sq_error_sum(psmf_filter* h, hipStream_t stream, int storage, const void* yp, const void* y, size_t n, double* part_d, double* acc);
 int impute_run_large(const psmf_impute_config* cfg, const double* YorgInt, const uint8_t* M, const uint8_t* Mmiss, double* C, double* X,
                      const double* V, const double* P, const double* Q, double rho, double* Epred, double* Efull, double* inside,

@@ -50,7 +50,13 @@ int impute_run_impl(const char* who, const psmf_impute_config* cfg, const double
                     const double* Q, double rho, const double* rho_rows, double* Epred, double* Efull, double* inside,
                     double* Yrec, double* YrecL, double* YrecH, int32_t* status, float* elapsed_ms) {
   using namespace psmf;
-  auto fail = [&](int code, const std::string& msg) { g_create_error = std::string(who) + ": " + msg; return code; };
+  // every message starts with `who`; there is no handle here, and the three-argument form is the one HIP_TRY / ALLOC_TRY call
+  const struct {
+    const char* who;
+    int operator()(int code, const std::string& msg) const { g_create_error = std::string(who) + ": " + msg; return code; }
+    int operator()(psmf_handle, int code, const std::string& msg) const { return (*this)(code, msg); }
+  } fail{who};
+  const psmf_handle w = nullptr;
   if (!cfg || !YorgInt || !M || !Mmiss || !C || !X || !V || !P || !Q || !Epred || !Efull || !inside)
     return fail(PSMF_ERR_ARG, "null argument");
   if (cfg->abi_version != PSMF_ABI_VERSION) return fail(PSMF_ERR_ARG, "ABI version mismatch");
@@ -74,53 +80,43 @@ int impute_run_impl(const char* who, const psmf_impute_config* cfg, const double
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(PSMF_ERR_NO_DEVICE, "no HIP device visible");
   if (cfg->device < 0 || cfg->device >= ndev) return fail(PSMF_ERR_ARG, "bad device ordinal");
 
-#define I_TRY(expr)                                                                          \
-  do {                                                                                       \
-    hipError_t e_ = (expr);                                                                  \
-    if (e_ != hipSuccess) { rc = fail(PSMF_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); goto done; } \
-  } while (0)
-
-  int rc = PSMF_OK;
   const size_t nd = (size_t)n * d, bnd = (size_t)B * nd;
-  double *dRho = nullptr;
-  const void* kern = nullptr;
-  double *dY = nullptr, *dC = nullptr, *dX = nullptr, *dV = nullptr, *dP = nullptr, *dQ = nullptr, *dEp = nullptr,
-         *dEf = nullptr, *dIn = nullptr, *dYr = nullptr, *dYl = nullptr, *dYh = nullptr;
-  uint8_t *dM = nullptr, *dMm = nullptr;
-  int* dErr = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
+  Dev<double> dY, dC, dX, dV, dP, dQ, dEp, dEf, dIn, dYr, dYl, dYh, dRho;
+  Dev<uint8_t> dM, dMm;
+  Dev<int> dErr;
+  Event e0, e1;
   std::vector<int> herr(B, 0);
   ImputeParams ip;
-  I_TRY(hipSetDevice(cfg->device));
-  I_TRY(hipMalloc((void**)&dY, nd * 8));
-  I_TRY(hipMalloc((void**)&dM, bnd));
-  I_TRY(hipMalloc((void**)&dMm, bnd));
-  I_TRY(hipMalloc((void**)&dC, (size_t)B * d * r * 8));
-  I_TRY(hipMalloc((void**)&dX, (size_t)B * n * r * 8));
-  I_TRY(hipMalloc((void**)&dV, r * r * 8));
-  I_TRY(hipMalloc((void**)&dP, r * r * 8));
-  I_TRY(hipMalloc((void**)&dQ, r * r * 8));
-  I_TRY(hipMalloc((void**)&dEp, (size_t)B * cfg->n_iter * 8));
-  I_TRY(hipMalloc((void**)&dEf, (size_t)B * cfg->n_iter * 8));
-  I_TRY(hipMalloc((void**)&dIn, (size_t)B * 8));
-  I_TRY(hipMalloc((void**)&dErr, (size_t)B * 4));
+  HIP_TRY(w, hipSetDevice(cfg->device));
+  ALLOC_TRY(w, dY.alloc(nd * 8));
+  ALLOC_TRY(w, dM.alloc(bnd));
+  ALLOC_TRY(w, dMm.alloc(bnd));
+  ALLOC_TRY(w, dC.alloc((size_t)B * d * r * 8));
+  ALLOC_TRY(w, dX.alloc((size_t)B * n * r * 8));
+  ALLOC_TRY(w, dV.alloc(r * r * 8));
+  ALLOC_TRY(w, dP.alloc(r * r * 8));
+  ALLOC_TRY(w, dQ.alloc(r * r * 8));
+  ALLOC_TRY(w, dEp.alloc((size_t)B * cfg->n_iter * 8));
+  ALLOC_TRY(w, dEf.alloc((size_t)B * cfg->n_iter * 8));
+  ALLOC_TRY(w, dIn.alloc((size_t)B * 8));
+  ALLOC_TRY(w, dErr.alloc((size_t)B * 4));
   if (cfg->want_bands) {
-    I_TRY(hipMalloc((void**)&dYr, bnd * 8));
-    I_TRY(hipMalloc((void**)&dYl, bnd * 8));
-    I_TRY(hipMalloc((void**)&dYh, bnd * 8));
+    ALLOC_TRY(w, dYr.alloc(bnd * 8));
+    ALLOC_TRY(w, dYl.alloc(bnd * 8));
+    ALLOC_TRY(w, dYh.alloc(bnd * 8));
   }
   if (rw) {
-    I_TRY(hipMalloc((void**)&dRho, (size_t)d * 8));
-    I_TRY(hipMemcpy(dRho, rho_rows, (size_t)d * 8, hipMemcpyHostToDevice));
+    ALLOC_TRY(w, dRho.alloc((size_t)d * 8));
+    HIP_TRY(w, hipMemcpy(dRho, rho_rows, (size_t)d * 8, hipMemcpyHostToDevice));
   }
-  I_TRY(hipMemcpy(dY, YorgInt, nd * 8, hipMemcpyHostToDevice));
-  I_TRY(hipMemcpy(dM, M, bnd, hipMemcpyHostToDevice));
-  I_TRY(hipMemcpy(dMm, Mmiss, bnd, hipMemcpyHostToDevice));
-  I_TRY(hipMemcpy(dC, C, (size_t)B * d * r * 8, hipMemcpyHostToDevice));
-  I_TRY(hipMemcpy(dX, X, (size_t)B * n * r * 8, hipMemcpyHostToDevice));
-  I_TRY(hipMemcpy(dV, V, r * r * 8, hipMemcpyHostToDevice));
-  I_TRY(hipMemcpy(dP, P, r * r * 8, hipMemcpyHostToDevice));
-  I_TRY(hipMemcpy(dQ, Q, r * r * 8, hipMemcpyHostToDevice));
+  HIP_TRY(w, hipMemcpy(dY, YorgInt, nd * 8, hipMemcpyHostToDevice));
+  HIP_TRY(w, hipMemcpy(dM, M, bnd, hipMemcpyHostToDevice));
+  HIP_TRY(w, hipMemcpy(dMm, Mmiss, bnd, hipMemcpyHostToDevice));
+  HIP_TRY(w, hipMemcpy(dC, C, (size_t)B * d * r * 8, hipMemcpyHostToDevice));
+  HIP_TRY(w, hipMemcpy(dX, X, (size_t)B * n * r * 8, hipMemcpyHostToDevice));
+  HIP_TRY(w, hipMemcpy(dV, V, r * r * 8, hipMemcpyHostToDevice));
+  HIP_TRY(w, hipMemcpy(dP, P, r * r * 8, hipMemcpyHostToDevice));
+  HIP_TRY(w, hipMemcpy(dQ, Q, r * r * 8, hipMemcpyHostToDevice));
   ip.d = d; ip.n = n; ip.r = r; ip.n_iter = cfg->n_iter; ip.robust = cfg->method == 1; ip.method = cfg->method; ip.want_bands = cfg->want_bands;
   ip.sig = cfg->sig; ip.lambda0 = cfg->lambda0; ip.rho0 = rho;
   ip.Yorg = dY; ip.M = dM; ip.Mmiss = dMm; ip.C = dC; ip.X = dX; ip.V0 = dV; ip.P0 = dP; ip.Q0 = dQ;
@@ -133,50 +129,44 @@ int impute_run_impl(const char* who, const psmf_impute_config* cfg, const double
         if (Q[i * r + c] != (i == c ? Q[0] : 0.0)) { iso = false; break; }
     ip.q_iso = iso ? 1 : 0;
   }
-  kern = v3 ? impute3_kernel(d, rw) : (rw ? (const void*)psmf_impute_kernel2w : (const void*)psmf_impute_kernel2);
-  if (lds > 48 * 1024) I_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  I_TRY(hipEventCreate(&e0));
-  I_TRY(hipEventCreate(&e1));
-  I_TRY(hipEventRecord(e0, 0));
-  { void* args[] = {&ip}; I_TRY(hipLaunchKernel(kern, dim3(B), dim3(WG), args, lds, 0)); }
-  I_TRY(hipGetLastError());
-  I_TRY(hipEventRecord(e1, 0));
-  I_TRY(hipEventSynchronize(e1));
-  if (elapsed_ms) I_TRY(hipEventElapsedTime(elapsed_ms, e0, e1));
-  I_TRY(hipMemcpy(C, dC, (size_t)B * d * r * 8, hipMemcpyDeviceToHost));
-  I_TRY(hipMemcpy(X, dX, (size_t)B * n * r * 8, hipMemcpyDeviceToHost));
-  I_TRY(hipMemcpy(Epred, dEp, (size_t)B * cfg->n_iter * 8, hipMemcpyDeviceToHost));
-  I_TRY(hipMemcpy(Efull, dEf, (size_t)B * cfg->n_iter * 8, hipMemcpyDeviceToHost));
-  I_TRY(hipMemcpy(inside, dIn, (size_t)B * 8, hipMemcpyDeviceToHost));
-  I_TRY(hipMemcpy(herr.data(), dErr, (size_t)B * 4, hipMemcpyDeviceToHost));
+  const void* const kern = v3 ? impute3_kernel(d, rw) : (rw ? (const void*)psmf_impute_kernel2w : (const void*)psmf_impute_kernel2);
+  if (lds > 48 * 1024) HIP_TRY(w, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  HIP_TRY(w, hipEventCreate(e0.put()));
+  HIP_TRY(w, hipEventCreate(e1.put()));
+  HIP_TRY(w, hipEventRecord(e0, 0));
+  { void* args[] = {&ip}; HIP_TRY(w, hipLaunchKernel(kern, dim3(B), dim3(WG), args, lds, 0)); }
+  HIP_TRY(w, hipGetLastError());
+  HIP_TRY(w, hipEventRecord(e1, 0));
+  HIP_TRY(w, hipEventSynchronize(e1));
+  if (elapsed_ms) HIP_TRY(w, hipEventElapsedTime(elapsed_ms, e0, e1));
+  HIP_TRY(w, hipMemcpy(C, dC, (size_t)B * d * r * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(w, hipMemcpy(X, dX, (size_t)B * n * r * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(w, hipMemcpy(Epred, dEp, (size_t)B * cfg->n_iter * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(w, hipMemcpy(Efull, dEf, (size_t)B * cfg->n_iter * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(w, hipMemcpy(inside, dIn, (size_t)B * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(w, hipMemcpy(herr.data(), dErr, (size_t)B * 4, hipMemcpyDeviceToHost));
   if (cfg->want_bands) {
-    I_TRY(hipMemcpy(Yrec, dYr, bnd * 8, hipMemcpyDeviceToHost));
-    I_TRY(hipMemcpy(YrecL, dYl, bnd * 8, hipMemcpyDeviceToHost));
-    I_TRY(hipMemcpy(YrecH, dYh, bnd * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(w, hipMemcpy(Yrec, dYr, bnd * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(w, hipMemcpy(YrecL, dYl, bnd * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(w, hipMemcpy(YrecH, dYh, bnd * 8, hipMemcpyDeviceToHost));
   }
   // Per-replica outcome (the reference records NaN for a diverged repeat and carries on, ExperimentImpute/rPSMF.py:236-243): a
   // replica whose r x r system lost positive definiteness -- or whose errors are not finite -- gets status PSMF_ERR_NUMERIC and NaN
   // results; the other replicas are untouched by it (one workgroup each).  Without a status array the call fails as a whole.
   for (int b = 0; b < B; ++b)
-    if (herr[b] == 9) { rc = fail(PSMF_ERR_HIP, "internal error: the wave programs of the column loop executed different numbers of barriers (imp_barrier_check)"); goto done; }
+    if (herr[b] == 9) return fail(PSMF_ERR_HIP, "internal error: the wave programs of the column loop executed different numbers of barriers (imp_barrier_check)");
   for (int b = 0; b < B; ++b) {
     bool bad = herr[b] != 0;
     for (int it = 0; it < cfg->n_iter && !bad; ++it)
       bad = !std::isfinite(Epred[(size_t)b * cfg->n_iter + it]) || !std::isfinite(Efull[(size_t)b * cfg->n_iter + it]);
     if (status) status[b] = bad ? PSMF_ERR_NUMERIC : PSMF_OK;
     if (!bad) continue;
-    if (!status) { rc = fail(PSMF_ERR_NUMERIC, "singular r x r system in replica " + std::to_string(b)); break; }
+    if (!status) return fail(PSMF_ERR_NUMERIC, "singular r x r system in replica " + std::to_string(b));
     const double qnan = std::numeric_limits<double>::quiet_NaN();
     for (int it = 0; it < cfg->n_iter; ++it) Epred[(size_t)b * cfg->n_iter + it] = Efull[(size_t)b * cfg->n_iter + it] = qnan;
     inside[b] = qnan;
   }
-done:
-  hipFree(dY); hipFree(dM); hipFree(dMm); hipFree(dC); hipFree(dX); hipFree(dV); hipFree(dP); hipFree(dQ);
-  hipFree(dEp); hipFree(dEf); hipFree(dIn); hipFree(dErr); hipFree(dYr); hipFree(dYl); hipFree(dYh); hipFree(dRho);
-  if (e0) hipEventDestroy(e0);
-  if (e1) hipEventDestroy(e1);
-#undef I_TRY
-  return rc;
+  return PSMF_OK;
 }
 }  // namespace
 

@@ -129,10 +129,10 @@ void launch_cast(psmf_filter* h, const TS* src, TD* dst, size_t n, int head) {
 // ring: through the one-chunk device staging buffer, converted by psmf_cast_rows on the copy stream
 int cast_on_device(psmf_filter* h, void* host, void* dev, size_t n, bool upload) {
   const size_t es = h->elem(), hs = 12 - es;
-  if (!h->ring_stage)      // one chunk of float64, and room to shift it to the rows' alignment: only streams of the other type pay for it
-    HIP_TRY(h, hipMalloc(&h->ring_stage, (size_t)h->ring_chunk * h->cfg.d_local * 8 + 16));
+  // one chunk of float64, and room to shift it to the rows' alignment: only streams of the other type pay for it
+  ALLOC_TRY(h, h->ring_stage.reserve((size_t)h->ring_chunk * h->cfg.d_local * 8 + 16));
   const int head = psmf::cast_head(dev, es);
-  char* stage = (char*)h->ring_stage + (size_t)psmf::cast_shift(head, hs) * hs;
+  char* stage = h->ring_stage.as<char>() + (size_t)psmf::cast_shift(head, hs) * hs;
   if (upload) {
     HIP_TRY(h, hipMemcpyAsync(stage, host, n * hs, hipMemcpyHostToDevice, h->cstream));
     if (es == 4) launch_cast(h, (const double*)stage, (float*)dev, n, head);
@@ -179,8 +179,7 @@ int copy_rows(psmf_filter* h, hipStream_t s, void* host, int dtype, void* dev, s
 
 // ---- allocation ----------------------------------------------------------------------------------------------------------------
 void series_free(psmf_filter* h) {
-  for (void** p : {(void**)&h->Y, (void**)&h->YP, (void**)&h->mask, (void**)&h->sc_hist, (void**)&h->mu_hist})
-    if (*p) { (void)hipFree(*p); *p = nullptr; }
+  h->Y.reset(); h->YP.reset(); h->mask.reset(); h->sc_hist.reset(); h->mu_hist.reset();
   h->sp.Y = h->sp.YP = nullptr; h->sp.mask = nullptr; h->sp.sc_hist = nullptr; h->sp.mu_hist = nullptr;
   h->have_mask = false;
   h->mask_hi = 0;
@@ -188,13 +187,13 @@ void series_free(psmf_filter* h) {
 
 // Y, YP, the mask, sc_hist and mu_hist for `rows` series rows, and the StepParams fields that point at them.  What a step touches
 // one row ahead of the series row it reads gets more: the histories (written: the mean of step k in row k, the (s, eta) of the next
-// step) hist_extra rows, the mask (read: the Gram of the next step) mask_extra rows.  (s, eta) start at zero.  On an error the caller
-// frees what exists (series_free).
+// step) hist_extra rows, the mask (read: the Gram of the next step) mask_extra rows.  (s, eta) start at zero.  The one function that
+// sets these fields; on an error the caller clears them again (series_free).
 int series_alloc(psmf_filter* h, size_t rows, size_t hist_extra, size_t mask_extra) {
   const size_t dl = h->cfg.d_local, es = h->elem(), r = h->cfg.r;
   if (h->cfg.masked) {
-    HIP_TRY(h, hipMalloc((void**)&h->mask, (rows + mask_extra) * dl));
-    HIP_TRY(h, hipMalloc((void**)&h->sc_hist, (rows + hist_extra) * 2 * sizeof(double)));
+    ALLOC_TRY(h, h->mask.alloc((rows + mask_extra) * dl));
+    ALLOC_TRY(h, h->sc_hist.alloc((rows + hist_extra) * 2 * sizeof(double)));
     HIP_TRY(h, hipMemsetAsync(h->sc_hist, 0, (rows + hist_extra) * 2 * sizeof(double), h->stream));
     h->sp.mask = h->mask;
     h->sp.mg = h->mg;
@@ -203,9 +202,9 @@ int series_alloc(psmf_filter* h, size_t rows, size_t hist_extra, size_t mask_ext
     h->sp.sc_hist = h->sc_hist;
     h->sp.mask_rows = (int)(rows + mask_extra);
   }
-  HIP_TRY(h, hipMalloc(&h->Y, rows * dl * es));
-  if (h->cfg.store_y_pred) HIP_TRY(h, hipMalloc(&h->YP, rows * dl * es));
-  HIP_TRY(h, hipMalloc((void**)&h->mu_hist, (rows + hist_extra) * r * sizeof(double)));
+  ALLOC_TRY(h, h->Y.alloc(rows * dl * es));
+  if (h->cfg.store_y_pred) ALLOC_TRY(h, h->YP.alloc(rows * dl * es));
+  ALLOC_TRY(h, h->mu_hist.alloc((rows + hist_extra) * r * sizeof(double)));
   h->sp.mu_hist = h->mu_hist;
   h->sp.Y = h->Y;
   h->sp.YP = h->YP;
@@ -229,7 +228,7 @@ int resident_reserve(psmf_filter* h, int64_t t0, int64_t nt, int64_t T_total) {
   return PSMF_OK;
 }
 
-// the buffers, the copy stream and the events of a ring; on an error the caller frees what exists
+// the buffers, the copy stream and the events of a ring; on an error the caller releases what exists (psmf_series_ring)
 int ring_alloc(psmf_filter* h, int64_t chunk, int n_slots) {
   const size_t dl = h->cfg.d_local, rows = (size_t)n_slots * chunk;
   // the mask gets one row behind the last slot, a copy of slot 0's first; the histories chunk + 1 rows per slot (ring_point)
@@ -237,11 +236,11 @@ int ring_alloc(psmf_filter* h, int64_t chunk, int n_slots) {
   if (rc) return rc;
   if (h->mask) HIP_TRY(h, hipMemsetAsync(h->mask, 0, (rows + 1) * dl, h->stream));
   HIP_TRY(h, hipMemsetAsync(h->Y, 0, rows * dl * h->elem(), h->stream));
-  HIP_TRY(h, hipStreamCreateWithFlags(&h->cstream, hipStreamNonBlocking));
-  h->ring.assign((size_t)n_slots, psmf_filter::RingSlot());
+  HIP_TRY(h, hipStreamCreateWithFlags(h->cstream.put(), hipStreamNonBlocking));
+  h->ring = std::vector<psmf_filter::RingSlot>((size_t)n_slots);
   for (auto& s : h->ring) {
-    HIP_TRY(h, hipEventCreateWithFlags(&s.up, hipEventDisableTiming));
-    HIP_TRY(h, hipEventCreateWithFlags(&s.run, hipEventDisableTiming));
+    HIP_TRY(h, hipEventCreateWithFlags(s.up.put(), hipEventDisableTiming));
+    HIP_TRY(h, hipEventCreateWithFlags(s.run.put(), hipEventDisableTiming));
   }
   HIP_TRY(h, hipStreamSynchronize(h->stream));      // the zero-fills
   return PSMF_OK;
@@ -294,7 +293,7 @@ int series_upload(psmf_filter* h, const char* who, const void* src, int dtype, b
   if (rc || sp.pieces.empty()) return rc;
   const SeriesPiece& pc = sp.pieces[0];
   const size_t dl = h->cfg.d_local, es = h->elem(), n = (size_t)nt * dl;
-  char* dst = (char*)h->Y + pc.row * dl * es;
+  char* dst = h->Y.as<char>() + pc.row * dl * es;
   if (mask) {
     HIP_TRY(h, hipMemcpyAsync(h->mask + pc.row * dl, src, n, hipMemcpyHostToDevice, sp.stream));
     // ring: the masked Gram is formed one step ahead: the last step of the last slot reads the row behind it, which is this one
@@ -327,12 +326,7 @@ int series_upload(psmf_filter* h, const char* who, const void* src, int dtype, b
 // the sums of psmf_masked_metrics over the steps t0+1 .. t0+nt, read at t - sp.series_t0, on `stream`; waits for it
 int masked_metrics_rows(psmf_filter* h, const StepParams& sp, hipStream_t stream, const uint8_t* Mmiss, int64_t t0, int64_t nt, double sig, double* out4) {
   const size_t dl = h->cfg.d_local, nb = (size_t)nt * dl;
-  if (h->mmiss_cap < nb) {
-    if (h->mmiss) HIP_TRY(h, hipFree(h->mmiss));
-    h->mmiss = nullptr; h->mmiss_cap = 0;
-    HIP_TRY(h, hipMalloc((void**)&h->mmiss, nb));
-    h->mmiss_cap = nb;
-  }
+  ALLOC_TRY(h, h->mmiss.reserve(nb));
   HIP_TRY(h, hipMemcpy(h->mmiss, Mmiss, nb, hipMemcpyHostToDevice));
   const int gx = (int)((dl + psmf::WG - 1) / psmf::WG);
   int gy = (int)((2048 + gx - 1) / gx);                  // ~2 k workgroups in all
@@ -412,15 +406,6 @@ int ring_run(psmf_filter* h, int64_t k_begin, int64_t k_end) {
   return PSMF_OK;
 }
 
-void ring_destroy(psmf_filter* h) {
-  if (h->cstream) hipStreamSynchronize(h->cstream);
-  for (auto& s : h->ring) { if (s.up) hipEventDestroy(s.up); if (s.run) hipEventDestroy(s.run); }
-  h->ring.clear();
-  if (h->ring_stage) hipFree(h->ring_stage);
-  if (h->cstream) hipStreamDestroy(h->cstream);
-  h->cstream = nullptr; h->ring_stage = nullptr;
-}
-
 extern "C" {
 
 int psmf_upload_series(psmf_handle h, const void* Y, int dtype, int64_t t0, int64_t nt, int64_t T_total) {
@@ -459,7 +444,8 @@ int psmf_series_ring(psmf_handle h, int64_t chunk, int n_slots) {
   rc = ring_alloc(h, chunk, n_slots);
   if (rc) {      // leave the handle as it was: without series buffers, so that the call can be made again
     series_free(h);
-    ring_destroy(h);
+    h->ring.clear();      // (the slots' events)
+    h->cstream.reset();
     return rc;
   }
   h->T_cap = (int64_t)n_slots * chunk;
@@ -489,14 +475,14 @@ int psmf_download_y_pred(psmf_handle h, void* out, int dtype, int64_t t0, int64_
   const size_t dl = h->cfg.d_local, es = h->elem(), hs = dtype == PSMF_F64 ? 8 : 4;
   for (const SeriesPiece& pc : sp.pieces) {
     const size_t n = (size_t)pc.nt * dl;
-    char* src = (char*)h->YP + pc.row * dl * es;
+    char* src = h->YP.as<char>() + pc.row * dl * es;
     if (h->rotU && n) {                    // non-diagonal R: y_hat = U (U^T y_hat) (resident only: a ring refuses the rotation)
       rc = ensure_rot_tmp(h, n * es);
       if (rc) return rc;
       rc = rot_rows(h, src, h->rot_tmp, pc.nt, false);
       if (rc) return rc;
       HIP_TRY(h, hipStreamSynchronize(h->stream));
-      src = (char*)h->rot_tmp;
+      src = h->rot_tmp.as<char>();
     }
     rc = copy_rows(h, sp.stream, (char*)out + (size_t)(pc.t0 - t0) * dl * hs, dtype, src, n, false);
     if (rc) return rc;
@@ -548,7 +534,7 @@ int psmf_sq_error(psmf_handle h, int64_t t0, int64_t nt, double* out) {
   double a = 0.0;
   for (const SeriesPiece& pc : sp.pieces) {
     const size_t off = pc.row * dl * es;
-    rc = sq_error_sum(h, sp.stream, h->cfg.storage, (const char*)h->YP + off, (const char*)h->Y + off, (size_t)pc.nt * dl, h->scratch, &a);
+    rc = sq_error_sum(h, sp.stream, h->cfg.storage, h->YP.as<char>() + off, h->Y.as<char>() + off, (size_t)pc.nt * dl, h->scratch, &a);
     if (rc) return rc;
   }
   *out = a;
