@@ -250,48 +250,106 @@ __device__ __forceinline__ bool f3_chain_next(const BlockParams& b, const F3Lds&
   return blk_chain_next(b, seq);
 }
 
-__device__ __forceinline__ void f3_assemble_K(const BlockParams& b, const F3Blk& k, const F3Lds& L, const int r, const int tid) {
+// What one thread reads of a block's cross-Gram for the K assembly, as ONE group of loads: the upper part (RB x nb, staged in
+// LDS as the B operand of the cross block) and Y^T Y (rows RB + q, the lower right corner of K).  Written as a loop with the
+// LDS store behind each load, the staging compiled to load, s_waitcnt vmcnt(0), ds_write per trip: six dependent L2 round trips.
+constexpr int F3_XS_TRIPS = RB * F3_AS / F3_NT;       // 6
+constexpr int F3_AP_TRIPS = RB * 32 / F3_NT;          // 4
+constexpr int F3_YY_TRIPS = 6;                        // row q = wave + 8 u, column q2 = lane: no division by the run-time nb
+static_assert(F3_XS_TRIPS * F3_NT == RB * F3_AS && F3_AP_TRIPS * F3_NT == RB * 32, "whole trips");
+static_assert(F3_YY_TRIPS * (F3_NT / 64) >= F3_AS && F3_AS <= 64 && F3_AS <= XGB, "Y^T Y of the longest block");
+struct F3XG {
+  double xs[F3_XS_TRIPS], yy[F3_YY_TRIPS];
+};
+__device__ __forceinline__ void f3_xg_fetch(F3XG& x, const double* XG, const int nb, const int tid) {
+#pragma unroll
+  for (int u = 0; u < F3_YY_TRIPS; ++u) {
+    const int q = max(min((tid >> 6) + 8 * u, nb - 1), 0), q2 = max(min(tid & 63, nb - 1), 0);
+    x.yy[u] = xg_load(XG + (size_t)(RB + q) * XGB + q2);
+  }
+#pragma unroll
+  for (int u = 0; u < F3_XS_TRIPS; ++u) {
+    const int idx = tid + u * F3_NT, m = idx / F3_AS, q = idx - m * F3_AS;
+    x.xs[u] = xg_load(XG + (size_t)m * XGB + max(min(q, nb - 1), 0));
+  }
+}
+__device__ __forceinline__ void f3_xg_stage(const F3XG& x, double* sX, const int nb, const int tid) {
+#pragma unroll
+  for (int u = 0; u < F3_XS_TRIPS; ++u) {
+    const int idx = tid + u * F3_NT, m = idx / F3_AS, q = idx - m * F3_AS;
+    sX[m * F3_AS + q] = q < nb ? x.xs[u] : 0.0;
+  }
+}
+__device__ __forceinline__ void f3_xg_corner(const F3XG& x, double* sK, const int r, const int nb, const int tid) {
+#pragma unroll
+  for (int u = 0; u < F3_YY_TRIPS; ++u) {
+    const int q = (tid >> 6) + 8 * u, q2 = tid & 63;
+    if (q < nb && q2 < nb) sK[(r + q) * RB + r + q2] = x.yy[u];
+  }
+}
+
+// Chain carry, fast hand-off (BlockParams::xg_ahead, PSMF_XG_AHEAD): the next block's group of cross-Gram loads is issued in FRONT
+// of the hand-off's store drain, so its L2 round trip is the one f3_chain_next's s_waitcnt vmcnt(0) waits for anyway, not a second one
+// behind the barrier.  The upper part goes straight into sX -- nothing in a filter3 block touches L.sKA between two assemblies --
+// and f3_chain_next's barrier orders it for the cross block's MFMAs; Y^T Y stays in registers across that barrier (sK is still
+// being read by waves that have not arrived).  Memory order: wave 6 observed the announcement with an agent-scope load and handed
+// it on through L.hand[1] and the barriers of the block end; the agent-scope data loads here are issued after that -- the order
+// f3_chain_next's "yes" already relies on, only earlier.  A "yes" here is the same word f3_chain_next reads, so it takes the fast
+// path too.  Anything else fetches nothing: the assembly loads behind blk_chain_next's wait as before.
+__device__ __forceinline__ bool f3_xg_ahead(const F3Blk& k, const F3Lds& L, F3XG& x, const int tid) {
+  if (__builtin_amdgcn_readfirstlane((int)L.hand[1]) == 0) return false;
+  f3_xg_fetch(x, k.XG, k.nb, tid);
+  f3_xg_stage(x, L.sKA, k.nb, tid);
+  return true;
+}
+
+// ahead (f3_xg_ahead): x was fetched, and its upper part staged in sX, in front of the hand-off's barrier
+__device__ __forceinline__ void f3_assemble_K(const BlockParams& b, const F3Blk& k, const F3Lds& L, const int r, const int tid, F3XG& x,
+                                              const bool ahead) {
   const int nb = k.nb, lane = tid & 63, w = tid >> 6, lrow = lane >> 4, lcol = lane & 15;
   double* sK = L.sK;
   double* sA = L.sA;
   double* sX = L.sA + RB * F3_AS;
   const DevState* st = b.sp.st;
   // every global load of the assembly is issued before the first barrier (one L2 round trip, not two)
-  double gv[2], yy[5];
+  // (every address is clamped into the block and the value discarded where it is not wanted: the loads are unconditional, the
+  //  trip counts compile-time constants, and nothing waits on vmcnt between the first load and the last)
+  double gv[2];
 #pragma unroll
   for (int u = 0; u < 2; ++u)                                                  // tracked G of the previous block (T-layout dump: an
     gv[u] = k.from_lds ? f3_carry(L).G[(w + 8 * u) * 64 + lane]                // assembled block always follows a filter3 block);
                        : st->f3_G[(w + 8 * u) * 64 + lane];                    // chain carry: where wave 0 parked it
+  if (!ahead) f3_xg_fetch(x, k.XG, nb, tid);
+  double ap[F3_AP_TRIPS];
+  if (k.Aprev) {              // (chained blocks: the previous block left its coefficients in sA)
 #pragma unroll
-  for (int u = 0; u < 5; ++u) {
-    const int idx = min(tid + u * F3_NT, nb * nb - 1), q = idx / nb, q2 = idx - q * nb;
-    yy[u] = xg_load(k.XG + (size_t)(RB + q) * XGB + q2);
+    for (int u = 0; u < F3_AP_TRIPS; ++u) {
+      const int idx = tid + u * F3_NT, m = idx >> 5, c = idx & 31;
+      ap[u] = k.Aprev[m * r + min(c, r - 1)];
+    }
   }
   if (r + nb < RB)            // a full block writes every entry of K below
     for (int idx = tid; idx < RB * RB; idx += F3_NT) sK[idx] = 0.0;
-  if (k.Aprev)                // (chained blocks: the previous block left its coefficients in sA)
-    for (int idx = tid; idx < RB * 32; idx += F3_NT) {
-      const int m = idx >> 5, c = idx & 31;
-      const double v = k.Aprev[m * r + min(c, r - 1)];
-      sA[m * F3_AS + c] = c < r ? v : 0.0;
+  if (k.Aprev) {
+#pragma unroll
+    for (int u = 0; u < F3_AP_TRIPS; ++u) {
+      const int idx = tid + u * F3_NT, m = idx >> 5, c = idx & 31;
+      sA[m * F3_AS + c] = c < r ? ap[u] : 0.0;
     }
-  for (int idx = tid; idx < RB * F3_AS; idx += F3_NT) {
-    const int m = idx / F3_AS, q = idx - m * F3_AS;
-    const double v = xg_load(k.XG + (size_t)m * XGB + min(q, nb - 1));
-    sX[m * F3_AS + q] = q < nb ? v : 0.0;
   }
-  __syncthreads();
+  if (!ahead) {
+    f3_xg_stage(x, sX, nb, tid);
+    __syncthreads();
+  } else if (r + nb < RB) {
+    f3_barrier();             // the zeroes | the corners.  (sA and sX were complete at the hand-off's barrier.)
+  }
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
     const int e = w + 8 * u;
     const int row = 16 * (e >> 3) + lrow + 4 * (e & 3), col = 16 * ((e >> 2) & 1) + lcol;
     if (row < r && col < r) sK[row * RB + col] = gv[u];
   }
-#pragma unroll
-  for (int u = 0; u < 5; ++u) {
-    const int idx = tid + u * F3_NT;
-    if (idx < nb * nb) { const int q = idx / nb, q2 = idx - q * nb; sK[(r + q) * RB + r + q2] = yy[u]; }
-  }
+  f3_xg_corner(x, sK, r, nb, tid);
   const int nct = (nb + 15) >> 4;
   if (w < 2 * nct) {
     const int ti = w & 1, ct = w >> 1;

@@ -102,7 +102,10 @@ __device__ __forceinline__ void blk_filter3_body(const BlockParams& b0) {
     }
   }
   const long long t_begin = (long long)__builtin_amdgcn_s_memrealtime();      // 100 MHz: in-situ duration / gap diagnostics
+  F3XG xg = {};     // (defined on every path: nothing of it crosses the chain loop)
+  bool ahead = false;
   if (j > 0) {
+    if (carry && b0.xg_ahead) ahead = f3_xg_ahead(k, L, xg, tid);
     if (!(carry ? f3_chain_next(b0, L, seq) : blk_chain_next(b0, seq))) {
       if (k.from_lds) f3_carry_flush(b0, L, k.k0, tid);                // the blocks completed, as they would have left DevState
       if (tid == 0) f3_acc_flush(st, L.acc);
@@ -129,7 +132,7 @@ __device__ __forceinline__ void blk_filter3_body(const BlockParams& b0) {
   if (!assemble) {
     for (int idx = tid; idx < RB * RB; idx += F3_NT) L.sK[idx] = b.K[idx];
   } else {
-    f3_assemble_K(b, k, L, r, tid);
+    f3_assemble_K(b, k, L, r, tid, xg, ahead);
   }
   if (tid == 0) { *L.errflag = 0; L.hand[0] = seq + 1; L.hand[1] = 0; L.acc[F3A_BLK] = 0; L.acc[F3A_BLK + 1] = 0; L.acc[F3A_BLK + 2] = 0; L.acc[F3A_BLK + 3] = 0; }
   // filter4, a block that follows another one in the same launch: h, w, ee, N, kappa and (a, b) of that block's last step stay

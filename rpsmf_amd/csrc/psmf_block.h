@@ -59,6 +59,7 @@ struct BlockParams {
   double* Bcoef0;         // 2 x RB x RB
   const double* XG0;      // 2 x (RB + XGB) x XGB
   int carry;              // filter3, chain > 1: blocks hand the r x r state on in LDS; DevState gets it when the launch ends (PSMF_CHAIN_CARRY)
+  int xg_ahead;           // filter3, carry: a fast hand-off fetches the next block's cross-Gram in front of its store drain (PSMF_XG_AHEAD)
   int dual6;              // psmf_blk_filter6: random walk, Q = q I, full filter, no schedules -> the two inversions of a step side by side
 };
 

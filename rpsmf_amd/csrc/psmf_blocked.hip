@@ -229,6 +229,7 @@ int enqueue_blocks_pipelined(psmf_filter* h, int64_t k_begin, int64_t k_end) {
     c.chain_B = B;
     c.chain_kend = k_end;
     c.carry = h->sw.chain_carry ? 1 : 0;
+    c.xg_ahead = h->sw.xg_ahead ? 1 : 0;
     c.Acoef0 = h->Acoef;
     c.Bcoef0 = h->Bcoef;
     c.XG0 = h->XG;

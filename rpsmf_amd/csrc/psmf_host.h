@@ -45,6 +45,7 @@ struct Switches {
   bool block_pipe = !off("PSMF_BLOCK_PIPE");             // =0: blocks one after the other
   bool block_chain = !off("PSMF_BLOCK_CHAIN");           // =0: one filter launch per block
   bool chain_carry = !off("PSMF_CHAIN_CARRY");           // =0: the blocks of a chained filter3 launch hand the r x r state on through DevState
+  bool xg_ahead = !off("PSMF_XG_AHEAD");                 // =0: a carried block loads its cross-Gram behind the hand-off's barrier, not in front of the store drain
   bool block_flags = !off("PSMF_BLOCK_FLAGS");           // =0: event hand-off instead of device flags
   int reserved_cus = as_int("PSMF_RESERVED_CUS", 8);     // CUs that the filter chain's stream owns
   int bulk_wgs_env = as_int("PSMF_BULK_WGS", 0);         // workgroups of the streaming bulk kernels (8..256, rounded down to a multiple of 8 where it is used)

@@ -6,8 +6,11 @@ the device assembly of the filter3 family's translation unit -- the recipe of pr
 
 A step loop = a back-edge range (label ... branch back to it) that holds the 10 s_barrier of one step (up to 12 where a tail was
 duplicated) and does not lie inside another such range; ranges that overlap (a rotated loop) count once.  The chain loop = the
-smallest back-edge range that holds every step loop.  .private_segment_fixed_size = scratch bytes per lane."""
+smallest back-edge range that holds every step loop.  .private_segment_fixed_size = scratch bytes per lane.
+digest = the first 16 hex digits of the SHA-256 of a step loop's instructions (comments, directives and label definitions dropped,
+label operands replaced by one word): two builds whose digests agree run the same instructions on the same registers there."""
 
+import hashlib
 import re
 import sys
 
@@ -40,6 +43,16 @@ def metadata(text, mangled):
 
 def count(lines, lo, hi, pat):
     return sum(1 for ln in lines[lo:hi + 1] if re.match(r"\s+" + pat, ln))
+
+
+def digest(lines, lo, hi):
+    body = []
+    for ln in lines[lo:hi + 1]:
+        ln = re.sub(r"\s*;.*$", "", ln).strip()
+        if not ln or ln.startswith(".") or ln.endswith(":"):
+            continue
+        body.append(re.sub(r"\.LBB\d+_\d+", "L", ln))
+    return hashlib.sha256("\n".join(body).encode()).hexdigest()[:16], len(body)
 
 
 def main():
@@ -80,8 +93,9 @@ def main():
             f64, f32 = count(lines, lo, hi, "v_mfma_f64"), count(lines, lo, hi, "v_mfma_f32")
             sl, ss = count(lines, lo, hi, "scratch_load"), count(lines, lo, hi, "scratch_store")
             tl, ts = tl + sl, ts + ss
+            dg, ni = digest(lines, lo, hi)
             print(f"  step loop {n} ({'inversion' if f64 else 'vector'} waves): lines [{lo - a},{hi - a}], s_barrier {count(lines, lo, hi, 's_barrier')}, "
-                  f"v_mfma_f64 {f64}, v_mfma_f32 {f32}, scratch_load {sl}, scratch_store {ss}")
+                  f"v_mfma_f64 {f64}, v_mfma_f32 {f32}, scratch_load {sl}, scratch_store {ss}, instructions {ni}, digest {dg}")
         print(f"  inside the {len(loops)} step loops: scratch_load {tl}, scratch_store {ts}")
 
 
