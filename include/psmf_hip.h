@@ -91,12 +91,16 @@ typedef struct {
   int32_t dyn_flags;     /* see psmf_dyn_kind                                                  */
   int32_t dyn_terms;     /* PSMF_DYN_FOURIER: N                                                */
   int32_t nonuniform_R;  /* 1: R = rho * diag(rho_rows) with per-row values uploaded by psmf_set_row_noise
-                            (psmf.py:140-153 takes any diagonal R); per-step engine, weighted Gram every step */
+                            (psmf.py:140-153 takes any diagonal R); per-step engine, weighted Gram every step.  With masked =
+                            1 / 2: the masked filters' diagonal R read row by row (ExperimentImpute/PSMF.py:70-72, rPSMF.py:91-98,
+                            MLESMF.py:70-76), weights m_i / (rho rho_i + s) (MLE-SMF: m_i / (rho rho_i)) -- one masked weighted
+                            Gram pass more per step; not with masked = 3 (TMF ignores R) */
   int32_t masked;        /* 1: every step has a 0/1 observation mask over the rows (psmf_upload_mask): the masked filter of
                             ExperimentImpute/PSMF.py:59-84, rPSMF.py:75-135 -- e = m o (y - y_hat), rows with m_i = 0 not
                             updated, Gram / innovation covariance over the observed rows only, eta and lambda with d (not the
                             observed count), y_hat stored unmasked.  Per-step engine, one masked Gram pass per step; needs the
-                            full filter (coef_update, eta_full, pbar_predict = 1), uniform R, store_y_pred = 1.
+                            full filter (coef_update, eta_full, pbar_predict = 1) and store_y_pred = 1; R = rho I, or any
+                            diagonal R with nonuniform_R = 1 (masked = 1 / 2; psmf_set_row_noise before the first run).
                             2 / 3: the baseline filters that share these contractions -- 2 = MLE-SMF (MLESMF.py:57-88: weights m_i / rho,
                             C += gam / eta (m o e) x_p^T, bands -+ sig sqrt(eta)), 3 = TMF (TMF.py:47-66: Pbar = I / nu with Q = I / nu and
                             P = 0 from the caller, kappa = 1, C += gam (m o e) x_p^T); gam from psmf_set_step_size */
@@ -145,7 +149,8 @@ int psmf_set_q_matrix_schedule(psmf_handle h, const double* Q_k, int64_t n);
 
 /* Non-uniform diagonal R (cfg.nonuniform_R = 1): rho_rows[d_local] = diag(R) of this handle's rows, rho_mean = sum of diag(R)
  * over ALL rows / d (tr(R) / d of psmf.py:121-125; the same value on every shard).  The `rho` of psmf_set_state is then the
- * scalar in front (1 to start with; rPSMF multiplies it by omega_k, rpsmf.py:169). */
+ * scalar in front (1 to start with; rPSMF multiplies it by omega_k, rpsmf.py:169).  Masked handles (masked = 1 / 2) take it the
+ * same way: eta of a step is then (rho sum_i m_i rho_i + <G_m, Pbar>) / d, the reference's trace(M R M + C_M Pbar C_M^T) / d. */
 int psmf_set_row_noise(psmf_handle h, const double* rho_rows, double rho_mean);
 
 /* A NON-DIAGONAL R (the dense d x d branch of psmf.py:150-152, rpsmf.py:150-152), cfg.nonuniform_R = 1, one shard (d_local = d):
@@ -157,7 +162,8 @@ int psmf_set_row_noise(psmf_handle h, const double* rho_rows, double rho_mean);
  * way out (float64 GEMMs against the resident U on the matrix cores) -- callers see original coordinates everywhere; no d x d
  * inverse is formed and a step stays O(d r^2).  Call it before the first psmf_set_state / psmf_upload_series.  U stays resident:
  * 8 d^2 bytes, d <= PSMF_ROTATION_DMAX (PSMF_ERR_ARG beyond).  Orthonormality of U is checked over the whole matrix in O(d^2)
- * (U^T U z = z for two sign vectors z): PSMF_ERR_ARG if it fails. */
+ * (U^T U z = z for two sign vectors z): PSMF_ERR_ARG if it fails.  Not on a masked handle: the mask selects rows of the original
+ * coordinates and is not equivariant under the rotation (PSMF_ERR_STATE). */
 int psmf_set_noise_rotation(psmf_handle h, const double* U, const double* lam);
 
 /* ---- series ---------------------------------------------------------------------------- */

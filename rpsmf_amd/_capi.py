@@ -341,7 +341,9 @@ class DeviceFilter:
         return launched
 
     def upload_mask(self, M, t0=0):
-        """Observation mask of the steps t0+1 .. t0+nt (masked handles): (nt, d_local), nonzero = observed."""
+        """Observation mask of the steps t0+1 .. t0+nt (masked handles): (nt, d_local), nonzero = observed.  With nonuniform_R the
+        mask row of a step is read twice: a step ahead by the unweighted masked Gram (as on every masked handle) and by the masked
+        weighted Gram in front of the step's own sweep."""
         M = np.ascontiguousarray(np.asarray(M) != 0, dtype=np.uint8)
         if M.ndim != 2 or M.shape[1] != self.d_local:
             raise ValueError(f"mask must be (T, {self.d_local}) time-major, got {M.shape}")
@@ -368,7 +370,10 @@ class DeviceFilter:
         return out
 
     def set_row_noise(self, rho_rows, rho_mean=None):
-        """diag(R) of this handle's rows (nonuniform_R handles); rho_mean = sum(diag R) over ALL rows / d (default: these rows')"""
+        """diag(R) of this handle's rows (nonuniform_R handles); rho_mean = sum(diag R) over ALL rows / d (default: these rows').
+        Masked handles (masked = 1 / 2: PSMF, rPSMF, MLE-SMF) take it too, at any d and r: the weights of a step become
+        m_i / (rho rho_i + s) (MLE-SMF: m_i / (rho rho_i)), `rho` of set_state the scalar in front (1 to start with).  Before the
+        first run."""
         rho_rows = _f64(rho_rows, (self.d_local,))
         if rho_mean is None:
             rho_mean = float(rho_rows.sum()) / self.d

@@ -110,7 +110,10 @@ int enqueue_weighted_gram(psmf_filter* h);
 int enqueue_serial_mgram(psmf_filter* h, int first);
 
 int enqueue_step(psmf_filter* h) {
-  if (h->sp.rho_rows && h->cfg.coef_update) {      // non-uniform diagonal R: this step's weighted Gram, before the sweep rewrites C
+  // non-uniform diagonal R: this step's weighted Gram, before the sweep rewrites C.  On a masked handle it is the masked weighted
+  // Gram of step k (mask row st->k, s_k from the serial stage of step k - 1): the sweep's block 0 solves with it, and the serial
+  // stage of step k then runs beside the UNWEIGHTED masked Gram of step k + 1 as on every masked handle
+  if (h->sp.rho_rows && h->cfg.coef_update) {
     const int rc = enqueue_weighted_gram(h);
     if (rc) return rc;
   }
@@ -186,21 +189,25 @@ int enqueue_serial_mgram(psmf_filter* h, int first) {
 
 int enqueue_gram(psmf_filter* h) { return enqueue_gram_into(h, h->st->G, nullptr, nullptr); }
 
-// the weighted Gram of the current step (non-uniform diagonal R) on the matrix cores: psmf_wgram_mfma + the masked Gram's reduction
+// the weighted Gram of the current step (non-uniform diagonal R) on the matrix cores: psmf_wgram_mfma -- on a masked handle
+// psmf_mwgram_mfma, the masked weighted Gram -- + the masked Gram's reduction
 typedef LdsKernel<void (*)(StepParams, double*)> wgram_t;
 template <typename T, int NT>
-wgram_t wgram_inst() { return {psmf::psmf_wgram_mfma<T, NT, 8>, 8 * 64, (size_t)psmf::mgram_lds_doubles(NT, 8) * sizeof(double)}; }
+wgram_t wgram_inst(bool masked) {
+  return {masked ? psmf::psmf_mwgram_mfma<T, NT, 8> : psmf::psmf_wgram_mfma<T, NT, 8>, 8 * 64, (size_t)psmf::mgram_lds_doubles(NT, 8) * sizeof(double)};
+}
 
 template <typename T>
-wgram_t wgram_for(int rpad, int r) {
-  if (rpad <= 16) return wgram_inst<T, 1>();
-  if (rpad == 32) return wgram_inst<T, 2>();
-  return r <= 48 ? wgram_inst<T, 3>() : wgram_inst<T, 4>();
+wgram_t wgram_for(int rpad, int r, bool masked) {
+  if (rpad <= 16) return wgram_inst<T, 1>(masked);
+  if (rpad == 32) return wgram_inst<T, 2>(masked);
+  return r <= 48 ? wgram_inst<T, 3>(masked) : wgram_inst<T, 4>(masked);
 }
-wgram_t wgram_kernel(const psmf_filter* h) { return by_storage(h, [&](auto t) { return wgram_for<decltype(t)>(h->geo.rpad, h->cfg.r); }); }
+wgram_t wgram_kernel(const psmf_filter* h) { return by_storage(h, [&](auto t) { return wgram_for<decltype(t)>(h->geo.rpad, h->cfg.r, h->cfg.masked != 0); }); }
 
 int enqueue_weighted_gram(psmf_filter* h) {
-  if (!h->sw.wgram_mfma) return enqueue_gram_into(h, h->st->GR, h->st, h->sp.rho_rows);      // PSMF_WGRAM_MFMA=0: the vector-unit Gram
+  // PSMF_WGRAM_MFMA=0: the vector-unit Gram (it knows no mask: psmf_create refuses the switch on a masked handle)
+  if (!h->sw.wgram_mfma) return enqueue_gram_into(h, h->st->GR, h->st, h->sp.rho_rows);
   const int r = h->cfg.r;
   const wgram_t k = wgram_kernel(h);
   hipLaunchKernelGGL(k.fn, dim3(kMGramWG), dim3(k.threads), k.lds, h->stream, h->sp, h->gpart);
@@ -452,9 +459,9 @@ const char* check_config(const psmf_config* cfg) {
   if (cfg->masked >= 2 && (cfg->robust || cfg->dyn_kind != PSMF_DYN_RANDOM_WALK)) return "psmf_create: masked = 2 (MLE-SMF) / 3 (TMF) are random-walk, non-robust filters";
   if (cfg->masked) {
     if (cfg->dyn_kind != PSMF_DYN_RANDOM_WALK) return "psmf_create: masked handles are random-walk filters (ExperimentImpute/PSMF.py:65-66: Pbar = P + Q)";
-    if (!cfg->coef_update || !cfg->eta_full || !cfg->pbar_predict || cfg->nonuniform_R || cfg->engine == 2 || !cfg->store_y_pred)
-      return "psmf_create: masked = 1 needs the full filter (coef_update, eta_full, pbar_predict), a uniform diagonal R, "
-             "store_y_pred = 1 and the per-step engine";
+    if (!cfg->coef_update || !cfg->eta_full || !cfg->pbar_predict || cfg->engine == 2 || !cfg->store_y_pred)
+      return "psmf_create: masked handles need the full filter (coef_update, eta_full, pbar_predict), store_y_pred = 1 and the per-step engine";
+    if (cfg->masked == 3 && cfg->nonuniform_R) return "psmf_create: masked = 3 (TMF) ignores R (TMF.py:47-66): not with nonuniform_R = 1";
   }
   return nullptr;
 }
@@ -602,6 +609,9 @@ int psmf_create(psmf_handle* out, const psmf_config* cfg) {
   compute_geometry(h->cfg, h->geo, h->sw.sweep_threads);
   auto bail = [&](int code) { g_create_error = h->err; psmf_destroy(h); return code; };
   int rc = choose_engine(h);
+  if (!rc && cfg->masked && cfg->nonuniform_R && !h->sw.wgram_mfma)
+    rc = fail(h, PSMF_ERR_ARG, "psmf_create: PSMF_WGRAM_MFMA=0 selects the vector-unit weighted Gram, which has no masked form: "
+                               "not on a masked handle with nonuniform_R = 1");
   if (!rc) rc = alloc_common(h);
   if (!rc && h->engine == 2) rc = init_blocked(h);
   // dynamic LDS beyond the default limit: opted in here, per handle and so on the handle's device, for the kernels it can launch
@@ -1210,7 +1220,7 @@ int psmf_set_row_noise(psmf_handle h, const double* rho_rows, double rho_mean) {
 int psmf_set_noise_rotation(psmf_handle h, const double* U, const double* lam) {
   if (!h || !U || !lam) return fail(h, PSMF_ERR_ARG, "psmf_set_noise_rotation: bad argument");
   if (!h->cfg.nonuniform_R) return fail(h, PSMF_ERR_STATE, "psmf_set_noise_rotation: the handle was created with nonuniform_R = 0");
-  if (h->cfg.masked) return fail(h, PSMF_ERR_STATE, "psmf_set_noise_rotation: a masked handle filters per row of the ORIGINAL coordinates; not with a rotation");
+  if (h->cfg.masked) return fail(h, PSMF_ERR_STATE, "psmf_set_noise_rotation: not on a masked handle (the mask selects rows of the ORIGINAL coordinates: it is not equivariant under a rotation)");
   if (h->use_coll || h->cfg.d_local != h->cfg.d)
     return fail(h, PSMF_ERR_STATE, "psmf_set_noise_rotation: a non-diagonal R couples all rows: one shard only (d_local = d, no communicator)");
   if (h->ring_slots) return fail(h, PSMF_ERR_STATE, std::string("psmf_set_noise_rotation") + kRingRefused + ": the rotation of the rows would have to run on the copy stream");

@@ -255,7 +255,7 @@ __global__ __launch_bounds__(NT) void psmf_sweep_solve(StepParams p) {
   // non-uniform diagonal R: also the weighted sums b = sum_i kappa_i c_i e_i, q = sum_i kappa_i e_i^2, kappa_i = 1 / (rho_i + s)
   // (psmf.py:140-159 with a diagonal R: SURVEY App. A); rows of partials then hold 2 (r + 1) values
   const double* __restrict__ rrow = p.rho_rows;
-  const double rsc = st->rho, sk = st->s;
+  const double rsc = st->rho, sk = p.masked_method ? 0.0 : st->s;      // (MLE-SMF weighs with m_i / (rho rho_i): MLESMF.py:70-76)
   double hacc2[VEC];
 #pragma unroll
   for (int v = 0; v < VEC; ++v) hacc2[v] = 0.0;

@@ -6,6 +6,10 @@
 //                                                nor time-blocking apply: one masked Gram pass per step (mgram_body)
 //   eta   = (rho n_obs + <G_m, P_bar>) / d       divided by d, NOT by the observed count (PSMF.py:77)
 //   kappa_i = m_i / (rho + s)                    =>  P+ = (P_bar^-1 + kappa G_m)^-1,  b = kappa h,  q = kappa ee  (uniform rho)
+//   any diagonal R = rho diag(rho_i) (cfg.nonuniform_R, PSMF.py:70-72, rPSMF.py:91-98): kappa_i = m_i / (rho rho_i + s),
+//                                                P+ = (P_bar^-1 + G_kappa)^-1 with G_kappa = sum_i kappa_i c_i c_i^T -- masked AND weighted,
+//                                                new with every step twice over (the mask, s): one more Gram pass (mgram_body MODE 2);
+//                                                b = sum kappa_i c_i e_i, q = sum kappa_i e_i^2 from the sweep; eta = (rho sum m_i rho_i + <G_m, P_bar>) / d
 //   lambda <- lambda + d                         (d again, rPSMF.py:135)
 //   bands : PSMF  y_hat -+ sig sqrt(N)  (PSMF.py:83-84);  rPSMF  y_hat_i -+ sig sqrt(s m_i + eta)  (rPSMF.py:112,121-123)
 // and, sharing these contractions (StepParams.masked_method), the two baseline filters of the imputation tables: MLE-SMF (weights
@@ -15,7 +19,10 @@
 // A step is: psmf_sweep_solve with the mask -- every workgroup first forms eta, N, the update direction from the step's reduced Gram
 // (masked_prep_block, psmf_kernels.hip; block 0 publishes them and the step's (s, eta) for the bands) -- (-> all-reduce of r + 1
 // doubles) -> psmf_serial_mgram: the serial stage of the step in block 0 and, beside it, the masked Gram of the NEXT step in the other
-// blocks -> psmf_mgram_reduce (-> all-reduce of r^2 + 1 doubles).  The metrics of a pass (RMSE of the predictions and of C X over the held-out entries, coverage of the bands:
+// blocks -> psmf_mgram_reduce (-> all-reduce of r^2 + 1 doubles).  With per-row noise the step starts with psmf_mwgram_mfma, the masked
+// weighted Gram of the step itself (s of the step is known only once the serial stage of the step before has run, so it cannot be
+// formed ahead) -> psmf_mgram_reduce into st->GR (-> all-reduce of r^2 doubles); the sweep's block 0 solves with it, and the scalar
+// kappa that masked_prep_block publishes is no row weight there: nothing reads it as one.  The metrics of a pass (RMSE of the predictions and of C X over the held-out entries, coverage of the bands:
 // ExperimentImpute/common.py:79-94) are reduced on the device by psmf_masked_metrics_k (psmf_series_kernels.hip); nothing d x n travels.
 #pragma once
 #include "psmf_kernels.hip"
@@ -40,6 +47,12 @@ __host__ __device__ constexpr int mgram_lds_doubles(int nt, int nw) {
 // MODE 1 (round 5): the WEIGHTED Gram of a non-uniform diagonal R, sum_i kappa_i c_i c_i^T with kappa_i = 1 / (rho rho_i + s) of the
 // current step (psmf.py:140-152 with a diagonal R) -- the same slabs, every row scaled by sqrt(kappa_i) as it is
 // stored, so that one image still serves both operands; partial rows of r * r doubles (no count).
+// MODE 2: the MASKED weighted Gram of a masked handle with a non-uniform diagonal R, sum_i m_i c_i c_i^T / (rho rho_i + s) of the
+// CURRENT step (ExperimentImpute/PSMF.py:70-72, rPSMF.py:91-98; MLE-SMF, masked_method 2: m_i / (rho rho_i), MLESMF.py:70-76) -- it
+// runs in front of the sweep, so its mask row is the one of st->k (MODE 0 beside the serial stage reads st->kq); rows scaled by
+// sqrt(kappa_i) as in MODE 1, rows with m_i = 0 stored as zeros as in MODE 0; partial rows of r * r doubles.
+// MODE 0 on such a handle (p.rho_rows set): the count slot holds sum m_i rho_i instead of sum m_i, so that masked_prep_block's
+// eta = (rho slot + <G_m, Pbar>) / d is the reference's trace(M R M + C_M Pbar C_M^T) / d; the Gram itself is the same.
 template <typename T, int NT, int NW, int MODE = 0>
 __device__ __forceinline__ void mgram_body(const StepParams& p, double* __restrict__ gpart, const int bid, const int nblk, double* sZ) {
   constexpr int S = mgram_stride(NT);
@@ -49,12 +62,14 @@ __device__ __forceinline__ void mgram_body(const StepParams& p, double* __restri
   const int r = p.r, rp = p.rp, dl = p.d_local;
   const T* __restrict__ C = reinterpret_cast<const T*>(p.C);
   // the step whose Gram this is: st->kq (written by the previous kernel; the serial stage running beside these blocks advances
-  // st->k, not kq); clamped: the Gram "of the step after the last" is computed and never used
-  long long trow = p.st->kq - p.series_t0;
+  // st->k, not kq); clamped: the Gram "of the step after the last" is computed and never used.  MODE 2 runs in front of the sweep
+  // of the step it belongs to: st->k
+  long long trow = (MODE == 2 ? p.st->k : p.st->kq) - p.series_t0;
   if (trow > (long long)p.mask_rows - 1) trow = (long long)p.mask_rows - 1;
-  const uint8_t* __restrict__ mk = MODE == 0 ? p.mask + (size_t)trow * dl : nullptr;
+  const uint8_t* __restrict__ mk = MODE != 1 ? p.mask + (size_t)trow * dl : nullptr;
   const double* __restrict__ rrow = p.rho_rows;
-  const double rsc = p.st->rho, sk = p.st->s;
+  const bool wcnt = MODE == 0 && rrow != nullptr;        // (uniform) the count slot weighted by rho_i
+  const double rsc = p.st->rho, sk = (MODE == 2 && p.masked_method == 2) ? 0.0 : p.st->s;
   double* slab = sZ + w * 16 * S;
   for (int idx = lane; idx < 16 * S; idx += 64) slab[idx] = 0.0;        // columns rp .. 16 NT stay zero
   f64x4 acc[NTT];
@@ -84,8 +99,8 @@ __device__ __forceinline__ void mgram_body(const StepParams& p, double* __restri
     for (int i = 0; i < NV; ++i) {
       const int row = min(s_ * 16 + vrow[i], dl - 1);
       v[i] = *reinterpret_cast<const VT*>(C + (size_t)row * rp + vcol[i]);
-      if (MODE == 0) m[i] = mk[row];
-      else wr[i] = rrow[row];
+      if (MODE != 1) m[i] = mk[row];
+      wr[i] = (MODE != 0 || wcnt) ? rrow[row] : 1.0;
     }
   };
   if (sl < nslab) load_slab(sl);
@@ -94,12 +109,12 @@ __device__ __forceinline__ void mgram_body(const StepParams& p, double* __restri
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
       const bool on = von[i] && (row0 + vrow[i] < dl) && (MODE == 1 || m[i] != 0);
-      const double sw = MODE == 1 ? rsqrt(rsc * wr[i] + sk) : 1.0;
+      const double sw = MODE != 0 ? rsqrt(rsc * wr[i] + sk) : 1.0;
       if (von[i]) {
 #pragma unroll
-        for (int j = 0; j < VEC; ++j) slab[vrow[i] * S + vcol[i] + j] = on ? (MODE == 1 ? (double)v[i][j] * sw : (double)v[i][j]) : 0.0;
+        for (int j = 0; j < VEC; ++j) slab[vrow[i] * S + vcol[i] + j] = on ? (MODE != 0 ? (double)v[i][j] * sw : (double)v[i][j]) : 0.0;
       }
-      cnt += (on && vcol[i] == 0) ? 1.0 : 0.0;          // the lane that holds a row's first vector counts the row
+      cnt += (on && vcol[i] == 0) ? (MODE == 0 ? wr[i] : 1.0) : 0.0;          // the lane that holds a row's first vector counts the row (1, or rho_i)
     }
     const int nx = sl + stride;
     if (nx < nslab) load_slab(nx);          // the next slab's loads fly during this slab's products
@@ -172,6 +187,14 @@ template <typename T, int NT, int NW>
 __global__ __launch_bounds__(NW * 64) void psmf_wgram_mfma(StepParams p, double* __restrict__ gpart) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   mgram_body<T, NT, NW, 1>(p, gpart, (int)blockIdx.x, (int)gridDim.x, reinterpret_cast<double*>(smem_raw));
+}
+
+// the masked weighted Gram of the current step (masked handle with a non-uniform diagonal R), launched in front of the sweep like
+// psmf_wgram_mfma and reduced the same way: gpart[blockIdx.x][r * r] -> psmf_mgram_reduce -> st->GR
+template <typename T, int NT, int NW>
+__global__ __launch_bounds__(NW * 64) void psmf_mwgram_mfma(StepParams p, double* __restrict__ gpart) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  mgram_body<T, NT, NW, 2>(p, gpart, (int)blockIdx.x, (int)gridDim.x, reinterpret_cast<double*>(smem_raw));
 }
 
 // One launch for the serial stage of step k (block 0: psmf_serial's body, psmf_kernels.hip) AND the masked Gram of step k + 1 (blocks
