@@ -53,11 +53,16 @@ typedef enum { PSMF_F32 = 0, PSMF_F64 = 1 } psmf_dtype;
  *                       advances the device one timestep at a time with psmf_step_host (the d-sized work stays on the device)
  * Kinds 0-4 are evaluated inside the device time loop of either engine, with analytic Jacobians df/dx, df/dtheta (the reference
  * uses autograd, psmf.py:41-44): the blocked engine (r <= 32) or the serial stage of the per-step engine's launched form (r > 32,
- * a non-uniform R, engine = 1; the persistent per-step kernel takes kinds 0, 1).  Kind 5 is the per-step engine's. */
+ * a non-uniform R, a masked handle, engine = 1; the persistent per-step kernel takes kinds 0, 1).  Kind 5 is the per-step engine's.
+ * A masked handle created with masked = PSMF_MASKED_DYNAMICS takes kinds 0-4, each with its own n_theta; kind 5 is refused there, and
+ * masked = 1 / 2 / 3 take kind 0 only. */
 typedef enum { PSMF_DYN_RANDOM_WALK = 0, PSMF_DYN_COS_PHASE = 1, PSMF_DYN_SCALED_WALK = 2, PSMF_DYN_SINUSOID = 3,
                PSMF_DYN_FOURIER = 4, PSMF_DYN_HOST = 5 } psmf_dyn_kind;
 
 typedef struct psmf_filter* psmf_handle;
+
+/* psmf_config.masked: 1 = the masked PSMF / rPSMF filter of ExperimentImpute (a random walk), 2 = MLE-SMF, 3 = TMF, and */
+#define PSMF_MASKED_DYNAMICS 4 /* the masked PSMF / rPSMF filter with any device-evaluated f_theta (see the field) */
 
 /* Mode table: which hook configuration of PSMFIter / rPSMFIter runs fused. */
 typedef struct {
@@ -78,7 +83,9 @@ typedef struct {
   int32_t store_y_pred;  /* keep y_hat_k = C_{k-1} mu_bar_k for every step (psmf.py:93)       */
   int32_t recursive;     /* 1: PSMFRecursive -- Adam step on theta inside the time loop every
                             `update_every` steps (psmf.py:287-304); 2: the same with plain SGD
-                            (psmf.py:244-248; learning rate = adam_lr / its schedule)           */
+                            (psmf.py:244-248; learning rate = adam_lr / its schedule).  0, 1 and 2 are accepted on a
+                            masked = PSMF_MASKED_DYNAMICS handle too (theta, its gradient sum and the moments are replicated over row shards);
+                            refused with PSMF_DYN_HOST, which keeps theta on the host            */
   int32_t update_every;
   int32_t gram_refresh;  /* recompute G = C^T C exactly every this many steps (0 = only at
                             set_state); between refreshes G is updated algebraically           */
@@ -101,6 +108,18 @@ typedef struct {
                             observed count), y_hat stored unmasked.  Per-step engine, one masked Gram pass per step; needs the
                             full filter (coef_update, eta_full, pbar_predict = 1) and store_y_pred = 1; R = rho I, or any
                             diagonal R with nonuniform_R = 1 (masked = 1 / 2; psmf_set_row_noise before the first run).
+                            masked = 1 is a random-walk filter (Pbar = P + Q, PSMF.py:65-66) and refuses every other dyn_kind.
+                            Dynamics: masked = 4 (PSMF_MASKED_DYNAMICS) is the step of masked = 1 with every device-evaluated
+                            f_theta (dyn_kind 0-4: mu_bar = f_theta(mu, k), Pbar = F P F^T + Q inside the time loop), robust = 0
+                            or 1 and recursive = 0, 1 or 2, on row shards and on the series ring; psmf_predict rolls out with
+                            f_theta; with dyn_kind 0 it is masked = 1, bit for bit, and takes a row noise the same way.  The theta gradient of a masked step is
+                            that of the masked incremental likelihood 1/2 sum_i log(s m_i + eta) + 1/2 e^T e / (s + eta)
+                            (psmf.py:264-270, rpsmf.py:196-200; the Gaussian form for robust = 1 too):
+                            g_f = n_obs w / N - h / N - ee w / N^2 with n_obs = sum_i m_i of the step; a step without any
+                            observation adds exactly zero.  Refused, each by name: dynamics with masked = 1; PSMF_DYN_HOST on a masked handle (the host
+                            would need the masked g_f); nonuniform_R = 1 together with n_theta > 0 (the Gram's count slot then
+                            carries sum m_i rho_i, so n_obs is not on the device); masked = 2 / 3 with any dynamics; R_k / Q_k
+                            schedules (psmf_set_schedules, psmf_set_q_matrix_schedule).
                             2 / 3: the baseline filters that share these contractions -- 2 = MLE-SMF (MLESMF.py:57-88: weights m_i / rho,
                             C += gam / eta (m o e) x_p^T, bands -+ sig sqrt(eta)), 3 = TMF (TMF.py:47-66: Pbar = I / nu with Q = I / nu and
                             P = 0 from the caller, kappa = 1, C += gam (m o e) x_p^T); gam from psmf_set_step_size */

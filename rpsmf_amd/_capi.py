@@ -16,6 +16,7 @@ ABI_VERSION = 3
 RMAX = 64
 F32, F64 = 0, 1
 DYN_RANDOM_WALK, DYN_COS_PHASE, DYN_SCALED_WALK, DYN_SINUSOID, DYN_FOURIER, DYN_HOST = 0, 1, 2, 3, 4, 5
+MASKED_DYNAMICS = 4        # psmf_config.masked: the masked PSMF / rPSMF filter with built-in dynamics (1: the random walk only, 2 MLE-SMF, 3 TMF)
 UNIQUE_ID_BYTES = 128
 
 OK, ERR_ARG, ERR_HIP, ERR_RCCL, ERR_NUMERIC, ERR_STATE, ERR_NO_DEVICE = 0, -1, -2, -3, -4, -5, -6

@@ -455,10 +455,19 @@ const char* check_config(const psmf_config* cfg) {
   if (cfg->dyn_kind == PSMF_DYN_HOST && cfg->recursive) return "psmf_create: host-stepped dynamics keep theta (and its optimiser) on the host";
   if (cfg->recursive && cfg->update_every < 1) return "psmf_create: update_every must be >= 1";
   if (cfg->recursive < 0 || cfg->recursive > 2) return "psmf_create: recursive must be 0, 1 (in-loop Adam) or 2 (in-loop SGD)";
-  if (cfg->masked < 0 || cfg->masked > 3) return "psmf_create: masked must be 0 .. 3";
-  if (cfg->masked >= 2 && (cfg->robust || cfg->dyn_kind != PSMF_DYN_RANDOM_WALK)) return "psmf_create: masked = 2 (MLE-SMF) / 3 (TMF) are random-walk, non-robust filters";
+  if (cfg->masked < 0 || cfg->masked > PSMF_MASKED_DYNAMICS) return "psmf_create: masked must be 0 .. 4";
+  if ((cfg->masked == 2 || cfg->masked == 3) && (cfg->robust || cfg->dyn_kind != PSMF_DYN_RANDOM_WALK))
+    return "psmf_create: masked = 2 (MLE-SMF) / 3 (TMF) are random-walk, non-robust filters";
   if (cfg->masked) {
-    if (cfg->dyn_kind != PSMF_DYN_RANDOM_WALK) return "psmf_create: masked handles are random-walk filters (ExperimentImpute/PSMF.py:65-66: Pbar = P + Q)";
+    // masked = 1 is the ExperimentImpute filter, a random walk by definition; masked = 4 (PSMF_MASKED_DYNAMICS) is the same step with
+    // every device-evaluated f_theta (cos-phase, scaled walk, sinusoid, Fourier basis), theta learned between epochs or in the loop:
+    // the gradient is that of the masked incremental likelihood (serial_body, psmf_kernels.hip)
+    if (cfg->masked == 1 && cfg->dyn_kind != PSMF_DYN_RANDOM_WALK)
+      return "psmf_create: masked = 1 handles are random-walk filters (ExperimentImpute/PSMF.py:65-66: Pbar = P + Q); masked = 4 runs f_theta";
+    if (cfg->dyn_kind == PSMF_DYN_HOST)
+      return "psmf_create: masked handles evaluate f_theta on the device: not with PSMF_DYN_HOST (the host would need the masked gradient g_f)";
+    if (cfg->nonuniform_R && cfg->n_theta > 0)
+      return "psmf_create: masked handles with nonuniform_R = 1 do not learn theta (the Gram's count slot carries sum m_i rho_i, not n_obs): n_theta must be 0";
     if (!cfg->coef_update || !cfg->eta_full || !cfg->pbar_predict || cfg->engine == 2 || !cfg->store_y_pred)
       return "psmf_create: masked handles need the full filter (coef_update, eta_full, pbar_predict), store_y_pred = 1 and the per-step engine";
     if (cfg->masked == 3 && cfg->nonuniform_R) return "psmf_create: masked = 3 (TMF) ignores R (TMF.py:47-66): not with nonuniform_R = 1";
@@ -595,10 +604,14 @@ int psmf_device_count(void) {
 
 const char* psmf_last_error(psmf_handle h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 
-int psmf_create(psmf_handle* out, const psmf_config* cfg) {
-  if (!out || !cfg) return fail(nullptr, PSMF_ERR_ARG, "psmf_create: null argument");
+int psmf_create(psmf_handle* out, const psmf_config* cfg_in) {
+  if (!out || !cfg_in) return fail(nullptr, PSMF_ERR_ARG, "psmf_create: null argument");
   *out = nullptr;
-  if (const char* msg = check_config(cfg)) return fail(nullptr, PSMF_ERR_ARG, msg);
+  if (const char* msg = check_config(cfg_in)) return fail(nullptr, PSMF_ERR_ARG, msg);
+  // masked = 4 is masked = 1 with f_theta allowed (check_config): one masked PSMF / rPSMF filter from here on
+  psmf_config cfg_norm = *cfg_in;
+  if (cfg_norm.masked == PSMF_MASKED_DYNAMICS) cfg_norm.masked = 1;
+  const psmf_config* cfg = &cfg_norm;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
     return fail(nullptr, PSMF_ERR_NO_DEVICE, "psmf_create: no HIP device visible (the MI355X path has no CPU fallback)");

@@ -453,6 +453,12 @@ __device__ __forceinline__ void serial_body(const StepParams& p, const int first
   double rho = st->rho, lam = st->lam;
   const double N0 = st->N, kappa0 = st->kappa, s0 = st->s, eta0 = st->eta;
   const long long k0 = st->k;       // read once (thread 0 rewrites it below)
+  // masked handle: the theta gradient is that of the masked incremental likelihood, 1/2 sum_i log(s m_i + eta) + 1/2 e^T e / (s + eta)
+  // (pypsmf psmf.py:264-270, rpsmf.py:196-200 -- the Gaussian form for the robust class too):
+  //   g_f = n_obs w / N - h / N - ee w / N^2,   n_obs = sum_i m_i of THIS step = the count slot of the step's reduced Gram.
+  // p.mg holds step k's Gram and count for the whole of this stage: the Gram of step k + 1 that runs beside it (psmf_serial_mgram) goes
+  // to the partial buffer, and psmf_mgram_reduce (with the shards' all-reduce behind it) rewrites p.mg only after this kernel
+  const double gn = p.mask ? p.mg[r * r] : dd;
   long long knext = k0;             // index (0-based) of the step to prepare
   const bool vl = tid < r;
   // the per-step engine evaluates the random walk and cos(2 pi theta t + x) itself (n_theta = r); every other f is
@@ -559,18 +565,18 @@ __device__ __forceinline__ void serial_body(const StepParams& p, const int first
     }
 
     PSMF_STAMP(3);
-    // ---- theta gradient at the pre-update state   psmf.py:48-66,167-177; rpsmf.py:53-73 ----
+    // ---- theta gradient at the pre-update state   psmf.py:48-66,167-177; rpsmf.py:53-73 (masked handle: gn, see above) ----
     if (tl && p.dyn_kind == 1) {
       const double tk = (double)(k0 + 1);
       const double arg = 2.0 * M_PI * theta * tk + mu_old;
       const double jt = -sin(arg) * (2.0 * M_PI * tk);
       const double wi = w_t, hi = s_he[tid];
       double gf;
-      if (p.robust) {
+      if (p.robust && !p.mask) {
         const double D = lam * N;
         gf = dd * wi / N + 0.5 * (dd + lam) * (-2.0 * hi / D - 2.0 * lam * ee * wi / (D * D)) / (1.0 + ee / D);
       } else {
-        gf = dd * wi / N - hi / N - ee * wi / (N * N);
+        gf = gn * wi / N - hi / N - ee * wi / (N * N);
       }
       gsum += jt * gf;
     }
@@ -579,11 +585,11 @@ __device__ __forceinline__ void serial_body(const StepParams& p, const int first
       if (vl) {
         const double wi = w_t, hi = s_he[tid];
         double gf;
-        if (p.robust) {
+        if (p.robust && !p.mask) {
           const double D = lam * N;
           gf = dd * wi / N + 0.5 * (dd + lam) * (-2.0 * hi / D - 2.0 * lam * ee * wi / (D * D)) / (1.0 + ee / D);
         } else {
-          gf = dd * wi / N - hi / N - ee * wi / (N * N);
+          gf = gn * wi / N - hi / N - ee * wi / (N * N);
         }
         s_gf[tid] = gf;
         s_dx[tid] = mu_old;
@@ -594,11 +600,11 @@ __device__ __forceinline__ void serial_body(const StepParams& p, const int first
     }
     if (host_dyn && vl) {     // g_f for the host, which holds J_theta (same closed forms)
       const double wi = w_t, hi = s_he[tid];
-      if (p.robust) {
+      if (p.robust && !p.mask) {
         const double D = lam * N;
         st->gf[tid] = dd * wi / N + 0.5 * (dd + lam) * (-2.0 * hi / D - 2.0 * lam * ee * wi / (D * D)) / (1.0 + ee / D);
       } else {
-        st->gf[tid] = dd * wi / N - hi / N - ee * wi / (N * N);
+        st->gf[tid] = gn * wi / N - hi / N - ee * wi / (N * N);
       }
     }
 

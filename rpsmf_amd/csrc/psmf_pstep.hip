@@ -828,11 +828,14 @@ __device__ __forceinline__ void pstep_hub(const PstepParams& q, char* smem) {
       const double jt = -ps_sin(arg) * (2.0 * M_PI * tk);
       const double wi = w_t, hi = s_he[tid];
       double gf;
-      if (p.robust) {
+      // masked instance: the gradient of the masked incremental likelihood (serial_body, psmf_kernels.hip) -- the Gaussian form for the
+      // robust filter too, with the observed count of the CURRENT step: nobs was read with this step's Gram (before the loop, or in
+      // phase C of the step before) and is not rewritten until this step's own phase C
+      if (!MASKED && p.robust) {
         const double D = lam * N;
         gf = dd * wi / N + 0.5 * (dd + lam) * (-2.0 * hi / D - 2.0 * lam * ee * wi / (D * D)) / (1.0 + ee / D);
       } else {
-        gf = dd * wi / N - hi / N - ee * wi / (N * N);
+        gf = (MASKED ? nobs : dd) * wi / N - hi / N - ee * wi / (N * N);
       }
       gsum += jt * gf;
     }

@@ -204,10 +204,13 @@ class PSMFIter:
             self._check_hip_configuration()
 
     # ------------------------------------------------------------------ drive methods
-    def run(self, y, T, n_iter, n_pred):
+    def run(self, y, T, n_iter, n_pred, mask=None):
         self.optim_init()
         for i in range(1, n_iter + 1):
-            self.step(y, i, T)
+            if mask is None:
+                self.step(y, i, T)
+            else:
+                self.step(y, i, T, mask=mask)
             self.predict(i, T, n_pred)
             self.optim_update(i)
 
@@ -225,9 +228,15 @@ class PSMFIter:
         self._V = _StateDict({0: latest(self._V, self.V0)})
         self._gradsum = np.zeros(np.asarray(self.theta0).shape)
 
-    def step(self, y, i, T):
+    def step(self, y, i, T, mask=None):
+        """One epoch over y[1..T].  `mask` (device back end): the observed entries of every step, {k: (d, 1) or (d,)} like y or an
+        array indexed the same way (row 0 unused), nonzero = observed -- the masked filter of ExperimentImpute (e = m o (y - y_hat),
+        eta and lambda with d, y_hat stored unmasked) with this class's f_theta, and theta learned from the gradient of the masked
+        incremental likelihood (psmf.py:264-270).  None: every entry observed, nothing changes."""
+        if mask is not None and self.backend != "hip":
+            raise NotImplementedError('mask=: backend="numpy" executes the reference\'s hooks, which know no missing entries; use backend="hip"')
         if self.backend == "hip":
-            return self._step_hip(y, i, T)
+            return self._step_hip(y, i, T, mask)
         self.step_reset()
         for k in range(1, T + 1):
             self.inner(i, k, np.asarray(y[k]).reshape(-1, 1))     # y[k], k = 1..T: dict or array-like (row 0 unused)
@@ -547,6 +556,8 @@ class PSMFIter:
             kw.update(engine="step")
         if self._row_noise() is not None:
             kw.update(nonuniform_R=True)
+        if getattr(self, "_masked", False):
+            kw.update(masked=_capi.MASKED_DYNAMICS, engine="step")
         return kw
 
     # a Q[k] schedule of matrices (not multiples of Q[1]) goes to the device as [T + 1, r, r] up to this size, else host-stepped
@@ -571,6 +582,7 @@ class PSMFIter:
             if hasattr(self, "_qmat_key"):
                 self._qmat_key = None
         if self._dev is None:
+            self._mask_key = None
             self._dev = _capi.DeviceFilter(self._d, self._r, **self._device_kwargs())
             if self._dense_noise() is not None:
                 lam, U = self._dense_noise()
@@ -605,6 +617,48 @@ class PSMFIter:
             return
         self._dev.upload_series(Y, t0=0, T_total=T)
         self._series_key = key
+
+    def _select_masked(self, mask, T):
+        """A masked epoch runs on a masked handle (cfg.masked = PSMF_MASKED_DYNAMICS, per-step engine), an unmasked one on the handle it always had:
+        going from one to the other replaces the handle.  What a masked handle cannot run is refused here, by name."""
+        want = mask is not None
+        if want:
+            if self._host_stepped():
+                raise NotImplementedError("mask=: host-stepped callables (a nonlinearity or learning-rate schedule evaluated on the host) "
+                                          "would need the masked gradient g_f on the host; use one of the built-in nonlinearities")
+            if HIP_MODES[self.hip_mode] != (True, True, True):
+                raise NotImplementedError(f"mask=: the masked filter is the full filter; hip_mode {self.hip_mode!r} is not")
+            _rho, _Q, rho_s, q_s = self._device_rho_q(T)
+            if rho_s is not None or q_s is not None or getattr(self, "_q_matrix_sched", False):
+                raise NotImplementedError("mask=: R / Q schedules that vary with k are not run on masked handles (a constant R = rho I or "
+                                          "diagonal R, a constant Q)")
+            if self._dense_noise() is not None:
+                raise NotImplementedError("mask=: a dense (non-diagonal) R is run in its eigenbasis, where a mask over the rows means nothing")
+            if self._row_noise() is not None and np.asarray(self.theta0).size > 0:
+                raise NotImplementedError("mask=: a non-uniform diagonal R with learned theta (the device then carries sum m_i rho_i in "
+                                          "place of the observed count the masked gradient needs); use R = rho I")
+        if want != getattr(self, "_masked", False):
+            if self._dev is not None:
+                self._C[0]                  # (fetches a device-resident C before its handle goes)
+                self._dev.close()
+                self._dev, self._series_key, self._sched_key = None, None, (None, None)
+            self._masked = want
+
+    def _upload_mask(self, mask, T):
+        """mask[k], k = 1..T, onto the device behind the series; as _upload_series, the resident copy is reused only if the content
+        (and the series it belongs to) is unchanged."""
+        if isinstance(mask, dict):
+            M = np.concatenate([np.asarray(mask[k]).reshape(1, -1) for k in range(1, T + 1)], axis=0)
+        else:
+            M = np.asarray(mask)[1:T + 1].reshape(T, -1)
+        if M.shape != (T, self._d):
+            raise ValueError(f"mask: expected {T} rows of length {self._d}, got an array of shape {M.shape}")
+        M = np.ascontiguousarray(M != 0, dtype=np.uint8)
+        key = (self._series_key, _content_hash(M))
+        if getattr(self, "_mask_key", None) == key:
+            return
+        self._dev.upload_mask(M)
+        self._mask_key = key
 
     def _push_state(self, i, T=None):
         dev = self._dev
@@ -642,8 +696,9 @@ class PSMFIter:
         self._y_pred = _YPred(self, T)
         return s
 
-    def _step_hip(self, y, i, T):
+    def _step_hip(self, y, i, T, mask=None):
         self.step_reset()
+        self._select_masked(mask, T)
         if (not self._host_stepped() and not self.robust and not getattr(self, "_q_matrix_sched", False)
                 and isinstance(self._device_rho_q(T)[3], str)):
             # Q[k] is not a scalar multiple of Q[1]: uploaded matrix by matrix, P_bar = F P F^T + Q_k formed in the per-step
@@ -658,6 +713,8 @@ class PSMFIter:
                 self._dev, self._series_key, self._sched_key = None, None, (None, None)
         self._ensure_device()
         self._upload_series(y, T)
+        if mask is not None:
+            self._upload_mask(mask, T)
         self._push_state(i, T)
         if self._host_stepped():
             return self._after_device_epoch(self._run_host_stepped(i, T), T)
@@ -686,6 +743,7 @@ class PSMFIter:
             raise NotImplementedError("step_stream: R / Q schedules that vary with k are indexed by step and not windowed; use step()")
         recursive = hasattr(type(self), "_step_hip_recursive")
         self.step_reset()
+        self._select_masked(None, None)      # (a stream carries no mask through the classes)
         dev = self._ensure_device(ring=(int(chunk), int(n_slots)))
         self._series_key = None
         if recursive:
@@ -836,6 +894,10 @@ def _recursive_host_stepped(obj, base):
 
 
 class PSMFIterMissing(PSMFIter):
+    """Unfinished in the reference (pypsmf/psmf/psmf.py:251-254) and not constructible here either.  Missing observations with this
+    library's dynamics: PSMFIter(...).step(y, i, T, mask=m) / .run(..., mask=m) (and the recursive classes' step / run), or
+    rpsmf_amd.impute for the ExperimentImpute drivers."""
+
     def __init__(*args, **kwargs):
         # unfinished in the reference as well (pypsmf/psmf/psmf.py:251-254); the working masked
         # filter is rpsmf_amd.impute (ExperimentImpute semantics)
@@ -846,15 +908,20 @@ class PSMFRecursive(PSMFIter):
     """Online variant: theta takes an optimiser step inside the time loop every `update_every`
     observations (pypsmf/psmf/psmf.py:275-331)."""
 
-    def run(self, y, T, n_pred, update_every=1):
+    def run(self, y, T, n_pred, update_every=1, mask=None):
         self._update_every = update_every
         self.optim_init()
-        self.step(y, T)
+        if mask is None:
+            self.step(y, T)
+        else:
+            self.step(y, T, mask=mask)
         self.predict(T, n_pred)
 
-    def step(self, y, T):
+    def step(self, y, T, mask=None):
+        if mask is not None and self.backend != "hip":
+            raise NotImplementedError('mask=: backend="numpy" executes the reference\'s hooks, which know no missing entries; use backend="hip"')
         if self.backend == "hip":
-            return self._step_hip_recursive(y, T)
+            return self._step_hip_recursive(y, T, mask)
         self.step_reset()
         for k in range(1, T + 1):
             self.inner(k, np.asarray(y[k]).reshape(-1, 1))
@@ -903,10 +970,13 @@ class PSMFRecursive(PSMFIter):
     def _device_kwargs(self):
         return _recursive_kwargs(self, super()._device_kwargs())
 
-    def _step_hip_recursive(self, y, T):
+    def _step_hip_recursive(self, y, T, mask=None):
         self.step_reset()
+        self._select_masked(mask, T)
         self._ensure_device()
         self._upload_series(y, T)
+        if mask is not None:
+            self._upload_mask(mask, T)
         self._theta = {0: self._theta[0]}
         self._push_state(1, T)
         if self._host_stepped():

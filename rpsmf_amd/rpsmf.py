@@ -120,7 +120,8 @@ class rPSMFIter(PSMFIter):
 class rPSMFIterMissing(rPSMFIter):
     """Not usable in the reference either (singular S_k whenever a row is missing and a hook called
     with the wrong arity, rpsmf.py:187-287); the working masked semantics are those of
-    ExperimentImpute, provided by rpsmf_amd.impute."""
+    ExperimentImpute, provided by rpsmf_amd.impute.  Missing observations with this library's dynamics:
+    rPSMFIter(...).step(y, i, T, mask=m) / .run(..., mask=m), and the same keyword on rPSMFRecursive."""
 
     def __init__(self, *args, **kwargs):
         raise NotImplementedError("use rpsmf_amd.impute.robust_PSMF (ExperimentImpute semantics)")
