@@ -410,6 +410,43 @@ int psmf_impute_run_rows(const psmf_impute_config* cfg, const double* YorgInt, c
  * 4 = masked per-step engine of the large-d handle.  Negative = error.  (Diagnostics; the reference has one code path.) */
 int psmf_impute_kernel_id(const psmf_impute_config* cfg);
 
+/* ================= batched PSMF with linear-Gaussian dynamics and an observation map (ExperimentChange) ==================== */
+typedef struct {
+  int32_t abi_version;
+  int32_t d, n, r;       /* Y is d x n, C d x r (reference layout)                                          */
+  int32_t p;             /* dimension of the latent state, r <= p <= 32: A, Q, P are p x p, H is r x p      */
+  int32_t batch;         /* independent series (replicas): own Y, C, V, x, P                                 */
+  int32_t device;
+  int32_t carry_P;       /* 1: P_prev = P_{t-1} (the textbook recursion).  0: PSMF.m:30 as written -- P_prev = P0 at the first
+                          * step of a series, 0 at every later step                                          */
+  int32_t first_step;    /* 1: the call starts a series.  0: it continues one (x, P, C, V of the previous call); with
+                          * carry_P = 0 every step of such a call uses P_prev = 0                            */
+  int32_t want_pred;     /* also return Ypred                                                                */
+} psmf_ssm_config;
+
+/* The filter of ExperimentChange/PSMF.m:6-45 for a batch of independent series, float64 throughout, one workgroup per replica and
+ * all replicas in one launch.  Per step: xbar = A x, Pbar = A P_prev A^T + Q, z = H xbar, w = V z, s = z^T w, yhat = C z,
+ * e = y - yhat, P_z = H Pbar H^T, S = C P_z C^T + (rho + s) I, x = xbar + Pbar H^T C^T S^-1 e,
+ * P = Pbar - Pbar H^T C^T S^-1 C H Pbar, eta = trace(C P_z C^T + rho I) / d, N = s + eta, C += e w^T / N, V -= w w^T / N
+ * (S is never formed: two symmetric r x r inversions).  Limits: 1 <= d <= 512, 1 <= r <= 16, r <= p <= 32; anything else is
+ * PSMF_ERR_ARG and the message names the limit.  All arrays row-major, time-major where there is a time axis:
+ *   Y        batch x n x d              (row t = y_t)
+ *   C        batch x d x r   in: C0     out: final C
+ *   V        batch x r x r   in / out
+ *   x        batch x p       in: x_0    out: x_n
+ *   P        batch x p x p   in: P0 (read at the first step of a series, and at every call with carry_P = 1)   out: P_n
+ *   A, Q     p x p, H r x p  shared by the replicas; Q symmetric positive definite (PSMF_ERR_ARG otherwise); rho >= 0, R = rho I
+ *   X        batch x n x p   the filtered states x_t
+ *   Ypred    batch x n x d or NULL (want_pred): the one-step predictions C z
+ *   scalars  batch x n x 2 or NULL: (s, eta) of every step
+ *   status   batch int32 or NULL, as in psmf_impute_run: PSMF_OK, or PSMF_ERR_NUMERIC for a replica whose r x r system lost
+ *            positive definiteness or whose state is not finite; the other replicas are untouched by it and the call returns
+ *            PSMF_OK.  With status = NULL such a replica fails the call (PSMF_ERR_NUMERIC).
+ *   elapsed_ms  the kernel alone (HIP events), or NULL */
+int psmf_ssm_run(const psmf_ssm_config* cfg, const double* Y, double* C, double* V, double* x, double* P, const double* A,
+                 const double* Q, const double* H, double rho, double* X, double* Ypred, double* scalars, int32_t* status,
+                 float* elapsed_ms);
+
 #ifdef __cplusplus
 }
 #endif

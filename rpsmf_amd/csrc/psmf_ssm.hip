@@ -1,0 +1,490 @@
+// Batched PSMF with linear-Gaussian dynamics and an observation map: the filter of the change-point experiment
+//   PSMF                                      ExperimentChange/PSMF.m:6-45 (driven by ExperimentChange/main.m)
+// for a whole batch of independent series.  The latent state x has its own dimension p >= r, moves by a linear map A (p x p) with
+// process noise Q and reaches the dictionary through an observation map H (r x p): y ~ C H x.  A, Q, H and rho (R = rho I) are shared
+// by the replicas; Y, C, V, x, P are per replica.  Per step
+//   xbar = A x,  Pbar = A P_prev A^T + Q       (carry_P = 0: P_prev = P0 at the first step of a series, 0 afterwards -- PSMF.m:30 as written)
+//   z = H xbar, w = V z, s = z^T w, yhat = C z, e = y - yhat,  P_z = H Pbar H^T,  S = C P_z C^T + (rho + s) I
+//   x = xbar + Pbar H^T C^T S^-1 e,  P = Pbar - Pbar H^T C^T S^-1 C H Pbar
+//   eta = trace(C P_z C^T + rho I) / d,  N = s + eta,  C += e w^T / N,  V -= w w^T / N
+// No d x d matrix is formed.  With G = C^T C, h = C^T e, kappa = 1 / (rho + s):
+//   P_z+ = (P_z^-1 + kappa G)^-1        two symmetric sweep inversions (wave_sweep16m), the first beside the Gram
+//   B = P_z^-1 P_z+ = I - kappa G P_z+  formed as the PRODUCT: the textbook W = kappa G - kappa^2 G P_z+ G cancels 1e3-fold where rho
+//                                       is small against C P_z C^T (the experiment's rho = 1e-3 with P0 = I)
+//   u = kappa B h = C^T S^-1 e,  W = kappa sym(B G) = C^T S^-1 C,  eta = <G, P_z> / d + rho
+//   x = xbar + Pbar H^T u,  P = Pbar - (Pbar H^T) W (Pbar H^T)^T
+// One 256-thread workgroup per replica, grid = batch; C, V, x, P, Pbar and the shared A, Q, H live in LDS in float64 for the whole
+// call (rows zero-padded: r to 16, p to 32, d to a multiple of 4), y_{t+1} is prefetched while step t runs, X[t], yhat and (s, eta)
+// are stored from LDS, and the barriers inside the step loop order LDS only (solve_barrier<true>): the prefetch and the stores stay
+// in flight across them.  G and h come from the augmented [C | e] product on the float64 matrix cores, recomputed every step, as in
+// psmf_impute2.hip; the p x p and p x r products of the step (A P_prev, its product with A^T, Pbar H^T, its product with W, the update
+// of P) run there too, one 16 x 16 output tile per wave.  Limits: d <= 512, r <= 16, r <= p <= 32.
+#include "psmf_host.h"        // g_create_error, HIP_TRY, Dev<>, Event
+#include "psmf_sweep.h"       // solve_barrier
+#include "psmf_wave16.hip"    // wave_sweep16m, Sw16K
+
+#include <cmath>
+#include <string>
+#include <vector>
+
+namespace psmf {
+
+constexpr int SR = 16;       // padded r
+constexpr int SP = 32;       // padded p
+constexpr int SLA = 33;      // row stride of A, H and the p x p matrices in LDS (read down a column by consecutive lanes)
+constexpr int SLH = 17;      // row stride of Pbar H^T and of (Pbar H^T) W
+
+struct SsmParams {
+  int d, n, r, p, carry_P, first_step;
+  double rho;
+  const double* Y;         // batch x n x d
+  double* C;               // batch x d x r
+  double* V;               // batch x r x r
+  double* x;               // batch x p
+  double* P;               // batch x p x p
+  const double* A;         // p x p (shared)
+  const double* Q;         // p x p
+  const double* H;         // r x p
+  double* X;               // batch x n x p
+  double* Ypred;           // batch x n x d or null
+  double* scal;            // batch x n x 2 or null
+  int* err;                // batch
+};
+
+__host__ __device__ inline size_t ssm_lds_doubles(int d) {
+  const size_t d4 = ((size_t)d + 3) & ~(size_t)3;
+  return d4 * SR + SR * SR                 // C, V
+         + 2 * (size_t)SP * SLA            // A, H (H uses SR rows of it)
+         + 3 * (size_t)SP * SLA            // Q, P, Pbar
+         + 3 * 2 * 256                     // A P_prev (phases 1-2), the Gram partials of waves 1-3 (5-6), (Pbar H^T) W (9-10)
+         + (size_t)SP * SLH                // Pbar H^T
+         + 7 * (size_t)SR * SR             // P_z, P_z^-1, P_z+, G, B, W, (spare)
+         + 2 * SP + 5 * SR                 // x, xbar, z, w, h, u, (spare)
+         + 2 * d4                          // e, yhat
+         + 8 + 2;                          // scalars, error flag
+}
+inline size_t ssm_lds_bytes(int d) { return (ssm_lds_doubles(d) * 8 + 15) & ~(size_t)15; }
+
+__device__ __forceinline__ void ssm_barrier() { solve_barrier<true>(); }
+
+__global__ __launch_bounds__(WG) void psmf_ssm_kernel(SsmParams p) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  double* sm = reinterpret_cast<double*>(smem_raw);
+  const int d = p.d, n = p.n, r = p.r, np = p.p, tid = threadIdx.x, rep = blockIdx.x;
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lane = tid & 63, lk = lane >> 4, lr = lane & 15;
+  const int d4 = (d + 3) & ~3, p4 = (np + 3) & ~3;
+  // ---- LDS carve (doubles); every padding entry is zero and stays zero ----
+  double* sC = sm;                           // d4 x SR
+  double* sV = sC + (size_t)d4 * SR;         // SR x SR
+  double* sA = sV + SR * SR;                 // SP x SLA
+  double* sH = sA + SP * SLA;                // SR x SLA
+  double* sQ = sH + SP * SLA;                // SP x SLA each from here
+  double* sP = sQ + SP * SLA;                // P_{t-1} / P_t
+  double* sPb = sP + SP * SLA;               // Pbar
+  double* sT = sPb + SP * SLA;               // 1536: A P_prev (row stride SLA) in phases 1-2; (Pbar H^T) W with row stride SLH in phases 9-10
+  double* sgp = sT;                          // ... and in phases 5-6 the Gram partials, 3 waves x 2 tiles x 256 in the MFMA output layout
+  double* sPH = sT + 3 * 2 * 256;            // SP x SLH: Pbar H^T
+  double* sPz = sPH + SP * SLH;              // SR x SR each from here
+  double* sPzi = sPz + SR * SR;
+  double* sPp = sPzi + SR * SR;
+  double* sG = sPp + SR * SR;
+  double* sB = sG + SR * SR;
+  double* sW = sB + SR * SR;
+  double* sx = sW + 2 * SR * SR;             // SP
+  double* sxb = sx + SP;                     // SP
+  double* sz = sxb + SP;                     // SR each from here
+  double* sw = sz + SR;
+  double* sh = sw + SR;
+  double* su = sh + SR;
+  double* se = su + 2 * SR;                  // d4
+  double* syh = se + d4;                     // d4
+  double* ssc = syh + d4;                    // 8 scalars: 0 s, 1 eta, 2 N, 3 kappa
+  int* errflag = reinterpret_cast<int*>(ssc + 8);
+
+  const double* Yg = p.Y + (size_t)rep * n * d;
+  double* Cg = p.C + (size_t)rep * d * r;
+  double* Vg = p.V + (size_t)rep * r * r;
+  double* xg = p.x + (size_t)rep * np;
+  double* Pg = p.P + (size_t)rep * np * np;
+  double* Xg = p.X + (size_t)rep * n * np;
+
+  {
+    const int total = (int)ssm_lds_doubles(d);
+    for (int idx = tid; idx < total; idx += WG) sm[idx] = 0.0;
+  }
+  __syncthreads();
+  for (int idx = tid; idx < d * r; idx += WG) { const int i = idx / r, l = idx - i * r; sC[i * SR + l] = Cg[idx]; }
+  for (int idx = tid; idx < r * r; idx += WG) { const int i = idx / r, l = idx - i * r; sV[i * SR + l] = Vg[idx]; }
+  for (int idx = tid; idx < np * np; idx += WG) {
+    const int i = idx / np, l = idx - i * np;
+    sA[i * SLA + l] = p.A[idx];
+    sQ[i * SLA + l] = p.Q[idx];
+    sP[i * SLA + l] = Pg[idx];
+  }
+  for (int idx = tid; idx < r * np; idx += WG) { const int i = idx / np, l = idx - i * np; sH[i * SLA + l] = p.H[idx]; }
+  if (tid < np) sx[tid] = xg[tid];
+  const double rho = p.rho, idd = 1.0 / (double)d;
+  const bool one_tile = r < 16;       // the augmented column e fits the 16 x 16 tile
+  const int r2 = r + (r & 1);         // sweep size: even, identity-padded
+  bool inq[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) inq[q] = (lk + 4 * q) < r && lr < r;
+  Sw16K swk;
+  if (wv == 0) sw16k_init(swk, lk, lr);
+  bool bad = false;
+  double A1[4] = {0.0, 0.0, 0.0, 0.0}, Pzr[4] = {0.0, 0.0, 0.0, 0.0}, s = 0.0, kappa = 0.0;      // wave 0: -P_z^-1, P_z, s, kappa of the step
+  // prefetch row 0 of the series: unconditional loads (row index clamped, value used only where the row exists)
+  int rowc[2];
+  double ny[2];
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    rowc[u] = min(tid + u * WG, d - 1);
+    ny[u] = Yg[rowc[u]];
+  }
+  // The p x p products run on the float64 matrix cores, one 16 x 16 output tile per wave (first row ti, first column tj): the A operand
+  // of v_mfma_f64_16x16x4_f64 is element (row lr, k-slot lk), the B operand (k-slot lk, column lr), the result rows lk + 4 q of column
+  // lr.  The p x r products (Pbar H^T, its product with W) are the two tiles of waves 0 and 1.  Of the r x r products a thread forms
+  // the element (rk0, rc).
+  const int ti = (wv >> 1) << 4, tj = (wv & 1) << 4;
+  const int rc = tid & 15, rk0 = tid >> 4;
+  __syncthreads();
+  for (int t = 0; t < n; ++t) {
+    double yv[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) yv[u] = ny[u];
+    {
+      const size_t base = (size_t)min(t + 1, n - 1) * d;      // (the last row is simply loaded twice)
+#pragma unroll
+      for (int u = 0; u < 2; ++u) ny[u] = Yg[base + rowc[u]];
+    }
+    const bool usep = p.carry_P || (p.first_step && t == 0);      // else P_prev = 0: Pbar = Q
+    // ---- phase 1: T = A P_prev; xbar = A x ----
+    if (usep) {
+      f64x4 acc = {0.0, 0.0, 0.0, 0.0};
+      for (int kk = 0; kk < p4; kk += 4)
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(sA[(ti + lr) * SLA + kk + lk], sP[(kk + lk) * SLA + tj + lr], acc, 0, 0, 0);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) sT[(ti + lk + 4 * q) * SLA + tj + lr] = acc[q];
+    }
+    if (wv == 3 && lane < SP) {
+      double a = 0.0;
+#pragma unroll 4
+      for (int k = 0; k < p4; ++k) a = fma(sA[lane * SLA + k], sx[k], a);
+      sxb[lane] = a;
+    }
+    ssm_barrier();
+    // ---- phase 2: Pbar = T A^T + Q; z = H xbar ----
+    {
+      f64x4 acc;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) acc[q] = sQ[(ti + lk + 4 * q) * SLA + tj + lr];
+      if (usep)
+        for (int kk = 0; kk < p4; kk += 4)
+          acc = __builtin_amdgcn_mfma_f64_16x16x4f64(sT[(ti + lr) * SLA + kk + lk], sA[(tj + lr) * SLA + kk + lk], acc, 0, 0, 0);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) sPb[(ti + lk + 4 * q) * SLA + tj + lr] = acc[q];
+    }
+    if (wv == 3 && lane < SR) {
+      double a = 0.0;
+#pragma unroll 4
+      for (int k = 0; k < p4; ++k) a = fma(sH[lane * SLA + k], sxb[k], a);
+      sz[lane] = a;
+    }
+    ssm_barrier();
+    // ---- phase 3: Pbar H^T; w = V z; yhat = C z, e = y - yhat (a row per thread, two when d > 256) ----
+    if (wv < 2) {
+      f64x4 acc = {0.0, 0.0, 0.0, 0.0};
+      for (int kk = 0; kk < p4; kk += 4)
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(sPb[(16 * wv + lr) * SLA + kk + lk], sH[lr * SLA + kk + lk], acc, 0, 0, 0);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) sPH[(16 * wv + lk + 4 * q) * SLH + lr] = acc[q];
+    }
+    if (wv == 3 && lane < SR) {
+      double a0 = 0.0, a1 = 0.0;
+#pragma unroll
+      for (int l = 0; l < SR; l += 2) { a0 = fma(sV[lane * SR + l], sz[l], a0); a1 = fma(sV[lane * SR + l + 1], sz[l + 1], a1); }
+      sw[lane] = a0 + a1;
+    }
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int i = tid + u * WG;
+      if (i < d) {
+        double cr[SR], zr[SR];
+#pragma unroll
+        for (int l = 0; l < SR; ++l) { cr[l] = sC[i * SR + l]; zr[l] = sz[l]; }
+        double d0 = 0.0, d1 = 0.0;
+#pragma unroll
+        for (int l = 0; l < SR; l += 2) { d0 = fma(cr[l], zr[l], d0); d1 = fma(cr[l + 1], zr[l + 1], d1); }
+        const double dot = d0 + d1;
+        syh[i] = dot;
+        se[i] = yv[u] - dot;
+      }
+    }
+    ssm_barrier();
+    // ---- phase 4: P_z = H (Pbar H^T), one element per thread ----
+    {
+      double a = 0.0;
+#pragma unroll 4
+      for (int k = 0; k < p4; ++k) a = fma(sH[rk0 * SLA + k], sPH[k * SLH + rc], a);
+      sPz[rk0 * SR + rc] = a;
+    }
+    ssm_barrier();
+    // ---- phase 5: wave 0: s, kappa, -P_z^-1 (needs no Gram); waves 1-3: the augmented Gram [C | e]^T [C | e] on the matrix cores ----
+    if (wv == 0) {
+      s = wave_sum_f64_dpp(lane < SR ? sz[lane & 15] * sw[lane & 15] : 0.0);
+      kappa = fast_rcp(rho + s);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int i = lk + 4 * q;
+        Pzr[q] = inq[q] ? 0.5 * (sPz[i * SR + lr] + sPz[lr * SR + i]) : 0.0;
+        A1[q] = inq[q] ? Pzr[q] : (i == lr ? 1.0 : 0.0);
+      }
+      wave_sweep16m(A1, r2, swk, bad);          // -P_z^-1
+#pragma unroll
+      for (int q = 0; q < 4; ++q) sPzi[(lk + 4 * q) * SR + lr] = inq[q] ? -A1[q] : 0.0;
+    } else {
+      f64x4 acc1 = {0.0, 0.0, 0.0, 0.0}, acc2 = {0.0, 0.0, 0.0, 0.0};
+      const int ngrp = d4 >> 2;
+      for (int g = wv - 1; g < ngrp; g += 3) {
+        const int k = 4 * g + lk;                                     // < d4: padding rows hold zeros
+        const double cval = sC[k * SR + lr], ek = se[k];
+        const double a = cval + ((one_tile && lr == r) ? ek : 0.0);   // augmented column r: e (C is zero there)
+        acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a, a, acc1, 0, 0, 0);
+        if (!one_tile) acc2 = __builtin_amdgcn_mfma_f64_16x16x4f64(a, lr == 0 ? ek : 0.0, acc2, 0, 0, 0);
+      }
+      double* o = sgp + (size_t)(wv - 1) * 512;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) { o[q * 64 + lane] = acc1[q]; o[256 + q * 64 + lane] = acc2[q]; }
+    }
+    ssm_barrier();
+    // ---- phase 6: wave 0: G, eta, N, P_z+ = (P_z^-1 + kappa G)^-1; waves 1-3: G and h row-major ----
+    if (wv == 0) {
+      double G[4], tr = 0.0;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const double g0 = (sgp[q * 64 + lane] + sgp[512 + q * 64 + lane]) + sgp[1024 + q * 64 + lane];
+        G[q] = inq[q] ? g0 : 0.0;
+        tr += G[q] * Pzr[q];
+      }
+      const double eta = fma(wave_sum_f64_dpp(tr), idd, rho);
+      if (lane == 0) { ssc[0] = s; ssc[1] = eta; ssc[2] = s + eta; ssc[3] = kappa; }
+      double A2[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) A2[q] = inq[q] ? kappa * G[q] - A1[q] : ((lk + 4 * q) == lr ? 1.0 : 0.0);
+      wave_sweep16m(A2, r2, swk, bad);          // -P_z+
+#pragma unroll
+      for (int q = 0; q < 4; ++q) sPp[(lk + 4 * q) * SR + lr] = inq[q] ? -A2[q] : 0.0;
+    } else {
+      const int hc = one_tile ? r : 0, ht = one_tile ? 0 : 256;      // where h sits: column r of the tile / column 0 of the second one
+      for (int idx = tid - 64; idx < 256; idx += WG - 64) {
+        const int q = idx >> 6, l = idx & 63, i = (l >> 4) + 4 * q, c = l & 15;
+        const double g0 = (sgp[idx] + sgp[512 + idx]) + sgp[1024 + idx];
+        sG[i * SR + c] = (i < r && c < r) ? g0 : 0.0;
+        if (c == hc) {
+          const double h0 = (sgp[ht + idx] + sgp[512 + ht + idx]) + sgp[1024 + ht + idx];
+          sh[i] = i < r ? h0 : 0.0;
+        }
+      }
+    }
+    ssm_barrier();
+    // ---- phase 7: B = P_z^-1 P_z+; rank-1 updates of C and V (they need N, e, w only) ----
+    {
+      double a0 = 0.0, a1 = 0.0;
+#pragma unroll
+      for (int k = 0; k < SR; k += 2) {
+        a0 = fma(sPzi[rk0 * SR + k], sPp[k * SR + rc], a0);
+        a1 = fma(sPzi[rk0 * SR + k + 1], sPp[(k + 1) * SR + rc], a1);
+      }
+      sB[rk0 * SR + rc] = a0 + a1;
+      const double wsc = fast_rcp(ssc[2]);
+      for (int idx = tid; idx < d * SR; idx += WG) {       // (padding columns: w is zero there)
+        const int i = idx >> 4, l = idx & 15;
+        sC[idx] = fma(se[i], sw[l] * wsc, sC[idx]);
+      }
+      sV[rk0 * SR + rc] = fma(-sw[rk0] * wsc, sw[rc], sV[rk0 * SR + rc]);
+    }
+    ssm_barrier();
+    // ---- phase 8: W = kappa sym(B G), u = kappa B h ----
+    {
+      const double kap = ssc[3];
+      double a0 = 0.0, a1 = 0.0;
+#pragma unroll
+      for (int k = 0; k < SR; ++k) {
+        a0 = fma(sB[rk0 * SR + k], sG[k * SR + rc], a0);
+        a1 = fma(sB[rc * SR + k], sG[k * SR + rk0], a1);
+      }
+      sW[rk0 * SR + rc] = 0.5 * kap * (a0 + a1);
+      if (wv == 3 && lane < SR) {
+        double b0 = 0.0, b1 = 0.0;
+#pragma unroll
+        for (int k = 0; k < SR; k += 2) { b0 = fma(sB[lane * SR + k], sh[k], b0); b1 = fma(sB[lane * SR + k + 1], sh[k + 1], b1); }
+        su[lane] = kap * (b0 + b1);
+      }
+    }
+    ssm_barrier();
+    // ---- phase 9: x = xbar + (Pbar H^T) u; T2 = (Pbar H^T) W ----
+    if (wv == 3 && lane < SP) {
+      double a0 = 0.0, a1 = 0.0;
+#pragma unroll
+      for (int c = 0; c < SR; c += 2) { a0 = fma(sPH[lane * SLH + c], su[c], a0); a1 = fma(sPH[lane * SLH + c + 1], su[c + 1], a1); }
+      const double xn = sxb[lane] + (a0 + a1);
+      bad |= !isfinite(xn);
+      sx[lane] = xn;                             // (rows >= p of Pbar H^T and of xbar are zero)
+    }
+    if (wv < 2) {
+      f64x4 acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int kk = 0; kk < SR; kk += 4)
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(sPH[(16 * wv + lr) * SLH + kk + lk], sW[(kk + lk) * SR + lr], acc, 0, 0, 0);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) sT[(16 * wv + lk + 4 * q) * SLH + lr] = acc[q];
+    }
+    ssm_barrier();
+    // ---- phase 10: P = Pbar - T2 (Pbar H^T)^T; the step's stores, from LDS ----
+    {
+      f64x4 acc;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) acc[q] = sPb[(ti + lk + 4 * q) * SLA + tj + lr];
+#pragma unroll
+      for (int kk = 0; kk < SR; kk += 4)
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(-sT[(ti + lr) * SLH + kk + lk], sPH[(tj + lr) * SLH + kk + lk], acc, 0, 0, 0);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) sP[(ti + lk + 4 * q) * SLA + tj + lr] = acc[q];
+    }
+    if (tid < np) Xg[(size_t)t * np + tid] = sx[tid];
+    if (p.Ypred) {
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const int i = tid + u * WG;
+        if (i < d) p.Ypred[((size_t)rep * n + t) * d + i] = syh[i];
+      }
+    }
+    if (p.scal && tid == 64) {
+      p.scal[((size_t)rep * n + t) * 2] = ssc[0];
+      p.scal[((size_t)rep * n + t) * 2 + 1] = ssc[1];
+    }
+    ssm_barrier();
+  }
+  if (tid == 0) *errflag = 0;
+  __syncthreads();
+  for (int idx = tid; idx < d * r; idx += WG) { const int i = idx / r, l = idx - i * r; Cg[idx] = sC[i * SR + l]; }
+  for (int idx = tid; idx < r * r; idx += WG) { const int i = idx / r, l = idx - i * r; Vg[idx] = sV[i * SR + l]; }
+  for (int idx = tid; idx < np * np; idx += WG) { const int i = idx / np, l = idx - i * np; Pg[idx] = sP[i * SLA + l]; }
+  if (tid < np) xg[tid] = sx[tid];
+  if (bad) *errflag = 1;                     // (benign race: every writer stores 1)
+  __syncthreads();
+  if (tid == 0) p.err[rep] = *errflag;
+}
+
+}  // namespace psmf
+
+extern "C" int psmf_ssm_run(const psmf_ssm_config* cfg, const double* Y, double* C, double* V, double* x, double* P, const double* A,
+                            const double* Q, const double* H, double rho, double* X, double* Ypred, double* scalars, int32_t* status,
+                            float* elapsed_ms) {
+  using namespace psmf;
+  const struct {
+    int operator()(int code, const std::string& msg) const { g_create_error = "psmf_ssm_run: " + msg; return code; }
+    int operator()(psmf_handle, int code, const std::string& msg) const { return (*this)(code, msg); }
+  } fail{};
+  const psmf_handle w = nullptr;
+  if (!cfg || !Y || !C || !V || !x || !P || !A || !Q || !H || !X) return fail(PSMF_ERR_ARG, "null argument");
+  if (cfg->abi_version != PSMF_ABI_VERSION) return fail(PSMF_ERR_ARG, "ABI version mismatch");
+  const int d = cfg->d, n = cfg->n, r = cfg->r, np = cfg->p, B = cfg->batch;
+  if (d < 1 || d > 2 * WG)
+    return fail(PSMF_ERR_ARG, "need 1 <= d <= 512 (one workgroup per replica holds C in LDS; d = " + std::to_string(d) + ")");
+  if (r < 1 || r > SR) return fail(PSMF_ERR_ARG, "need 1 <= r <= 16 (r = " + std::to_string(r) + ")");
+  if (np > SP) return fail(PSMF_ERR_ARG, "need p <= 32 (p = " + std::to_string(np) + ")");
+  if (np < r) return fail(PSMF_ERR_ARG, "need p >= r: the observation map H is r x p (p = " + std::to_string(np) + ", r = " + std::to_string(r) + ")");
+  if (n < 1 || B < 1) return fail(PSMF_ERR_ARG, "need n >= 1 and batch >= 1");
+  if (cfg->want_pred && !Ypred) return fail(PSMF_ERR_ARG, "want_pred needs Ypred");
+  if (!std::isfinite(rho) || rho < 0.0) return fail(PSMF_ERR_ARG, "rho must be finite and >= 0 (R = rho I)");
+  const size_t lds = ssm_lds_bytes(d);
+  if (lds > 160 * 1024) return fail(PSMF_ERR_ARG, "the replica's state needs more than 160 KB of LDS");
+  {
+    // Q: symmetric positive definite (Cholesky on the host, p <= 32)
+    double qmax = 0.0;
+    for (int i = 0; i < np * np; ++i) {
+      if (!std::isfinite(Q[i]) || !std::isfinite(A[i])) return fail(PSMF_ERR_ARG, "A and Q must be finite");
+      qmax = std::fmax(qmax, std::fabs(Q[i]));
+    }
+    for (int i = 0; i < np; ++i)
+      for (int j = 0; j < i; ++j)
+        if (std::fabs(Q[i * np + j] - Q[j * np + i]) > 1e-12 * qmax) return fail(PSMF_ERR_ARG, "Q must be symmetric");
+    std::vector<double> L((size_t)np * np, 0.0);
+    for (int i = 0; i < np; ++i)
+      for (int j = 0; j <= i; ++j) {
+        double a = Q[i * np + j];
+        for (int k = 0; k < j; ++k) a -= L[i * np + k] * L[j * np + k];
+        if (i == j) {
+          if (!(a > 0.0)) return fail(PSMF_ERR_ARG, "Q must be positive definite");
+          L[i * np + i] = std::sqrt(a);
+        } else {
+          L[i * np + j] = a / L[j * np + j];
+        }
+      }
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(PSMF_ERR_NO_DEVICE, "no HIP device visible");
+  if (cfg->device < 0 || cfg->device >= ndev) return fail(PSMF_ERR_ARG, "bad device ordinal");
+
+  const size_t nY = (size_t)B * n * d, nC = (size_t)B * d * r, nV = (size_t)B * r * r, nx = (size_t)B * np, nP = (size_t)B * np * np;
+  const size_t nX = (size_t)B * n * np, nS = (size_t)B * n * 2;
+  Dev<double> dY, dC, dV, dx, dP, dA, dQ, dH, dX, dYp, dSc;
+  Dev<int> dErr;
+  Event e0, e1;
+  std::vector<int> herr(B, 0);
+  HIP_TRY(w, hipSetDevice(cfg->device));
+  ALLOC_TRY(w, dY.alloc(nY * 8));
+  ALLOC_TRY(w, dC.alloc(nC * 8));
+  ALLOC_TRY(w, dV.alloc(nV * 8));
+  ALLOC_TRY(w, dx.alloc(nx * 8));
+  ALLOC_TRY(w, dP.alloc(nP * 8));
+  ALLOC_TRY(w, dA.alloc((size_t)np * np * 8));
+  ALLOC_TRY(w, dQ.alloc((size_t)np * np * 8));
+  ALLOC_TRY(w, dH.alloc((size_t)r * np * 8));
+  ALLOC_TRY(w, dX.alloc(nX * 8));
+  ALLOC_TRY(w, dErr.alloc((size_t)B * 4));
+  if (cfg->want_pred) ALLOC_TRY(w, dYp.alloc(nY * 8));
+  if (scalars) ALLOC_TRY(w, dSc.alloc(nS * 8));
+  HIP_TRY(w, hipMemcpy(dY, Y, nY * 8, hipMemcpyHostToDevice));
+  HIP_TRY(w, hipMemcpy(dC, C, nC * 8, hipMemcpyHostToDevice));
+  HIP_TRY(w, hipMemcpy(dV, V, nV * 8, hipMemcpyHostToDevice));
+  HIP_TRY(w, hipMemcpy(dx, x, nx * 8, hipMemcpyHostToDevice));
+  HIP_TRY(w, hipMemcpy(dP, P, nP * 8, hipMemcpyHostToDevice));
+  HIP_TRY(w, hipMemcpy(dA, A, (size_t)np * np * 8, hipMemcpyHostToDevice));
+  HIP_TRY(w, hipMemcpy(dQ, Q, (size_t)np * np * 8, hipMemcpyHostToDevice));
+  HIP_TRY(w, hipMemcpy(dH, H, (size_t)r * np * 8, hipMemcpyHostToDevice));
+  SsmParams sp;
+  sp.d = d; sp.n = n; sp.r = r; sp.p = np; sp.carry_P = cfg->carry_P != 0; sp.first_step = cfg->first_step != 0; sp.rho = rho;
+  sp.Y = dY; sp.C = dC; sp.V = dV; sp.x = dx; sp.P = dP; sp.A = dA; sp.Q = dQ; sp.H = dH; sp.X = dX;
+  sp.Ypred = cfg->want_pred ? dYp.get() : nullptr; sp.scal = scalars ? dSc.get() : nullptr; sp.err = dErr;
+  const void* const kern = (const void*)psmf_ssm_kernel;
+  if (lds > 48 * 1024) HIP_TRY(w, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  HIP_TRY(w, hipEventCreate(e0.put()));
+  HIP_TRY(w, hipEventCreate(e1.put()));
+  HIP_TRY(w, hipEventRecord(e0, 0));
+  { void* args[] = {&sp}; HIP_TRY(w, hipLaunchKernel(kern, dim3(B), dim3(WG), args, lds, 0)); }
+  HIP_TRY(w, hipGetLastError());
+  HIP_TRY(w, hipEventRecord(e1, 0));
+  HIP_TRY(w, hipEventSynchronize(e1));
+  if (elapsed_ms) HIP_TRY(w, hipEventElapsedTime(elapsed_ms, e0, e1));
+  HIP_TRY(w, hipMemcpy(C, dC, nC * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(w, hipMemcpy(V, dV, nV * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(w, hipMemcpy(x, dx, nx * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(w, hipMemcpy(P, dP, nP * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(w, hipMemcpy(X, dX, nX * 8, hipMemcpyDeviceToHost));
+  if (cfg->want_pred) HIP_TRY(w, hipMemcpy(Ypred, dYp, nY * 8, hipMemcpyDeviceToHost));
+  if (scalars) HIP_TRY(w, hipMemcpy(scalars, dSc, nS * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(w, hipMemcpy(herr.data(), dErr, (size_t)B * 4, hipMemcpyDeviceToHost));
+  // Per-replica outcome, as psmf_impute_run: a replica whose r x r system lost positive definiteness, or whose state is not finite, gets
+  // PSMF_ERR_NUMERIC; the other replicas are untouched by it (one workgroup each).  Without a status array it fails the call.
+  for (int b = 0; b < B; ++b) {
+    bool bad = herr[b] != 0;
+    for (int i = 0; i < np && !bad; ++i) bad = !std::isfinite(x[(size_t)b * np + i]);
+    for (size_t i = 0; i < (size_t)d * r && !bad; ++i) bad = !std::isfinite(C[(size_t)b * d * r + i]);
+    if (status) status[b] = bad ? PSMF_ERR_NUMERIC : PSMF_OK;
+    if (bad && !status) return fail(PSMF_ERR_NUMERIC, "the r x r system lost positive definiteness, or the state is not finite, in replica " + std::to_string(b));
+  }
+  return PSMF_OK;
+}
