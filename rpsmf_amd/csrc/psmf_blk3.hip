@@ -84,7 +84,7 @@ struct F3Lds {
   double* rowbufY;  // 4 RM
   int* errflag;
   long long* tick;  // 2: loop start / loop end (s_memrealtime), diagnostics
-  long long* acc;   // F3A_*: counters and tick sums of a chained launch (thread 0 only), flushed to DevState where the launch ends
+  long long* acc;   // F3A_*: counters and tick sums of a chained launch (wave 0 alone touches them), flushed to DevState where the launch ends
   long long* hand;  // chain carry: [0] sequence number of the next block, [1] 1: wave 6 saw its cross-Gram announced (f3_chain_next)
 };
 
@@ -115,11 +115,16 @@ struct F3Blk {
 // Chain carry (BlockParams::carry, filter3 only).  Between two blocks of ONE launch nobody but this workgroup reads the r x r
 // state, so it does not travel through the DevState dump (global stores that the hand-off has to drain, an L2 round trip to read
 // them back): every wave parks what it holds in LDS that is idle at a block boundary and picks it up in its next prologue.
-//   Xc (wave c's column of its iterate)   dump, parity 0, the wave's own slot            [e][lane]
-//   Xa (its float32 A operands)           dumpP, the wave's own slot of both parities    [e >> 3][.][e & 7][lane]
-//   G (wave 0), W (wave 2)                dump, parity 1: the slots of waves 0-1 / 2-3   [e][lane]   (as the dump: one writer each)
-//   V (wave 4), the scalars               the sweep images (nothing sweeps at a boundary)
+//   Xc (wave c's column of its iterate)   dump, parity 0, the wave's own slot            [e][lane]           | [e / 2][lane][2]
+//   Xa (its float32 A operands)           dumpP, the wave's own slot of both parities    [e >> 3][.][e & 7][lane] | [e >> 3][.][(e >> 2) & 1][lane][4]
+//   G (wave 0), W (wave 2)                dump, parity 1: the slots of waves 0-1 / 2-3   [e][lane]           | [e / 2][lane][2]   (one writer each)
+//   V (wave 4), the scalars               the sweep images (nothing sweeps at a boundary) [t][lane]          | [t / 2][lane][2]
 //   mu_bar                                stays in L.mub
+// Two layouts (f3_carry_d, f3_carry_xa).  Left: psmf_blk_filter3s, an element per read and write.  Right (WIDE): psmf_blk_filter3,
+// a lane's elements in 16-byte pieces -- parking and pick-up are ds_write_b128 / ds_read_b128, a quarter-wave per 256 bytes and
+// no bank conflict, half (doubles) or a quarter (floats) of the instructions.  WIDE is a compile-time property of the kernel:
+// everything that shortens the carried boundary (docs/MEASUREMENTS.md) is built into psmf_blk_filter3 alone, and the other four
+// kernels of the family compile to the instructions they had before it.
 // The dump, the images and dumpP are read for the last time before the barrier of the block end and written next behind the
 // first step's B1; the K assembly touches none of them.  DevState gets the state where the launch ends (f3_ns_dump, f3_v0_dump).
 enum { F3C_IQW = 0, F3C_IOM, F3C_PSCALE, F3C_Q, F3C_RHO, F3C_LAM, F3C_PHI, F3C_OMEGA, F3C_EE, F3C_S, F3C_ETA, F3C_N };
@@ -141,7 +146,13 @@ __device__ __forceinline__ F3Carry f3_carry(const F3Lds& L) {
   c.sc = L.img + 16 * 64;
   return c;
 }
-__device__ __forceinline__ int f3_carry_xa(const int role, const int e, const int lane) { return (((e >> 3) * 4 + role) * 8 + (e & 7)) * 64 + lane; }
+// element e of a lane's doubles (Xc: within the wave's slot) / of its float32 A operands (within dumpP)
+template <bool WIDE>
+__device__ __forceinline__ int f3_carry_d(const int e, const int lane) { return WIDE ? (e >> 1) * 128 + 2 * lane + (e & 1) : e * 64 + lane; }
+template <bool WIDE>
+__device__ __forceinline__ int f3_carry_xa(const int role, const int e, const int lane) {
+  return WIDE ? ((((e >> 3) * 4 + role) * 2 + ((e >> 2) & 1)) * 64 + lane) * 4 + (e & 3) : (((e >> 3) * 4 + role) * 8 + (e & 7)) * 64 + lane;
+}
 
 // The inversion waves' share of the DevState dump (valid while ns_valid == 3): what a later launch, or the host, starts from
 __device__ __forceinline__ void f3_ns_dump(DevState* st, const int role, const int lane, const double (&Xc)[8], const float (&Xa)[16],
@@ -193,6 +204,7 @@ __device__ __forceinline__ void f3_v0_dump(DevState* st, const F3Lds& L, const i
 
 // A chained launch that ends between two blocks (dead hand-off): the state of the blocks completed, parked in LDS, goes to
 // DevState as a block that does not carry would have left it.  Called by the whole workgroup behind a barrier.
+template <bool WIDE>
 __device__ __forceinline__ void f3_carry_flush(const BlockParams& b, const F3Lds& L, const long long kdone, const int tid) {
   DevState* st = b.sp.st;
   const int role = tid >> 6, lane = tid & 63;
@@ -201,14 +213,14 @@ __device__ __forceinline__ void f3_carry_flush(const BlockParams& b, const F3Lds
     double Xc[8], G[16], Wf[16];
     float Xa[16];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) Xc[e] = cy.Xc[role * 512 + e * 64 + lane];
+    for (int e = 0; e < 8; ++e) Xc[e] = cy.Xc[role * 512 + f3_carry_d<WIDE>(e, lane)];
 #pragma unroll
-    for (int e = 0; e < 16; ++e) { Xa[e] = cy.Xa[f3_carry_xa(role, e, lane)]; G[e] = cy.G[e * 64 + lane]; Wf[e] = cy.W[e * 64 + lane]; }
+    for (int e = 0; e < 16; ++e) { Xa[e] = cy.Xa[f3_carry_xa<WIDE>(role, e, lane)]; G[e] = cy.G[f3_carry_d<WIDE>(e, lane)]; Wf[e] = cy.W[f3_carry_d<WIDE>(e, lane)]; }
     f3_ns_dump(st, role, lane, Xc, Xa, G, Wf, cy.sc[F3C_IQW]);
   } else if (role == 4) {
     double V[16], sc[12];
 #pragma unroll
-    for (int t = 0; t < 16; ++t) V[t] = cy.V[t * 64 + lane];
+    for (int t = 0; t < 16; ++t) V[t] = cy.V[f3_carry_d<WIDE>(t, lane)];
 #pragma unroll
     for (int i = 0; i < 12; ++i) sc[i] = cy.sc[i];
     f3_v0_dump(st, L, b.sp.r, lane, kdone, false, V, sc);
@@ -217,8 +229,8 @@ __device__ __forceinline__ void f3_carry_flush(const BlockParams& b, const F3Lds
 
 // Diagnostics of a chained launch (F3Lds::acc).  One launch per block adds its counters and tick sums to DevState when the block
 // ends; chained, that was five dependent global round trips of one lane between two blocks with all eight waves waiting at the
-// hand-off behind it.  The host reads cnt / dbg after a launch has ended, so a chained launch sums in LDS (thread 0 writes and
-// reads every word) and adds the sums to DevState once: after its last block, or where a dead hand-off ends it.
+// hand-off behind it.  The host reads cnt / dbg after a launch has ended, so a chained launch sums in LDS (wave 0 writes and
+// reads every word: psmf_blk_filter3 one lane per word, blk_filter3_body) and adds the sums to DevState once: after its last block, or where a dead hand-off ends it.
 enum { F3A_CNT = 0, F3A_DUR = 4, F3A_GAP, F3A_TEND, F3A_BLOCKS, F3A_DBG = 8, F3A_BLK = 13, F3A_N = 17 };   // F3A_BLK: this block's cnt[0..3]
 __device__ __forceinline__ void f3_acc_flush(DevState* st, const long long* a) {
 #pragma unroll
@@ -304,8 +316,11 @@ __device__ __forceinline__ bool f3_xg_ahead(const F3Blk& k, const F3Lds& L, F3XG
 }
 
 // ahead (f3_xg_ahead): x was fetched, and its upper part staged in sX, in front of the hand-off's barrier
+// WIDE: the layout of the parked G (F3Carry); close = false (WIDE only): the caller has more LDS words to set up and ends the
+// assembly with its own barrier (blk_filter3_body)
+template <bool WIDE>
 __device__ __forceinline__ void f3_assemble_K(const BlockParams& b, const F3Blk& k, const F3Lds& L, const int r, const int tid, F3XG& x,
-                                              const bool ahead) {
+                                              const bool ahead, const bool close) {
   const int nb = k.nb, lane = tid & 63, w = tid >> 6, lrow = lane >> 4, lcol = lane & 15;
   double* sK = L.sK;
   double* sA = L.sA;
@@ -317,7 +332,7 @@ __device__ __forceinline__ void f3_assemble_K(const BlockParams& b, const F3Blk&
   double gv[2];
 #pragma unroll
   for (int u = 0; u < 2; ++u)                                                  // tracked G of the previous block (T-layout dump: an
-    gv[u] = k.from_lds ? f3_carry(L).G[(w + 8 * u) * 64 + lane]                // assembled block always follows a filter3 block);
+    gv[u] = k.from_lds ? f3_carry(L).G[f3_carry_d<WIDE>(w + 8 * u, lane)]      // assembled block always follows a filter3 block);
                        : st->f3_G[(w + 8 * u) * 64 + lane];                    // chain carry: where wave 0 parked it
   if (!ahead) f3_xg_fetch(x, k.XG, nb, tid);
   double ap[F3_AP_TRIPS];
@@ -363,7 +378,26 @@ __device__ __forceinline__ void f3_assemble_K(const BlockParams& b, const F3Blk&
       if (i < r && c < nb) { sK[i * RB + r + c] = acc[q]; sK[(r + c) * RB + i] = acc[q]; }
     }
   }
-  f3_barrier();               // (LDS order is all that is needed; __syncthreads() would make wave 6 wait for its flag store's acknowledgement)
+  if (!WIDE || close) f3_barrier();    // (LDS order is all that is needed; __syncthreads() would make wave 6 wait for its flag store's acknowledgement)
+}
+
+// A_B (RB x r, row-major) from its LDS staging to global memory by the four vector waves, coalesced: thread t of the 256 stores
+// the elements t, t + 256, ... in that order.  The staging address of (m, c) = (idx / r, idx mod r) is carried from trip to trip
+// instead of divided out in each: the step (256 / r, 256 mod r) is one division of uniform values, and the first pair comes from
+// a float32 reciprocal -- with x = (t + 1/2) / r the fractional part of x lies in [1 / 2r, 1 - 1 / 2r], at least 1 / 64 from an
+// integer, and the rounding of the reciprocal and of the product moves x < 2^8 by less than 2^-13: the truncation is
+// floor(t / r) exactly.
+__device__ __forceinline__ void f3_store_Acoef(double* Acoef, const double* sA, const int r, const int t) {
+  // (the step is uniform: scalar registers; the staging address m F3_AS + c is carried as one word beside c)
+  const float ir = __builtin_amdgcn_rcpf((float)r);
+  const int qs = __builtin_amdgcn_readfirstlane(256 / r), cs = 256 - qs * r, as = qs * F3_AS + cs;
+  const int m = (int)(((float)t + 0.5f) * ir);
+  int c = t - m * r, at = m * F3_AS + c;
+  for (int idx = t; idx < RB * r; idx += 256) {
+    coef_store(Acoef + idx, sA[at]);
+    c += cs; at += as;
+    if (c >= r) { c -= r; at += F3_AS - r; }
+  }
 }
 
 // Knock-out switches for tools/blk3_knock.hip (timing what each piece costs on the critical path; results are wrong
@@ -508,6 +542,7 @@ __device__ __forceinline__ void f3_ns_program(const BlockParams& b, const F3Blk&
   float Xa[16];                             // float32 A operands of the correction product (see f3_ns_iter)
   const int pcol = (lcol >> 2) + 4 * (lcol & 3);     // pi(lcol)       // Wf: W of the last step (zero outside r x r): Lbar = (I / q - W / q^2) / omega
   const bool from_lds = k.from_lds != 0;     // chain carry (implies carried): nothing below reads DevState
+  constexpr bool WIDE = FULL != 2;           // psmf_blk_filter3: F3Carry in 16-byte pieces (filter3s: an element per access)
   const F3Carry cy = f3_carry(L);
   const double q0 = from_lds ? 0.0 : st->Q[0];
   F3Mask<FULL> mk;
@@ -526,7 +561,7 @@ __device__ __forceinline__ void f3_ns_program(const BlockParams& b, const F3Blk&
         const int e = (ti * 2 + tj) * 4 + qq;
         G[e] = in ? L.sK[row * RB + col] : 0.0;                              // G_0: exact Gram of the stored C / tracked G
         if (from_lds) {
-          Wf[e] = cy.W[e * 64 + lane];
+          if (!WIDE) Wf[e] = cy.W[e * 64 + lane];       // (WIDE: picked up below, two elements per read)
         } else if (carried) {
           Wf[e] = st->f3_W[e * 64 + lane];
         } else {
@@ -538,14 +573,29 @@ __device__ __forceinline__ void f3_ns_program(const BlockParams& b, const F3Blk&
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     const int row = 16 * (e >> 2) + lrow + 4 * (e & 3);
-    if (from_lds) Xc[e] = cy.Xc[role * 512 + e * 64 + lane];
+    if (from_lds) { if (!WIDE) Xc[e] = cy.Xc[role * 512 + e * 64 + lane]; }
     else Xc[e] = carried ? st->f3_Xc[role][e * 64 + lane] : (row == 16 * C + lcol ? 1.0 : 0.0);
   }
 #pragma unroll
   for (int e = 0; e < 16; ++e) {
     const int row = 16 * ((e >> 2) & 1) + lrow + 4 * (e & 3), cp = 16 * (e >> 3) + pcol;
-    if (from_lds) Xa[e] = cy.Xa[f3_carry_xa(role, e, lane)];
+    if (from_lds) { if (!WIDE) Xa[e] = cy.Xa[f3_carry_xa<false>(role, e, lane)]; }
     else Xa[e] = carried ? st->f3_Xa[role][e * 64 + lane] : (row == cp ? 1.f : 0.f);
+  }
+  if (WIDE && from_lds) {
+    // chain carry: W, the own column and its A operands as the block before parked them (F3Carry), 16 bytes per read
+    const f64x2* w2 = reinterpret_cast<const f64x2*>(cy.W) + lane;
+    const f64x2* x2 = reinterpret_cast<const f64x2*>(cy.Xc + role * 512) + lane;
+    const f32x4s* a4 = reinterpret_cast<const f32x4s*>(cy.Xa) + lane;
+#pragma unroll
+    for (int e = 0; e < 16; e += 2) { const f64x2 v = w2[(e >> 1) * 64]; Wf[e] = v[0]; Wf[e + 1] = v[1]; }
+#pragma unroll
+    for (int e = 0; e < 8; e += 2) { const f64x2 v = x2[(e >> 1) * 64]; Xc[e] = v[0]; Xc[e + 1] = v[1]; }
+#pragma unroll
+    for (int e = 0; e < 16; e += 4) {
+      const f32x4s v = a4[f3_carry_xa<true>(role, e, 0) >> 2];
+      Xa[e] = v[0]; Xa[e + 1] = v[1]; Xa[e + 2] = v[2]; Xa[e + 3] = v[3];
+    }
   }
   if (isX) {
     // <G_0, P> and tr G_0 of the own column, for eta of the first step (Pbar_1 = P + q I); carried: P = beta omega P+
@@ -876,18 +926,38 @@ __device__ __forceinline__ void f3_ns_program(const BlockParams& b, const F3Blk&
   const double ps = L.sc[F3_PSCALE], iom = L.sc[F3_IOM];
   if (k.to_lds) {
     // chain carry: the next block of this launch picks the state up from LDS (every reader of the dump is behind the barrier above)
+    if (WIDE) {
+      f64x2* x2 = reinterpret_cast<f64x2*>(cy.Xc + role * 512) + lane;
+      f32x4s* a4 = reinterpret_cast<f32x4s*>(cy.Xa) + lane;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) cy.Xc[role * 512 + e * 64 + lane] = Xc[e];
+      for (int e = 0; e < 8; e += 2) x2[(e >> 1) * 64] = f64x2{Xc[e], Xc[e + 1]};
 #pragma unroll
-    for (int e = 0; e < 16; ++e) cy.Xa[f3_carry_xa(role, e, lane)] = Xa[e];
-    if (role == 0) {
+      for (int e = 0; e < 16; e += 4) a4[f3_carry_xa<true>(role, e, 0) >> 2] = f32x4s{Xa[e], Xa[e + 1], Xa[e + 2], Xa[e + 3]};
+      if (role == 0) {
+        f64x2* g2 = reinterpret_cast<f64x2*>(cy.G) + lane;
 #pragma unroll
-      for (int e = 0; e < 16; ++e) cy.G[e * 64 + lane] = G[e];
-      if (lane == 0) cy.sc[F3C_IQW] = iq_w;
-    }
-    if (role == 2) {
+        for (int e = 0; e < 16; e += 2) g2[(e >> 1) * 64] = f64x2{G[e], G[e + 1]};
+        if (lane == 0) cy.sc[F3C_IQW] = iq_w;
+      }
+      if (role == 2) {
+        f64x2* w2 = reinterpret_cast<f64x2*>(cy.W) + lane;
 #pragma unroll
-      for (int e = 0; e < 16; ++e) cy.W[e * 64 + lane] = Wf[e];
+        for (int e = 0; e < 16; e += 2) w2[(e >> 1) * 64] = f64x2{Wf[e], Wf[e + 1]};
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) cy.Xc[role * 512 + e * 64 + lane] = Xc[e];
+#pragma unroll
+      for (int e = 0; e < 16; ++e) cy.Xa[f3_carry_xa<false>(role, e, lane)] = Xa[e];
+      if (role == 0) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) cy.G[e * 64 + lane] = G[e];
+        if (lane == 0) cy.sc[F3C_IQW] = iq_w;
+      }
+      if (role == 2) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) cy.W[e * 64 + lane] = Wf[e];
+      }
     }
   } else {
     f3_ns_dump(st, role, lane, Xc, Xa, G, Wf, iq_w);
@@ -921,7 +991,7 @@ __device__ __forceinline__ void f3_ns_program(const BlockParams& b, const F3Blk&
 // ------------------------------------------------------------------------------------------------------------
 // Program of the four vector waves: 4 = V and every scalar, 5 = A by rows, 6 = KA by rows, 7 = A^T by columns.
 // ------------------------------------------------------------------------------------------------------------
-template <int ROLE>
+template <int ROLE, bool WIDE>       // WIDE: psmf_blk_filter3 (see F3Carry)
 __device__ __forceinline__ void f3_v_program(const BlockParams& b, const F3Blk& k, const F3Lds& L, const int lane, const bool carried) {
   const StepParams& p = b.sp;
   DevState* st = p.st;
@@ -950,7 +1020,10 @@ __device__ __forceinline__ void f3_v_program(const BlockParams& b, const F3Blk& 
     const int j = lane & 31, hf = lane >> 5;
     if (from_lds) {
 #pragma unroll
-      for (int t = 0; t < 16; ++t) pr[t] = cy.V[t * 64 + lane];
+      for (int t = 0; t < 16; t += 2) {
+        if (WIDE) { const f64x2 v = reinterpret_cast<const f64x2*>(cy.V)[(t >> 1) * 64 + lane]; pr[t] = v[0]; pr[t + 1] = v[1]; }
+        else { pr[t] = cy.V[t * 64 + lane]; pr[t + 1] = cy.V[(t + 1) * 64 + lane]; }
+      }
       iom0 = cy.sc[F3C_IOM];
       pscale = cy.sc[F3C_PSCALE];
     } else if (carried) {
@@ -1148,6 +1221,13 @@ __device__ __forceinline__ void f3_v_program(const BlockParams& b, const F3Blk& 
       }
     }
     if (poll && lane == 0) L.hand[1] = (poll_ab == 0 && poll_xg >= L.hand[0]) ? 1 : 0;
+    // A_B: wave 5's rows are final here in the block's last timestep, and nothing inside a step reads sA (the assembly is done
+    // with it before the first one).  Staged now, BF orders the rows for the four vector waves, whose coefficient stores then
+    // leave in FRONT of the barrier of the block end and drain beside the inversion waves' last W and traces.
+    if (WIDE && isV1 && jb == k.nb - 1) {
+#pragma unroll
+      for (int c = 0; c < 32; ++c) L.sA[lane * F3_AS + c] = pr[c];       // (a strided global store per column took ~4 us)
+    }
     BLK_T(3);
     if (!done) {
       f3_barrier();                                                   // ---- B3
@@ -1177,10 +1257,13 @@ __device__ __forceinline__ void f3_v_program(const BlockParams& b, const F3Blk& 
   if (role == 4 && lane == 0) L.tick[1] = (long long)__builtin_amdgcn_s_memrealtime();
 
   // ---- block end ----
+  // A_B (wave 5's rows) leaves through LDS: all four vector waves store it, coalesced.  WIDE: staged in the last timestep
+  // (phase 2; a block has at least one: the host cuts a run into ceil(steps / B) blocks), stored in front of the barrier
+  if (WIDE) f3_store_Acoef(k.Acoef, L.sA, r, tid - 256);
   if (isV0) {
     if (k.nb > 0) F3_V0_FINISH_PREV();
     if (lane == 0) { L.sc[F3_PSCALE] = pscale; L.sc[F3_IOM] = fast_rcp(omega); L.sc[F3_Q] = q; }
-  } else if (isV1) {
+  } else if (!WIDE && isV1) {
 #pragma unroll
     for (int c = 0; c < 32; ++c) L.sA[lane * F3_AS + c] = pr[c];       // (a strided global store per column took ~4 us)
   }
@@ -1192,7 +1275,10 @@ __device__ __forceinline__ void f3_v_program(const BlockParams& b, const F3Blk& 
     if (k.to_lds) {
       // chain carry: V and the scalars wait in the sweep images (mu_bar stays in L.mub); sc[F3C_IQW] is wave 0's
 #pragma unroll
-      for (int t = 0; t < 16; ++t) cy.V[t * 64 + lane] = pr[t];
+      for (int t = 0; t < 16; t += 2) {
+        if (WIDE) reinterpret_cast<f64x2*>(cy.V)[(t >> 1) * 64 + lane] = f64x2{pr[t], pr[t + 1]};
+        else { cy.V[t * 64 + lane] = pr[t]; cy.V[(t + 1) * 64 + lane] = pr[t + 1]; }
+      }
       if (lane == 0) {
 #pragma unroll
         for (int i = 1; i < 12; ++i) cy.sc[i] = sc[i];
@@ -1202,8 +1288,8 @@ __device__ __forceinline__ void f3_v_program(const BlockParams& b, const F3Blk& 
     }
     if (lane == 0 && *L.errflag && st->err == 0) st->err = (int)(k.k0 + 1);
   }
-  // A_B (wave 5's rows) left through LDS before the barrier above: all four vector waves store it, coalesced
-  for (int idx = tid - 256; idx < RB * r; idx += 256) { const int m = idx / r, c = idx - m * r; coef_store(k.Acoef + idx, L.sA[m * F3_AS + c]); }
+  // (filter3s: A_B left through LDS before the barrier above)
+  if (!WIDE) for (int idx = tid - 256; idx < RB * r; idx += 256) { const int m = idx / r, c = idx - m * r; coef_store(k.Acoef + idx, L.sA[m * F3_AS + c]); }
 #undef F3_V0_FINISH_PREV
 }
 

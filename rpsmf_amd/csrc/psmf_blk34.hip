@@ -65,6 +65,9 @@ __device__ __forceinline__ void blk_filter3_body(const BlockParams& b0) {
   // Chain carry (KIND 0): between the blocks of one launch the state stays on chip (F3Carry); DevState gets it where the launch ends.
   const int nchain = b0.chain > 1 ? b0.chain : 1;
   const bool carry = KIND == 0 && b0.chain > 1 && b0.carry != 0;
+  // WIDE: psmf_blk_filter3 itself.  What shortens the boundary between two carried blocks (F3Carry in 16-byte pieces, one barrier
+  // behind the assembly, the diagnostics one lane per word, A_B staged and stored early) is compiled into this kernel alone.
+  constexpr bool WIDE = KIND == 0 && !SMALL;
   const bool acc_lds = b0.chain > 1;      // the diagnostics of a chained launch are summed in LDS (f3_acc_flush)
   if (tid0 == 0) {
 #pragma unroll
@@ -107,7 +110,7 @@ __device__ __forceinline__ void blk_filter3_body(const BlockParams& b0) {
   if (j > 0) {
     if (carry && b0.xg_ahead) ahead = f3_xg_ahead(k, L, xg, tid);
     if (!(carry ? f3_chain_next(b0, L, seq) : blk_chain_next(b0, seq))) {
-      if (k.from_lds) f3_carry_flush(b0, L, k.k0, tid);                // the blocks completed, as they would have left DevState
+      if (k.from_lds) f3_carry_flush<WIDE>(b0, L, k.k0, tid);                // the blocks completed, as they would have left DevState
       if (tid == 0) f3_acc_flush(st, L.acc);
       return;
     }
@@ -129,12 +132,30 @@ __device__ __forceinline__ void blk_filter3_body(const BlockParams& b0) {
     if (pf == 1.2345e300) hot[0] = pf;                                 // (keeps the loads; never true)
   }
   const long long t_h = (long long)__builtin_amdgcn_s_memrealtime();
+  // psmf_blk_filter3: a block that arrives through LDS (chain carry, j > 0) has ONE barrier between the hand-off and the prologues: the assembly
+  // leaves its closing barrier to the one behind the LDS set-up below.  The set-up then runs beside the assembly, behind the
+  // hand-off's barrier only, so every word it writes must have been read for the last time IN FRONT of that barrier:
+  //   errflag           read by the sweeps (inside a step) and by wave 4 at the block end, in front of its drain;
+  //   hand[0]           read by wave 6 in phase 2 of the last timestep;
+  //   acc[F3A_BLK..]    read by wave 0 behind its block end, in front of the hand-off;
+  //   w, h, sc          read inside the steps; sc[F3_PSCALE], sc[F3_IOM] once more by waves 0-4 between the barrier of the block
+  //                     end and the hand-off;
+  //   the K image       read inside the steps (wave 6) and nowhere behind them.
+  // hand[1] is the exception: every wave reads it BEHIND the hand-off's barrier (f3_chain_next), so it is not reset here -- and
+  // need not be.  It is 0 already unless the hand-off was the fast one; a block that hands on rewrites it in its last timestep
+  // (wave 6's poll, ordered by BF and the barrier of the block end) before f3_xg_ahead / f3_chain_next read it again; behind the
+  // last block of a launch nobody reads it, and the next launch starts from 0.
+  const bool one_barrier = WIDE && k.from_lds != 0;
   if (!assemble) {
     for (int idx = tid; idx < RB * RB; idx += F3_NT) L.sK[idx] = b.K[idx];
   } else {
-    f3_assemble_K(b, k, L, r, tid, xg, ahead);
+    f3_assemble_K<WIDE>(b, k, L, r, tid, xg, ahead, !one_barrier);
   }
-  if (tid == 0) { *L.errflag = 0; L.hand[0] = seq + 1; L.hand[1] = 0; L.acc[F3A_BLK] = 0; L.acc[F3A_BLK + 1] = 0; L.acc[F3A_BLK + 2] = 0; L.acc[F3A_BLK + 3] = 0; }
+  if (tid == 0) {
+    *L.errflag = 0; L.hand[0] = seq + 1;
+    if (!one_barrier) L.hand[1] = 0;
+    L.acc[F3A_BLK] = 0; L.acc[F3A_BLK + 1] = 0; L.acc[F3A_BLK + 2] = 0; L.acc[F3A_BLK + 3] = 0;
+  }
   // filter4, a block that follows another one in the same launch: h, w, ee, N, kappa and (a, b) of that block's last step stay
   // where they are in LDS -- the first step's start predictor uses them
   const bool warm = KIND == 1 && j > 0;      // (filter5 has no start to predict)
@@ -217,16 +238,39 @@ __device__ __forceinline__ void blk_filter3_body(const BlockParams& b0) {
       else f3_ns_program<0, 1>(b, k, L, inv, role, lane, carried);
     }
   } else {
-    if (role == 4) f3_v_program<4>(b, k, L, lane, carried);
-    else if (role == 5) f3_v_program<5>(b, k, L, lane, carried);
-    else if (role == 6) f3_v_program<6>(b, k, L, lane, carried);
-    else f3_v_program<7>(b, k, L, lane, carried);
+    if (role == 4) f3_v_program<4, WIDE>(b, k, L, lane, carried);
+    else if (role == 5) f3_v_program<5, WIDE>(b, k, L, lane, carried);
+    else if (role == 6) f3_v_program<6, WIDE>(b, k, L, lane, carried);
+    else f3_v_program<7, WIDE>(b, k, L, lane, carried);
   }
-  if (tid == 0) {
+  if (WIDE && acc_lds) {
+    // psmf_blk_filter3, chained: the sums of F3Lds::acc, ONE LANE PER WORD.  (Thread 0 alone made fourteen dependent LDS read-modify-writes here,
+    // between two blocks, with seven waves waiting at the hand-off's barrier.)  Wave 0 holds the block's stamps in scalar
+    // registers; every lane reads the two ticks of the step loop, the end of the block before and its own word in one group,
+    // forms what its word gains and writes it once.  64-bit integers throughout: the sums are what thread 0 formed.
+    if (role == 0) {
+      static_assert(F3A_CNT == 0 && F3A_DUR == 4 && F3A_GAP == 5 && F3A_TEND == 6 && F3A_BLOCKS == 7 && F3A_DBG == 8 && F3A_BLK == 13, "one lane per word of F3Lds::acc");
+      const long long t_end = (long long)__builtin_amdgcn_s_memrealtime();
+      long long* a = L.acc;
+      const int wd = lane < F3A_BLK ? lane : 0;
+      const long long tk0 = L.tick[0], tk1 = L.tick[1], tend0 = a[F3A_TEND], old = a[wd], blk = a[F3A_BLK + (lane & 3)];
+      long long add = blk;                                                      // F3A_CNT + i: this block's counters
+      if (wd == F3A_DUR) add = t_end - t_begin;
+      if (wd == F3A_GAP) add = tend0 != 0 ? t_begin - tend0 : 0;                // (the first block of a handle's life has no gap)
+      if (wd == F3A_TEND) add = t_end - old;                                    // (the word becomes t_end)
+      if (wd == F3A_BLOCKS) add = 1;
+      if (wd == F3A_DBG) add = t_h - t_begin;
+      if (wd == F3A_DBG + 1) add = t_a - t_h;
+      if (wd == F3A_DBG + 2) add = tk0 - t_a;
+      if (wd == F3A_DBG + 3) add = tk1 - tk0;
+      if (wd == F3A_DBG + 4) add = t_end - tk1;
+      if (lane < F3A_BLK) a[wd] = old + add;
+    }
+  } else if (tid == 0) {
     // cnt[4]: sum of in-kernel durations, cnt[5]: sum of the gaps to the previous filter kernel, cnt[7]: launches (10 ns ticks)
     const long long t_end = (long long)__builtin_amdgcn_s_memrealtime();
     const long long dt[5] = {t_h - t_begin, t_a - t_h, L.tick[0] - t_a, L.tick[1] - L.tick[0], t_end - L.tick[1]};
-    if (acc_lds) {
+    if (acc_lds) {            // (the other kernels of the family, chained: the same sums by thread 0, as they were)
       long long* a = L.acc;
 #pragma unroll
       for (int i = 0; i < 4; ++i) a[F3A_CNT + i] += a[F3A_BLK + i];
