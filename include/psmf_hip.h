@@ -447,6 +447,51 @@ int psmf_ssm_run(const psmf_ssm_config* cfg, const double* Y, double* C, double*
                  const double* Q, const double* H, double rho, double* X, double* Ypred, double* scalars, int32_t* status,
                  float* elapsed_ms);
 
+/* psmf_ssm_run with the robust form (rPSMF: a t-distributed likelihood, ExperimentImpute/rPSMF.py:75-135 and
+ * pypsmf/psmf/rpsmf.py:125-172) and with missing observations.  psmf_ssm_config's fields, then: */
+typedef struct {
+  int32_t abi_version;
+  int32_t d, n, r;
+  int32_t p;
+  int32_t batch;
+  int32_t device;
+  int32_t carry_P;
+  int32_t first_step;
+  int32_t want_pred;
+  int32_t robust;        /* 1: rPSMF -- the lines marked rob below                                           */
+  int32_t fixed_lambda;  /* 1: lambda stays lambda0; 0: lambda <- lambda + d after every step                */
+  double lambda0;        /* robust: degrees of freedom at the start of a series, finite and > 0              */
+  double alpha, beta;    /* robust: the factors of V and of P (finite and > 0; 1 = the reference)            */
+} psmf_ssm_config_ex;
+
+/* Per replica and step t, float64 throughout; m is the 0/1 mask column (all ones with mask = NULL), M = diag(m), Omega the running
+ * product of omega (1 at the start of a series, and always when not robust), e_i zero on unobserved rows:
+ *   xbar = A x                         Pbar = A P_prev A^T + Omega Q            (carry_P as in psmf_ssm_run)
+ *   z = H xbar, w = V z, s = z^T w     yhat = C z                               (Ypred: all rows, observed or not)
+ *   e_i = m_i (y_i - yhat_i)           y_i is not read where m_i = 0 (it may be NaN)
+ *   P_z = H Pbar H^T                   rho_t = Omega rho
+ *   S = (M C) P_z (M C)^T + diag(rho_t m) + s I                                 (rPSMF.py:92-98: s I, not s M)
+ *   x = xbar + Pbar H^T (MC)^T S^-1 e
+ *   omega = (lambda + e^T S^-1 e) / (lambda + d)                           rob  (d, not the observed count)
+ *   P = beta omega (Pbar - Pbar H^T (MC)^T S^-1 (MC) H Pbar)               rob: beta omega; else 1
+ *   eta = (rho_t sum m_i + trace((MC) P_z (MC)^T)) / d,   N = s + eta
+ *   C += e w^T / N                                                              (unobserved rows do not move)
+ *   phi = (lambda + e^T e / N) / (lambda + d)                              rob
+ *   V = alpha phi (V - w w^T / N)                                          rob: alpha phi; else 1
+ *   Omega <- omega Omega;  lambda <- lambda + d unless fixed_lambda        rob
+ * (S is never formed: G = sum m_i c_i c_i^T, h = sum m_i c_i e_i, the two r x r inversions of psmf_ssm_run, and
+ * e^T S^-1 e = kappa e^T e - kappa^2 h^T P_z+ h.)  With robust = 0 and mask = NULL the call runs psmf_ssm_run's own kernel (the same
+ * bits).  Limits and arguments as psmf_ssm_run, and:
+ *   mask          batch x n x d uint8 (row t = m_t), 0 or 1, or NULL: all observed.  A step without an observed row is
+ *                 PSMF_ERR_ARG (eta = 0 and phi = 0 / 0 there); the message names the replica and the step
+ *   robust_state  batch x 2, in / out: (lambda, Omega) per replica -- what a continuing call takes.  Read when first_step = 0; with
+ *                 first_step = 1 the call starts from (lambda0, 1).  May be NULL when not robust
+ *   scalars       batch x n x 4 or NULL: (s, eta, omega, phi) of every step (omega = phi = 1 when not robust)
+ * PSMF_ERR_ARG also for robust with lambda0 <= 0 or not finite, and alpha or beta <= 0. */
+int psmf_ssm_run_ex(const psmf_ssm_config_ex* cfg, const double* Y, const uint8_t* mask, double* C, double* V, double* x, double* P,
+                    const double* A, const double* Q, const double* H, double rho, double* robust_state, double* X, double* Ypred,
+                    double* scalars, int32_t* status, float* elapsed_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,7 @@
 
     from rpsmf_amd import PSMFIter, rPSMFIter, PSMFRecursive, rPSMFRecursive
     from rpsmf_amd.impute import ProbabilisticSequentialMatrixFactorizer, robust_PSMF
-    from rpsmf_amd.ssm import PSMF, linear_psmf_batch, matern32_state_space
+    from rpsmf_amd.ssm import PSMF, rPSMF, linear_psmf_batch, matern32_state_space
 
 The device path (backend="hip", default) needs rpsmf_amd/lib/libpsmf_hip.so
 (`python -m rpsmf_amd.build`) and a gfx950 GPU; it never falls back to the CPU.

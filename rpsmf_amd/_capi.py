@@ -44,6 +44,11 @@ class PsmfSsmConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("abi_version", "d", "n", "r", "p", "batch", "device", "carry_P", "first_step", "want_pred")]
 
 
+class PsmfSsmConfigEx(C.Structure):
+    _fields_ = PsmfSsmConfig._fields_ + [("robust", C.c_int32), ("fixed_lambda", C.c_int32), ("lambda0", C.c_double), ("alpha", C.c_double),
+                                         ("beta", C.c_double)]
+
+
 _dp = C.POINTER(C.c_double)
 _u8p = C.POINTER(C.c_uint8)
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, _dp, C.c_int64)   # psmf_allreduce_fn
@@ -94,6 +99,8 @@ SIGNATURES = {
     "psmf_impute_kernel_id": (C.c_int, [C.POINTER(PsmfImputeConfig)]),
     "psmf_ssm_run": (C.c_int, [C.POINTER(PsmfSsmConfig), _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_double, _dp, _dp, _dp,
                                C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
+    "psmf_ssm_run_ex": (C.c_int, [C.POINTER(PsmfSsmConfigEx), _dp, _u8p, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_double, _dp, _dp, _dp, _dp,
+                                  C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
     "psmf_comm_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "psmf_device_pci_bus_id": (C.c_int, [C.c_int, C.c_char_p, C.c_int]),
     "psmf_upload_mask": (C.c_int, [C.c_void_p, _u8p, C.c_int64, C.c_int64]),

@@ -24,6 +24,7 @@
 #include "psmf_wave16.hip"    // wave_sweep16m, Sw16K
 
 #include <cmath>
+#include <type_traits>
 #include <string>
 #include <vector>
 
@@ -51,6 +52,14 @@ struct SsmParams {
   int* err;                // batch
 };
 
+// what the robust and the masked instances take beside it
+struct SsmParamsEx : SsmParams {
+  const unsigned char* mask;   // batch x n x d, 1 = observed (masked instances)
+  double* rstate;              // batch x 2: (lambda, Omega) in / out (robust instances)
+  double lambda0, alpha, beta;
+  int fixed_lambda;
+};
+
 __host__ __device__ inline size_t ssm_lds_doubles(int d) {
   const size_t d4 = ((size_t)d + 3) & ~(size_t)3;
   return d4 * SR + SR * SR                 // C, V
@@ -64,12 +73,27 @@ __host__ __device__ inline size_t ssm_lds_doubles(int d) {
          + 8 + 2;                          // scalars, error flag
 }
 inline size_t ssm_lds_bytes(int d) { return (ssm_lds_doubles(d) * 8 + 15) & ~(size_t)15; }
+// the masked instances keep the step's mask column in front of it, a byte per row (at a fixed place: 512 bytes whatever d is)
+constexpr int SSM_MASK_BYTES = 2 * WG;
+inline size_t ssm_lds_bytes(int d, bool masked) { return ssm_lds_bytes(d) + (masked ? SSM_MASK_BYTES : 0); }
 
 __device__ __forceinline__ void ssm_barrier() { solve_barrier<true>(); }
 
-__global__ __launch_bounds__(WG) void psmf_ssm_kernel(SsmParams p) {
+// ROB: rPSMF (ExperimentImpute/rPSMF.py:75-135, pypsmf/psmf/rpsmf.py:125-172).  Omega is the running product of omega (Q and rho are
+// scaled by it), lambda the degrees of freedom:
+//   Pbar = A P_prev A^T + Omega Q,  rho_t = Omega rho,  omega = (lambda + e^T S^-1 e) / (lambda + d),  P = beta omega (...)
+//   phi = (lambda + e^T e / N) / (lambda + d),  V = alpha phi (V - w w^T / N),  Omega <- omega Omega,  lambda <- lambda + d unless fixed
+// with e^T S^-1 e = kappa e^T e - kappa^2 h^T P_z+ h (S^-1 = kappa I - kappa^2 C_m P_z+ C_m^T).
+// MSK: a 0/1 mask column m per step (a byte per row, prefetched with y): e_i = m_i (y_i - yhat_i) by selection, so that a NaN under a
+// zero never enters; G = sum m_i c_i c_i^T, h = sum m_i c_i e_i (the mask multiplies the Gram's operand);
+// eta = (rho_t sum m_i + <G, P_z>) / d; S keeps s I on every row (rPSMF.py:97-98), and yhat is written for every row.
+// sum m_i is counted by ballot in phase 3; e^T e is reduced beside the Gram in phase 5 (waves 1-3), so phi is there for the update of V
+// in phase 7; omega comes from wave 2, idle in phase 9, ahead of the store of P in phase 10 and of the next step's Omega Q and rho_t:
+// the step has the plain instance's ten barriers and not one more.  With both off the step loop is the plain one, statement for statement.
+template <bool ROB, bool MSK>
+__global__ __launch_bounds__(WG) void psmf_ssm_kernel(typename std::conditional<ROB || MSK, SsmParamsEx, SsmParams>::type p) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  double* sm = reinterpret_cast<double*>(smem_raw);
+  double* sm = reinterpret_cast<double*>(smem_raw + (MSK ? SSM_MASK_BYTES : 0));
   const int d = p.d, n = p.n, r = p.r, np = p.p, tid = threadIdx.x, rep = blockIdx.x;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lane = tid & 63, lk = lane >> 4, lr = lane & 15;
@@ -101,6 +125,8 @@ __global__ __launch_bounds__(WG) void psmf_ssm_kernel(SsmParams p) {
   double* syh = se + d4;                     // d4
   double* ssc = syh + d4;                    // 8 scalars: 0 s, 1 eta, 2 N, 3 kappa
   int* errflag = reinterpret_cast<int*>(ssc + 8);
+  double* sxt = su + SR;                     // (the spare vector) robust / masked instances: 0-2 e^T e of waves 1-3, 3 omega, 4-7 sum m_i per wave, 8-9 the next lambda, 1 / (lambda + d)
+  unsigned char* smk = reinterpret_cast<unsigned char*>(smem_raw);      // masked instances: the mask column of the step, 512 bytes
 
   const double* Yg = p.Y + (size_t)rep * n * d;
   double* Cg = p.C + (size_t)rep * d * r;
@@ -112,6 +138,8 @@ __global__ __launch_bounds__(WG) void psmf_ssm_kernel(SsmParams p) {
   {
     const int total = (int)ssm_lds_doubles(d);
     for (int idx = tid; idx < total; idx += WG) sm[idx] = 0.0;
+    if constexpr (MSK)
+      for (int idx = tid; idx < SSM_MASK_BYTES; idx += WG) smk[idx] = 0;
   }
   __syncthreads();
   for (int idx = tid; idx < d * r; idx += WG) { const int i = idx / r, l = idx - i * r; sC[i * SR + l] = Cg[idx]; }
@@ -142,6 +170,21 @@ __global__ __launch_bounds__(WG) void psmf_ssm_kernel(SsmParams p) {
     rowc[u] = min(tid + u * WG, d - 1);
     ny[u] = Yg[rowc[u]];
   }
+  // the mask column of a step stands in LDS (smk): the one of step t + 1 is prefetched beside y's row t + 1 and replaces it in phase 10,
+  // which no longer reads the present one (phases 3 and 5 do)
+  const unsigned char* Mg = nullptr;
+  if constexpr (MSK) {
+    Mg = p.mask + (size_t)rep * n * d;
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+      if (tid + u * WG < d) smk[tid + u * WG] = Mg[tid + u * WG];
+  }
+  if constexpr (ROB)       // Omega, lambda and 1 / (lambda + d) of the step: ssc[4-6], moved on by one thread in phase 10 (nobody reads them there)
+    if (tid == 0) {
+      ssc[4] = p.first_step ? 1.0 : p.rstate[2 * rep + 1];
+      ssc[5] = p.first_step ? p.lambda0 : p.rstate[2 * rep];
+      ssc[6] = 1.0 / (ssc[5] + (double)d);
+    }
   // The p x p products run on the float64 matrix cores, one 16 x 16 output tile per wave (first row ti, first column tj): the A operand
   // of v_mfma_f64_16x16x4_f64 is element (row lr, k-slot lk), the B operand (k-slot lk, column lr), the result rows lk + 4 q of column
   // lr.  The p x r products (Pbar H^T, its product with W) are the two tiles of waves 0 and 1.  Of the r x r products a thread forms
@@ -158,7 +201,18 @@ __global__ __launch_bounds__(WG) void psmf_ssm_kernel(SsmParams p) {
 #pragma unroll
       for (int u = 0; u < 2; ++u) ny[u] = Yg[base + rowc[u]];
     }
+    unsigned char nm[2] = {1, 1};
+    if constexpr (MSK) {
+      const unsigned char* mrow = Mg + (size_t)min(t + 1, n - 1) * d;
+#pragma unroll
+      for (int u = 0; u < 2; ++u) nm[u] = mrow[(unsigned)rowc[u]];
+    }
     const bool usep = p.carry_P || (p.first_step && t == 0);      // else P_prev = 0: Pbar = Q
+    if constexpr (ROB || MSK) {       // wave 0's values of phases 5-6 hold no registers outside them: these instances have none to spare
+#pragma unroll
+      for (int q = 0; q < 4; ++q) A1[q] = Pzr[q] = 0.0;
+      s = kappa = 0.0;
+    }
     // ---- phase 1: T = A P_prev; xbar = A x ----
     if (usep) {
       f64x4 acc = {0.0, 0.0, 0.0, 0.0};
@@ -178,7 +232,7 @@ __global__ __launch_bounds__(WG) void psmf_ssm_kernel(SsmParams p) {
     {
       f64x4 acc;
 #pragma unroll
-      for (int q = 0; q < 4; ++q) acc[q] = sQ[(ti + lk + 4 * q) * SLA + tj + lr];
+      for (int q = 0; q < 4; ++q) acc[q] = ROB ? ssc[4] * sQ[(ti + lk + 4 * q) * SLA + tj + lr] : sQ[(ti + lk + 4 * q) * SLA + tj + lr];
       if (usep)
         for (int kk = 0; kk < p4; kk += 4)
           acc = __builtin_amdgcn_mfma_f64_16x16x4f64(sT[(ti + lr) * SLA + kk + lk], sA[(tj + lr) * SLA + kk + lk], acc, 0, 0, 0);
@@ -206,9 +260,11 @@ __global__ __launch_bounds__(WG) void psmf_ssm_kernel(SsmParams p) {
       for (int l = 0; l < SR; l += 2) { a0 = fma(sV[lane * SR + l], sz[l], a0); a1 = fma(sV[lane * SR + l + 1], sz[l + 1], a1); }
       sw[lane] = a0 + a1;
     }
+    int nobs = 0;       // masked instances: the observed rows of this wave
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const int i = tid + u * WG;
+      if constexpr (MSK) nobs += __popcll(__ballot(i < d && smk[i] != 0));
       if (i < d) {
         double cr[SR], zr[SR];
 #pragma unroll
@@ -218,7 +274,12 @@ __global__ __launch_bounds__(WG) void psmf_ssm_kernel(SsmParams p) {
         for (int l = 0; l < SR; l += 2) { d0 = fma(cr[l], zr[l], d0); d1 = fma(cr[l + 1], zr[l + 1], d1); }
         const double dot = d0 + d1;
         syh[i] = dot;
-        se[i] = yv[u] - dot;
+        if constexpr (MSK) {
+          se[i] = smk[i] ? yv[u] - dot : 0.0;
+          if (lane == 0) sxt[4 + wv] = (double)nobs;       // (with u = 1 the sum of both halves)
+        } else {
+          se[i] = yv[u] - dot;
+        }
       }
     }
     ssm_barrier();
@@ -233,7 +294,7 @@ __global__ __launch_bounds__(WG) void psmf_ssm_kernel(SsmParams p) {
     // ---- phase 5: wave 0: s, kappa, -P_z^-1 (needs no Gram); waves 1-3: the augmented Gram [C | e]^T [C | e] on the matrix cores ----
     if (wv == 0) {
       s = wave_sum_f64_dpp(lane < SR ? sz[lane & 15] * sw[lane & 15] : 0.0);
-      kappa = fast_rcp(rho + s);
+      kappa = fast_rcp((ROB ? ssc[4] * rho : rho) + s);
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int i = lk + 4 * q;
@@ -244,14 +305,26 @@ __global__ __launch_bounds__(WG) void psmf_ssm_kernel(SsmParams p) {
 #pragma unroll
       for (int q = 0; q < 4; ++q) sPzi[(lk + 4 * q) * SR + lr] = inq[q] ? -A1[q] : 0.0;
     } else {
+      if constexpr (ROB)       // the next step's lambda and 1 / (lambda + d), in the shorter half of the phase; phase 10 moves them in
+        if (tid == 192) {
+          const double ln = p.fixed_lambda ? ssc[5] : ssc[5] + (double)d;
+          sxt[8] = ln;
+          sxt[9] = 1.0 / (ln + (double)d);
+        }
       f64x4 acc1 = {0.0, 0.0, 0.0, 0.0}, acc2 = {0.0, 0.0, 0.0, 0.0};
+      double ee = 0.0;       // robust: this wave's share of e^T e, beside the Gram (wave 0's inversion is the longer half of the phase)
       const int ngrp = d4 >> 2;
       for (int g = wv - 1; g < ngrp; g += 3) {
         const int k = 4 * g + lk;                                     // < d4: padding rows hold zeros
-        const double cval = sC[k * SR + lr], ek = se[k];
+        const double cval = MSK ? sC[k * SR + lr] * (smk[k] ? 1.0 : 0.0) : sC[k * SR + lr], ek = se[k];
         const double a = cval + ((one_tile && lr == r) ? ek : 0.0);   // augmented column r: e (C is zero there)
         acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a, a, acc1, 0, 0, 0);
         if (!one_tile) acc2 = __builtin_amdgcn_mfma_f64_16x16x4f64(a, lr == 0 ? ek : 0.0, acc2, 0, 0, 0);
+        if constexpr (ROB) ee = fma(lr == 0 ? ek : 0.0, ek, ee);
+      }
+      if constexpr (ROB) {
+        ee = wave_sum_f64_dpp(ee);
+        if (lane == 0) sxt[wv - 1] = ee;
       }
       double* o = sgp + (size_t)(wv - 1) * 512;
 #pragma unroll
@@ -267,7 +340,14 @@ __global__ __launch_bounds__(WG) void psmf_ssm_kernel(SsmParams p) {
         G[q] = inq[q] ? g0 : 0.0;
         tr += G[q] * Pzr[q];
       }
-      const double eta = fma(wave_sum_f64_dpp(tr), idd, rho);
+      const double rho_t = ROB ? ssc[4] * rho : rho;
+      double eta;
+      if constexpr (MSK) {
+        const double cnt = (sxt[4] + sxt[5]) + (sxt[6] + sxt[7]);       // sum m_i
+        eta = fma(wave_sum_f64_dpp(tr), idd, cnt == (double)d ? rho_t : rho_t * (cnt * idd));
+      } else {
+        eta = fma(wave_sum_f64_dpp(tr), idd, rho_t);
+      }
       if (lane == 0) { ssc[0] = s; ssc[1] = eta; ssc[2] = s + eta; ssc[3] = kappa; }
       double A2[4];
 #pragma unroll
@@ -302,7 +382,13 @@ __global__ __launch_bounds__(WG) void psmf_ssm_kernel(SsmParams p) {
         const int i = idx >> 4, l = idx & 15;
         sC[idx] = fma(se[i], sw[l] * wsc, sC[idx]);
       }
-      sV[rk0 * SR + rc] = fma(-sw[rk0] * wsc, sw[rc], sV[rk0 * SR + rc]);
+      if constexpr (ROB) {
+        const double phi = fma((sxt[0] + sxt[1]) + sxt[2], wsc, ssc[5]) * ssc[6];
+        sV[rk0 * SR + rc] = (p.alpha * phi) * fma(-sw[rk0] * wsc, sw[rc], sV[rk0 * SR + rc]);
+        if (tid == 64) ssc[7] = phi;
+      } else {
+        sV[rk0 * SR + rc] = fma(-sw[rk0] * wsc, sw[rc], sV[rk0 * SR + rc]);
+      }
     }
     ssm_barrier();
     // ---- phase 8: W = kappa sym(B G), u = kappa B h ----
@@ -332,6 +418,18 @@ __global__ __launch_bounds__(WG) void psmf_ssm_kernel(SsmParams p) {
       bad |= !isfinite(xn);
       sx[lane] = xn;                             // (rows >= p of Pbar H^T and of xbar are zero)
     }
+    if constexpr (ROB)
+      if (wv == 2) {       // (the idle wave of this phase) omega = (lambda + kappa e^T e - kappa^2 h^T P_z+ h) / (lambda + d)
+        double b0 = 0.0, b1 = 0.0;
+        const int i = lane & 15;
+#pragma unroll
+        for (int k = 0; k < SR; k += 2) { b0 = fma(sPp[i * SR + k], sh[k], b0); b1 = fma(sPp[i * SR + k + 1], sh[k + 1], b1); }
+        const double hph = wave_sum_f64_dpp(lane < SR ? sh[i] * (b0 + b1) : 0.0);
+        const double kap = ssc[3];
+        const double om = (ssc[5] + kap * (((sxt[0] + sxt[1]) + sxt[2]) - kap * hph)) * ssc[6];
+        bad |= !(om > 0.0) || !isfinite(om);
+        if (lane == 0) sxt[3] = om;
+      }
     if (wv < 2) {
       f64x4 acc = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
@@ -349,8 +447,18 @@ __global__ __launch_bounds__(WG) void psmf_ssm_kernel(SsmParams p) {
 #pragma unroll
       for (int kk = 0; kk < SR; kk += 4)
         acc = __builtin_amdgcn_mfma_f64_16x16x4f64(-sT[(ti + lr) * SLH + kk + lk], sPH[(tj + lr) * SLH + kk + lk], acc, 0, 0, 0);
+      if constexpr (ROB) {
+        const double bom = p.beta * sxt[3];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc[q] *= bom;
+      }
 #pragma unroll
       for (int q = 0; q < 4; ++q) sP[(ti + lk + 4 * q) * SLA + tj + lr] = acc[q];
+    }
+    if constexpr (MSK) {
+#pragma unroll
+      for (int u = 0; u < 2; ++u)
+        if (tid + u * WG < d) smk[tid + u * WG] = nm[u];
     }
     if (tid < np) Xg[(size_t)t * np + tid] = sx[tid];
     if (p.Ypred) {
@@ -360,12 +468,28 @@ __global__ __launch_bounds__(WG) void psmf_ssm_kernel(SsmParams p) {
         if (i < d) p.Ypred[((size_t)rep * n + t) * d + i] = syh[i];
       }
     }
-    if (p.scal && tid == 64) {
+    if constexpr (ROB || MSK) {       // four scalars per step: (s, eta, omega, phi)
+      if (p.scal && tid == 64) {
+        double* o = p.scal + ((size_t)rep * n + t) * 4;
+        o[0] = ssc[0];
+        o[1] = ssc[1];
+        o[2] = ROB ? sxt[3] : 1.0;
+        o[3] = ROB ? ssc[7] : 1.0;
+      }
+    } else if (p.scal && tid == 64) {
       p.scal[((size_t)rep * n + t) * 2] = ssc[0];
       p.scal[((size_t)rep * n + t) * 2 + 1] = ssc[1];
     }
+    if constexpr (ROB)
+      if (tid == 64) {
+        ssc[4] *= sxt[3];
+        ssc[5] = sxt[8];
+        ssc[6] = sxt[9];
+      }
     ssm_barrier();
   }
+  if constexpr (ROB)
+    if (tid == 0) { p.rstate[2 * rep] = ssc[5]; p.rstate[2 * rep + 1] = ssc[4]; }
   if (tid == 0) *errflag = 0;
   __syncthreads();
   for (int idx = tid; idx < d * r; idx += WG) { const int i = idx / r, l = idx - i * r; Cg[idx] = sC[i * SR + l]; }
@@ -379,17 +503,23 @@ __global__ __launch_bounds__(WG) void psmf_ssm_kernel(SsmParams p) {
 
 }  // namespace psmf
 
-extern "C" int psmf_ssm_run(const psmf_ssm_config* cfg, const double* Y, double* C, double* V, double* x, double* P, const double* A,
-                            const double* Q, const double* H, double rho, double* X, double* Ypred, double* scalars, int32_t* status,
-                            float* elapsed_ms) {
-  using namespace psmf;
-  const struct {
-    int operator()(int code, const std::string& msg) const { g_create_error = "psmf_ssm_run: " + msg; return code; }
+namespace psmf {
+namespace {
+
+// psmf_ssm_run (ex = false: `scalars` is batch x n x 2, no mask, not robust) and psmf_ssm_run_ex (batch x n x 4)
+int ssm_run(const char* who, bool ex, const psmf_ssm_config_ex* cfg, const double* Y, const uint8_t* mask, double* C, double* V, double* x,
+            double* P, const double* A, const double* Q, const double* H, double rho, double* robust_state, double* X, double* Ypred,
+            double* scalars, int32_t* status, float* elapsed_ms) {
+  struct Fail {
+    const char* who;
+    int operator()(int code, const std::string& msg) const { g_create_error = std::string(who) + ": " + msg; return code; }
     int operator()(psmf_handle, int code, const std::string& msg) const { return (*this)(code, msg); }
-  } fail{};
+  };
+  const Fail fail{who};
   const psmf_handle w = nullptr;
   if (!cfg || !Y || !C || !V || !x || !P || !A || !Q || !H || !X) return fail(PSMF_ERR_ARG, "null argument");
   if (cfg->abi_version != PSMF_ABI_VERSION) return fail(PSMF_ERR_ARG, "ABI version mismatch");
+  const bool robust = cfg->robust != 0, masked = mask != nullptr;
   const int d = cfg->d, n = cfg->n, r = cfg->r, np = cfg->p, B = cfg->batch;
   if (d < 1 || d > 2 * WG)
     return fail(PSMF_ERR_ARG, "need 1 <= d <= 512 (one workgroup per replica holds C in LDS; d = " + std::to_string(d) + ")");
@@ -399,7 +529,30 @@ extern "C" int psmf_ssm_run(const psmf_ssm_config* cfg, const double* Y, double*
   if (n < 1 || B < 1) return fail(PSMF_ERR_ARG, "need n >= 1 and batch >= 1");
   if (cfg->want_pred && !Ypred) return fail(PSMF_ERR_ARG, "want_pred needs Ypred");
   if (!std::isfinite(rho) || rho < 0.0) return fail(PSMF_ERR_ARG, "rho must be finite and >= 0 (R = rho I)");
-  const size_t lds = ssm_lds_bytes(d);
+  if (robust) {
+    if (!std::isfinite(cfg->lambda0) || cfg->lambda0 <= 0.0) return fail(PSMF_ERR_ARG, "robust needs a finite lambda0 > 0");
+    if (!std::isfinite(cfg->alpha) || cfg->alpha <= 0.0 || !std::isfinite(cfg->beta) || cfg->beta <= 0.0)
+      return fail(PSMF_ERR_ARG, "alpha and beta must be finite and > 0");
+    if (!robust_state) return fail(PSMF_ERR_ARG, "robust needs robust_state (batch x 2: lambda, Omega)");
+    if (!cfg->first_step)
+      for (int b = 0; b < B; ++b) {
+        const double l = robust_state[2 * b], o = robust_state[2 * b + 1];
+        if (!std::isfinite(l) || l <= 0.0 || !std::isfinite(o) || o <= 0.0)
+          return fail(PSMF_ERR_ARG, "robust_state needs finite lambda > 0 and Omega > 0 (replica " + std::to_string(b) + ")");
+      }
+  }
+  if (masked)       // every step needs an observed row: eta = 0 and phi = 0 / 0 otherwise
+    for (int b = 0; b < B; ++b)
+      for (int t = 0; t < n; ++t) {
+        const uint8_t* m = mask + ((size_t)b * n + t) * d;
+        int cnt = 0;
+        for (int i = 0; i < d; ++i) {
+          if (m[i] > 1) return fail(PSMF_ERR_ARG, "the mask must hold 0 and 1 only (replica " + std::to_string(b) + ", step " + std::to_string(t) + ")");
+          cnt += m[i];
+        }
+        if (cnt == 0) return fail(PSMF_ERR_ARG, "no observed row in replica " + std::to_string(b) + ", step " + std::to_string(t) + ": every step needs at least one");
+      }
+  const size_t lds = ssm_lds_bytes(d, masked);
   if (lds > 160 * 1024) return fail(PSMF_ERR_ARG, "the replica's state needs more than 160 KB of LDS");
   {
     // Q: symmetric positive definite (Cholesky on the host, p <= 32)
@@ -429,8 +582,10 @@ extern "C" int psmf_ssm_run(const psmf_ssm_config* cfg, const double* Y, double*
   if (cfg->device < 0 || cfg->device >= ndev) return fail(PSMF_ERR_ARG, "bad device ordinal");
 
   const size_t nY = (size_t)B * n * d, nC = (size_t)B * d * r, nV = (size_t)B * r * r, nx = (size_t)B * np, nP = (size_t)B * np * np;
-  const size_t nX = (size_t)B * n * np, nS = (size_t)B * n * 2;
-  Dev<double> dY, dC, dV, dx, dP, dA, dQ, dH, dX, dYp, dSc;
+  const bool plain = !robust && !masked;       // the plain instance writes two scalars per step
+  const size_t nX = (size_t)B * n * np, nS = (size_t)B * n * (plain ? 2 : 4);
+  Dev<double> dY, dC, dV, dx, dP, dA, dQ, dH, dX, dYp, dSc, dRs;
+  Dev<unsigned char> dM;
   Dev<int> dErr;
   Event e0, e1;
   std::vector<int> herr(B, 0);
@@ -455,16 +610,28 @@ extern "C" int psmf_ssm_run(const psmf_ssm_config* cfg, const double* Y, double*
   HIP_TRY(w, hipMemcpy(dA, A, (size_t)np * np * 8, hipMemcpyHostToDevice));
   HIP_TRY(w, hipMemcpy(dQ, Q, (size_t)np * np * 8, hipMemcpyHostToDevice));
   HIP_TRY(w, hipMemcpy(dH, H, (size_t)r * np * 8, hipMemcpyHostToDevice));
-  SsmParams sp;
+  if (masked) {
+    ALLOC_TRY(w, dM.alloc(nY));
+    HIP_TRY(w, hipMemcpy(dM, mask, nY, hipMemcpyHostToDevice));
+  }
+  if (robust) {
+    ALLOC_TRY(w, dRs.alloc((size_t)B * 2 * 8));
+    if (!cfg->first_step) HIP_TRY(w, hipMemcpy(dRs, robust_state, (size_t)B * 2 * 8, hipMemcpyHostToDevice));
+  }
+  SsmParamsEx sp;
   sp.d = d; sp.n = n; sp.r = r; sp.p = np; sp.carry_P = cfg->carry_P != 0; sp.first_step = cfg->first_step != 0; sp.rho = rho;
   sp.Y = dY; sp.C = dC; sp.V = dV; sp.x = dx; sp.P = dP; sp.A = dA; sp.Q = dQ; sp.H = dH; sp.X = dX;
   sp.Ypred = cfg->want_pred ? dYp.get() : nullptr; sp.scal = scalars ? dSc.get() : nullptr; sp.err = dErr;
-  const void* const kern = (const void*)psmf_ssm_kernel;
+  sp.mask = masked ? dM.get() : nullptr; sp.rstate = robust ? dRs.get() : nullptr;
+  sp.lambda0 = cfg->lambda0; sp.alpha = cfg->alpha; sp.beta = cfg->beta; sp.fixed_lambda = cfg->fixed_lambda != 0;
+  SsmParams sp0 = sp;       // what the plain instance takes
+  const void* const kern = robust ? (masked ? (const void*)psmf_ssm_kernel<true, true> : (const void*)psmf_ssm_kernel<true, false>)
+                                  : (masked ? (const void*)psmf_ssm_kernel<false, true> : (const void*)psmf_ssm_kernel<false, false>);
   if (lds > 48 * 1024) HIP_TRY(w, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   HIP_TRY(w, hipEventCreate(e0.put()));
   HIP_TRY(w, hipEventCreate(e1.put()));
   HIP_TRY(w, hipEventRecord(e0, 0));
-  { void* args[] = {&sp}; HIP_TRY(w, hipLaunchKernel(kern, dim3(B), dim3(WG), args, lds, 0)); }
+  { void* args[] = {plain ? (void*)&sp0 : (void*)&sp}; HIP_TRY(w, hipLaunchKernel(kern, dim3(B), dim3(WG), args, lds, 0)); }
   HIP_TRY(w, hipGetLastError());
   HIP_TRY(w, hipEventRecord(e1, 0));
   HIP_TRY(w, hipEventSynchronize(e1));
@@ -476,6 +643,12 @@ extern "C" int psmf_ssm_run(const psmf_ssm_config* cfg, const double* Y, double*
   HIP_TRY(w, hipMemcpy(X, dX, nX * 8, hipMemcpyDeviceToHost));
   if (cfg->want_pred) HIP_TRY(w, hipMemcpy(Ypred, dYp, nY * 8, hipMemcpyDeviceToHost));
   if (scalars) HIP_TRY(w, hipMemcpy(scalars, dSc, nS * 8, hipMemcpyDeviceToHost));
+  if (scalars && ex && plain)       // (s, eta) -> (s, eta, omega = 1, phi = 1), in place from the back
+    for (size_t i = (size_t)B * n; i-- > 0;) {
+      const double s0 = scalars[2 * i], s1 = scalars[2 * i + 1];
+      scalars[4 * i] = s0; scalars[4 * i + 1] = s1; scalars[4 * i + 2] = 1.0; scalars[4 * i + 3] = 1.0;
+    }
+  if (robust) HIP_TRY(w, hipMemcpy(robust_state, dRs, (size_t)B * 2 * 8, hipMemcpyDeviceToHost));
   HIP_TRY(w, hipMemcpy(herr.data(), dErr, (size_t)B * 4, hipMemcpyDeviceToHost));
   // Per-replica outcome, as psmf_impute_run: a replica whose r x r system lost positive definiteness, or whose state is not finite, gets
   // PSMF_ERR_NUMERIC; the other replicas are untouched by it (one workgroup each).  Without a status array it fails the call.
@@ -487,4 +660,24 @@ extern "C" int psmf_ssm_run(const psmf_ssm_config* cfg, const double* Y, double*
     if (bad && !status) return fail(PSMF_ERR_NUMERIC, "the r x r system lost positive definiteness, or the state is not finite, in replica " + std::to_string(b));
   }
   return PSMF_OK;
+}
+
+}  // namespace
+}  // namespace psmf
+
+extern "C" int psmf_ssm_run(const psmf_ssm_config* cfg, const double* Y, double* C, double* V, double* x, double* P, const double* A,
+                            const double* Q, const double* H, double rho, double* X, double* Ypred, double* scalars, int32_t* status,
+                            float* elapsed_ms) {
+  psmf_ssm_config_ex c{};
+  if (cfg) {
+    c.abi_version = cfg->abi_version; c.d = cfg->d; c.n = cfg->n; c.r = cfg->r; c.p = cfg->p; c.batch = cfg->batch; c.device = cfg->device;
+    c.carry_P = cfg->carry_P; c.first_step = cfg->first_step; c.want_pred = cfg->want_pred;
+  }
+  return psmf::ssm_run("psmf_ssm_run", false, cfg ? &c : nullptr, Y, nullptr, C, V, x, P, A, Q, H, rho, nullptr, X, Ypred, scalars, status, elapsed_ms);
+}
+
+extern "C" int psmf_ssm_run_ex(const psmf_ssm_config_ex* cfg, const double* Y, const uint8_t* mask, double* C, double* V, double* x,
+                               double* P, const double* A, const double* Q, const double* H, double rho, double* robust_state, double* X,
+                               double* Ypred, double* scalars, int32_t* status, float* elapsed_ms) {
+  return psmf::ssm_run("psmf_ssm_run_ex", true, cfg, Y, mask, C, V, x, P, A, Q, H, rho, robust_state, X, Ypred, scalars, status, elapsed_ms);
 }
