@@ -36,6 +36,11 @@ on unobserved rows:
 
 A step without an observed row is refused (ValueError): eta = 0 and phi = 0 / 0 there.
 
+Conditioning: the engine never forms the d x d matrix S; it forms P_z^-1 (r x r), so its error against the d x d recursion grows with
+cond(P_z) ~ cond(H)^2 cond(Pbar).  With a plain Gaussian H and p = r at 15 / 16 two float64 models of the recursion differ by 7e-10
+(d = 127, r = p = 15) and 1.1e-9 (d = 63, r = p = 16); with the singular values of H in [0.5, 1.5] (tests/ssm_net_cases.py) they agree to
+1e-11 and the device is within 1e-11 of the d x d model.
+
 `linear_psmf_batch` runs many independent series in one launch, one workgroup per replica (psmf_ssm_run and psmf_ssm_run_ex,
 include/psmf_hip.h: d <= 512, r <= 16, r <= p <= 32); `PSMF` and `rPSMF` keep the Matlab function's signature;
 `matern32_state_space` builds the (A, Q, H) of the experiment's Matern-3/2 prior from the closed form.  There is no CPU fallback.
