@@ -492,6 +492,55 @@ int psmf_ssm_run_ex(const psmf_ssm_config_ex* cfg, const double* Y, const uint8_
                     const double* A, const double* Q, const double* H, double rho, double* robust_state, double* X, double* Ypred,
                     double* scalars, int32_t* status, float* elapsed_ms);
 
+/* Batched multivariate Bayesian online change-point detection: the BOCPD baseline of the change-point experiment
+ * (ExperimentChange/MVBOCPD.m: a normal-inverse-Wishart model per run length, Student-t predictive, constant hazard h = 1 / lambda,
+ * and the reference's detection heuristic), float64 throughout, for a batch of independent series. */
+typedef struct {
+  int32_t abi_version;
+  int32_t dim, T;          /* samples of dimension dim, T of them per series: 1 <= dim <= 32, 1 <= T <= 4096     */
+  int32_t batch;           /* independent series                                                               */
+  int32_t device;
+  int32_t drop, settle, confirm;   /* the heuristic's constants (the reference: 10, 10, 10)                    */
+  int32_t max_changepoints;        /* change points stored per series (every one is counted)                   */
+  int32_t want_R;          /* also return every column of R                                                    */
+  int32_t want_logpred;    /* also return the log predictive of every (step, age)                              */
+  double lambda;           /* > 1: hazard h = 1 / lambda (the reference: 200)                                  */
+  double kappa0, nu0;      /* prior: kappa0 > 0, nu0 > dim - 1 (the reference: 1, dim)                         */
+  double sigma0;           /* prior scatter Sigma0 = sigma0 I, sigma0 > 0 (the reference: 1); mu0 = 0          */
+} psmf_bocpd_config;
+
+/* Per series, with time 1-based (t = 1 .. T) and n_t live hypotheses of ages 0 .. n_t - 1 at step t (n_1 = 1; a hypothesis of age a
+ * has absorbed the a most recent samples: kappa = kappa0 + a, nu = nu0 + a; absorbing x: delta = x - mu,
+ * mu <- (kappa mu + x) / (kappa + 1), Sigma <- Sigma + kappa / (2 (kappa + 1)) delta delta^T; age 0 is the prior):
+ *   1. log p_a = lgamma((nu + dim) / 2) - lgamma(nu / 2) + log det(c) / 2 - dim / 2 log(nu pi) - (nu + dim) / 2 log1p(delta^T c delta / nu),
+ *      c = [2 (kappa + 1) Sigma / (nu kappa)]^-1
+ *   2. R(a + 1, t + 1) = R(a, t) p_a (1 - h),  R(0, t + 1) = sum_a R(a, t) p_a h  over a < n_t, the column normalised to sum 1
+ *   3. m_t = 1 + argmax_a R(a, t) over the stored column t (lowest age on a tie)
+ *   4. for t > 1: m_t - m_{t-1} < -drop sets a flag; otherwise, with the flag set, |m_t - m_{t-1}| < settle counts up and the count
+ *      exceeding `confirm` declares the change point cp = t - m_t + 1, clears flag and count and discards the hypotheses of age
+ *      >= m_t - 1 (n_{t+1} = m_t); |m_t - m_{t-1}| >= settle clears flag and count
+ *   5. every remaining hypothesis absorbs x_t; a fresh prior enters at age 0
+ * R is carried in the log domain: a step at which every p_a underflows leaves it finite.  One lane per hypothesis holds the Cholesky
+ * factor of Sigma on chip (a forward substitution and a rank-one update per step, no inverse and no determinant); a second kernel
+ * runs the recursion on R, one workgroup per series.  A batch whose scratch (T x T doubles per series) exceeds what is free on
+ * the device is processed in chunks.
+ *   X             batch x T x dim, time-major
+ *   map_run       batch x T: m_t
+ *   changepoints  batch x max_changepoints: the first max_changepoints cp values of every series (the rest of a row is 0);
+ *                 may be NULL with max_changepoints = 0
+ *   n_changepoints  batch: how many were declared (it may exceed max_changepoints)
+ *   R_last        batch x (T + 1) or NULL: column T + 1 by age
+ *   R             batch x (T + 1) x (T + 1), row t - 1 = column t by age, zero where nothing is stored; want_R = 1, else NULL
+ *   logpred       batch x T x T, [t - 1][a] = log p_a of step t, NaN where age a is not live; want_logpred = 1, else NULL
+ *   status        batch int32 or NULL, as in psmf_ssm_run: PSMF_OK, or PSMF_ERR_NUMERIC for a replica with a non-finite sample,
+ *                 a non-finite state or a non-positive pivot (its other outputs are zero or unspecified); the other replicas are
+ *                 untouched by it.  With status = NULL such a replica fails the call (PSMF_ERR_NUMERIC)
+ *   elapsed_ms    the kernels alone (HIP events, summed over the chunks), or NULL
+ * PSMF_ERR_ARG, by message: dim > 32, T > 4096, batch < 1, lambda <= 1, kappa0 <= 0, nu0 <= dim - 1, sigma0 <= 0, and want_R or
+ * want_logpred with more than 2^28 doubles (2 GiB) of output. */
+int psmf_bocpd_run(const psmf_bocpd_config* cfg, const double* X, int32_t* map_run, int32_t* changepoints, int32_t* n_changepoints,
+                   double* R_last, double* R, double* logpred, int32_t* status, float* elapsed_ms);
+
 #ifdef __cplusplus
 }
 #endif

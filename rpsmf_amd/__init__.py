@@ -3,11 +3,13 @@
     from rpsmf_amd import PSMFIter, rPSMFIter, PSMFRecursive, rPSMFRecursive
     from rpsmf_amd.impute import ProbabilisticSequentialMatrixFactorizer, robust_PSMF
     from rpsmf_amd.ssm import PSMF, rPSMF, linear_psmf_batch, matern32_state_space
+    from rpsmf_amd.changepoint import MVBOCPD, mvbocpd_batch, find_changepoint
 
 The device path (backend="hip", default) needs rpsmf_amd/lib/libpsmf_hip.so
 (`python -m rpsmf_amd.build`) and a gfx950 GPU; it never falls back to the CPU.
 """
 
+from . import changepoint  # noqa: F401
 from .learning_rate import BaseLearningRate, ConstantLearningRate, ExponentialLearningRate  # noqa: F401
 from .nonlinearities import (BaseNonLinearity, CosPhase, FourierBasis, RandomWalk, ScaledWalk, Sinusoid,  # noqa: F401
                              wrap_nonlinearity)

@@ -44,6 +44,11 @@ class PsmfSsmConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("abi_version", "d", "n", "r", "p", "batch", "device", "carry_P", "first_step", "want_pred")]
 
 
+class PsmfBocpdConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("abi_version", "dim", "T", "batch", "device", "drop", "settle", "confirm", "max_changepoints",
+                                         "want_R", "want_logpred")] + [(n, C.c_double) for n in ("lam", "kappa0", "nu0", "sigma0")]
+
+
 class PsmfSsmConfigEx(C.Structure):
     _fields_ = PsmfSsmConfig._fields_ + [("robust", C.c_int32), ("fixed_lambda", C.c_int32), ("lambda0", C.c_double), ("alpha", C.c_double),
                                          ("beta", C.c_double)]
@@ -101,6 +106,8 @@ SIGNATURES = {
                                C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
     "psmf_ssm_run_ex": (C.c_int, [C.POINTER(PsmfSsmConfigEx), _dp, _u8p, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_double, _dp, _dp, _dp, _dp,
                                   C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
+    "psmf_bocpd_run": (C.c_int, [C.POINTER(PsmfBocpdConfig), _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp, _dp, _dp,
+                                 C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
     "psmf_comm_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "psmf_device_pci_bus_id": (C.c_int, [C.c_int, C.c_char_p, C.c_int]),
     "psmf_upload_mask": (C.c_int, [C.c_void_p, _u8p, C.c_int64, C.c_int64]),

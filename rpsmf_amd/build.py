@@ -7,7 +7,8 @@ The library is a handful of translation units, compiled side by side (at most 16
 per-step engine (psmf_capi.hip), the series buffers -- resident or a ring: uploads, downloads, reductions over stored rows --
 (psmf_series.hip), the blocked engine's host driver and kernels (psmf_blocked.hip), the filter3 family of block filters
 (psmf_filter34.hip), the masked small-shape engine (psmf_impute.hip), the persistent per-step engine (psmf_pstep.hip), the batched filter with
-linear-Gaussian dynamics and an observation map (psmf_ssm.hip), and the build identity (psmf_buildid.cpp: `psmf_build_id()` returns the SHA-256 of every source file and of the compiler flags the library was built
+linear-Gaussian dynamics and an observation map (psmf_ssm.hip), the batched Bayesian online change-point detection (psmf_bocpd.hip),
+and the build identity (psmf_buildid.cpp: `psmf_build_id()` returns the SHA-256 of every source file and of the compiler flags the library was built
 from).  An object is stale when the hash of what its source reaches through `#include "..."`, followed transitively, differs from the one
 it was compiled from -- no list of dependencies is kept by hand.  `build_library` rebuilds whenever the whole-library hash differs from
 the sources on disk -- modification times play no part -- and `source_hash()` / `library_build_id()` let `__graft_entry__.build()`
@@ -37,7 +38,8 @@ FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-Wno-unused-val
 FLAGS += os.environ.get("PSMF_CXXFLAGS", "").split()      # diagnostic builds (e.g. -DPSTEP_PROF); part of the build id
 LINK = ["-L/opt/rocm/lib", "-lrccl", "-Wl,-rpath,/opt/rocm/lib"]
 
-UNITS = ("psmf_capi.hip", "psmf_series.hip", "psmf_blocked.hip", "psmf_filter34.hip", "psmf_impute.hip", "psmf_pstep.hip", "psmf_ssm.hip")
+UNITS = ("psmf_capi.hip", "psmf_series.hip", "psmf_blocked.hip", "psmf_filter34.hip", "psmf_impute.hip", "psmf_pstep.hip", "psmf_ssm.hip",
+         "psmf_bocpd.hip")
 MAX_JOBS = 16
 
 
