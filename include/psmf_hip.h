@@ -533,8 +533,11 @@ typedef struct {
  *   R             batch x (T + 1) x (T + 1), row t - 1 = column t by age, zero where nothing is stored; want_R = 1, else NULL
  *   logpred       batch x T x T, [t - 1][a] = log p_a of step t, NaN where age a is not live; want_logpred = 1, else NULL
  *   status        batch int32 or NULL, as in psmf_ssm_run: PSMF_OK, or PSMF_ERR_NUMERIC for a replica with a non-finite sample,
- *                 a non-finite state or a non-positive pivot (its other outputs are zero or unspecified); the other replicas are
- *                 untouched by it.  With status = NULL such a replica fails the call (PSMF_ERR_NUMERIC)
+ *                 a non-finite state or a non-positive pivot; the other replicas are untouched by it.  Every other output of a
+ *                 replica with a non-finite sample or a non-finite log p_a (an overflowing sample, a non-positive pivot) is zero,
+ *                 R(0, 1) included: the recursion on R never starts.  (Only a log R that leaves the finite range with every
+ *                 log p_a finite is found after the outputs are written; they are unspecified then.)  With status = NULL such a
+ *                 replica fails the call (PSMF_ERR_NUMERIC)
  *   elapsed_ms    the kernels alone (HIP events, summed over the chunks), or NULL
  * PSMF_ERR_ARG, by message: dim > 32, T > 4096, batch < 1, lambda <= 1, kappa0 <= 0, nu0 <= dim - 1, sigma0 <= 0, and want_R or
  * want_logpred with more than 2^28 doubles (2 GiB) of output. */

@@ -24,6 +24,20 @@ The device keeps the Cholesky factor of Sigma per hypothesis (one forward substi
 no determinant) and carries R in the log domain: a step at which every p_a underflows in float64, where the reference's linear
 recursion turns into NaN, leaves it finite.  There is no CPU fallback.
 
+Accuracy: with a prior on the data's scale (sigma0 within a few powers of ten of the data's variance) log p is good to about 1e-12
+absolute and R to 1e-13 of its largest entry, at any dim and T the library takes. With a prior far off that scale -- data at 1e3
+under sigma0 = 1 -- the first sample moves the factor by six orders of magnitude, and a float64 formulation with the textbook
+rank-one update (w_i <- c w_i - s L_ik', the difference of two products a million times its result) loses about eight digits of log p:
+the numpy model of the tests is 4e-9 (dim 5) and 3e-8 (dim 32) off there. The device updates w_i <- (w_i - s L_ik) / c and stays
+within 1e-11 (2.7e-12 and 8.3e-12 measured); map_run and the change points are not affected either way as long as the columns of R
+have a clear maximum. A hypothesis that has absorbed a sample beyond about 1e15 times the data's scale (1e100, say) stays finite,
+but float64 no longer holds the later samples beside it and its log p is not meaningful (it is strongly negative: such a hypothesis
+weighs nothing in R); a sample whose square overflows (about 1e154 and beyond) fails its replica. tests/test_hip_bocpd_edges.py
+measures all three.
+
+A batch whose scratch does not fit half of the free device memory is processed in chunks of series; PSMF_BOCPD_CHUNK=n (read at every
+call) caps a chunk at n series, which changes no output bit.
+
 `MVBOCPD` keeps the Matlab function's signature.  `find_changepoint` is the single change-point search of the experiment's other two
 columns, host numpy: two cumulative sums per row.
 """

@@ -13,11 +13,18 @@
 //       Per step t >= b, with delta = x_t - mu and one fused pass over the columns of L that reads and writes every entry once:
 //         forward substitution  L z = delta                              (column k: z_k = u_k / L_kk, u_i -= L_ik z_k)
 //         rank-one update       L L^T += coef delta delta^T              (column k: r = sqrt(L_kk^2 + w_k^2), c = r / L_kk, s = w_k / L_kk,
-//                                                                         L_ik <- (L_ik + s w_i) / c, w_i <- c w_i - s L_ik)
+//                                                                         L_ik' = L_ik / c + (s / c) w_i, w_i <- w_i / c - (s / c) L_ik)
 //       with coef = kappa / (2 (kappa + 1)), w = sqrt(coef) delta, and
 //         log p = cst[a] - ld - (nu + dim) / 2 * log1p(coef |z|^2),      sc = nu coef,  sc |z|^2 / nu = coef |z|^2,  ld = sum_j log L_jj
 //       where cst[a] = lgamma((nu + dim) / 2) - lgamma(nu / 2) + dim / 2 (log sc - log(nu pi)) comes from a host table (it depends on the
 //       age alone) and ld is carried: det(Sigma + coef delta delta^T) = det(Sigma) (1 + coef |z|^2), so ld += log1p(coef |z|^2) / 2.
+//       The update of w_i is the textbook's w_i <- c w_i - s L_ik' with c^2 - s^2 = 1 put in.  The textbook's form subtracts two products of
+//       size s^2 w_i to get a result of size w_i / c.  With a sample at 1e100 under a unit prior the rounding of that difference, 1e184,
+//       went into the next column, whose square overflowed: a finite series failed with PSMF_ERR_NUMERIC; and with data at 1e3 under a
+//       unit prior it cost log p three of its digits (4e-9 against 3e-12 at dim 5).  This form has no such difference, and with 1 / c = L_kk / r and s / c = w_k / r
+//       (both at most 1) as the column's constants no product exceeds its operands: a sample fails only where its own square overflows.
+//       The operation count is the textbook's (a multiplication and a fused multiply-add for each of L_ik', w_i); measured against it
+//       at T = 801: -2 % at dim 20, +3 % at dim 32, +4 % at dim 28, +8 % at dim 12, equal at dim 3 (docs/MEASUREMENTS.md).
 //       log p goes to table[series][t][b] (lanes = consecutive b: coalesced).  x_t is the same for the whole workgroup.  All lanes of a
 //       block but those of its first NL steps are busy; the blocks of a series differ in length (T - first birth), and with about
 //       batch * T / NL of them against 256 CUs the dispatcher evens that out.  Hypotheses that a truncation discards later cost their
@@ -70,7 +77,7 @@ __host__ __device__ constexpr int bocpd_lanes(int dim) {
 
 // One instance per dimension: every loop over coordinates is unrolled, so mu and the two work vectors of a step are registers (3 DIM
 // doubles, no scratch memory), every LDS address of L is an immediate, and the compiler moves a column's loads ahead of the column
-// before it (no column of L touches another).  What stays serial is the chain w_k -> r -> L_ik' -> w_{k+1} from column to column; the
+// before it (no column of L touches another).  What stays serial is the chain w_k -> 1 / r -> w_{k+1} from column to column; the
 // reciprocals of the old diagonal stand outside it and the square root is taken as x rsqrt(x), so no division lies on it.
 template <int DIM>
 __global__ __launch_bounds__(bocpd_lanes(DIM) < 64 ? 64 : bocpd_lanes(DIM)) void psmf_bocpd_chain_kernel(BocpdParams p) {
@@ -119,16 +126,15 @@ __global__ __launch_bounds__(bocpd_lanes(DIM) < 64 ? 64 : bocpd_lanes(DIM)) void
       zz = fma(zk, zk, zz);
       const double r2 = fma(lkk, lkk, w[k] * w[k]);
       const double rinv = rsqrt(r2), r = r2 * rinv;
-      const double c = r * linv, s = w[k] * linv, cinv = lkk * rinv;
+      const double cinv = lkk * rinv, sc = w[k] * rinv;      // 1 / c and s / c
       sL[e * NL] = r;
       ++e;
 #pragma unroll
       for (int i = k + 1; i < DIM; ++i, ++e) {
         const double l = sL[e * NL];
         u[i] = fma(-l, zk, u[i]);
-        const double ln = fma(s, w[i], l) * cinv;
-        sL[e * NL] = ln;
-        w[i] = fma(c, w[i], -s * ln);
+        sL[e * NL] = fma(sc, w[i], l * cinv);
+        w[i] = fma(-sc, l, w[i] * cinv);             // = c w_i - s L_ik' (c^2 - s^2 = 1), without its cancellation: see above
       }
     }
     const double lq = log1p(coef * zz);              // sc |z|^2 / nu = coef |z|^2
@@ -268,6 +274,7 @@ int bocpd_run(const psmf_bocpd_config* cfg, const double* X, int32_t* map_run, i
               double* R_last, double* R, double* logpred, int32_t* status, float* elapsed_ms) {
   const BocpdFail fail{};
   const psmf_handle w = nullptr;
+  const Switches sw;      // no handle here: read at entry, on every call
   if (!cfg || !X || !map_run || !n_changepoints) return fail(PSMF_ERR_ARG, "null argument");
   if (cfg->abi_version != PSMF_ABI_VERSION) return fail(PSMF_ERR_ARG, "ABI version mismatch");
   const int dim = cfg->dim, T = cfg->T, B = cfg->batch, maxcp = cfg->max_changepoints;
@@ -280,6 +287,7 @@ int bocpd_run(const psmf_bocpd_config* cfg, const double* X, int32_t* map_run, i
   if (!std::isfinite(cfg->sigma0) || !(cfg->sigma0 > 0.0)) return fail(PSMF_ERR_ARG, "need a finite sigma0 > 0 (Sigma0 = sigma0 I)");
   if (cfg->drop < 0 || cfg->settle < 0 || cfg->confirm < 0) return fail(PSMF_ERR_ARG, "drop, settle and confirm must be >= 0");
   if (maxcp < 0 || (maxcp > 0 && !changepoints)) return fail(PSMF_ERR_ARG, "max_changepoints must be >= 0, and > 0 needs changepoints");
+  if (sw.bocpd_chunk < 0) return fail(PSMF_ERR_ARG, "PSMF_BOCPD_CHUNK must be >= 0 (series per chunk; 0 = sized from free memory)");
   if (cfg->want_R && !R) return fail(PSMF_ERR_ARG, "want_R needs R");
   if (cfg->want_logpred && !logpred) return fail(PSMF_ERR_ARG, "want_logpred needs logpred");
   if (cfg->want_R && (long long)B * (T + 1) * (T + 1) > BOCPD_MAX_TABLE_DOUBLES)
@@ -313,7 +321,8 @@ int bocpd_run(const psmf_bocpd_config* cfg, const double* X, int32_t* map_run, i
   size_t budget = free_b / 2;
   if (budget > ((size_t)16 << 30)) budget = (size_t)16 << 30;
   if (per_series > budget) return fail(PSMF_ERR_HIP, "one series needs " + std::to_string(per_series) + " bytes of device scratch, more than is free");
-  const int chunk = (int)std::min<size_t>((size_t)B, budget / per_series);
+  int chunk = (int)std::min<size_t>((size_t)B, budget / per_series);
+  if (sw.bocpd_chunk > 0) chunk = std::min(chunk, sw.bocpd_chunk);      // PSMF_BOCPD_CHUNK: smaller chunks than memory asks for
 
   Dev<double> dX, dCst, dTab, dRl, dR, dLp;
   Dev<int> dMap, dCp, dNcp, dErr;

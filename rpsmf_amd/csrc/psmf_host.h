@@ -29,7 +29,7 @@ struct Geometry {
 // Environment switches: one row each, and this struct is the library's only reader of the environment.  The rows
 // are read when a Switches is constructed: ONCE per handle, with the handle at psmf_create -- tests flip them between handles of one
 // process, and nothing on the per-block host path looks at the environment; the entry points without a handle (psmf_impute_*,
-// psmf_measure_copy_bandwidth) construct one at entry, on every call.
+// psmf_measure_copy_bandwidth, psmf_bocpd_run) construct one at entry, on every call.
 struct Switches {
   static bool set(const char* name) { return getenv(name) != nullptr; }                                  // present at all
   static bool on(const char* name) { const char* e = getenv(name); return e && atoi(e) != 0; }           // set and non-zero
@@ -68,6 +68,8 @@ struct Switches {
   double ns_far4 = as_double("PSMF_NS_FAR4", 0.6);       // filter4 / filter4s: their give-up residual (PSMF_NS_FAR, when set, rules both)
   // small-shape masked engine (psmf_impute.hip)
   bool impute_v3 = !off("PSMF_IMPUTE_V3"), impute_par = !off("PSMF_IMPUTE_PAR");      // =0: round 2's loop for the small shapes too; inversions one after the other
+  // change-point detection (psmf_bocpd.hip)
+  int bocpd_chunk = as_int("PSMF_BOCPD_CHUNK", 0);       // n > 0: at most n series per chunk, still capped by free memory (0, unset: sized from free memory alone)
   // diagnostics
   bool dbg_breakdown = set("PSMF_DBG_BREAKDOWN");        // psmf_counters prints the in-situ breakdown of a filter3 launch
   bool host_timing = on("PSMF_HOST_TIMING");             // report slow host-side enqueues and waits

@@ -8,8 +8,10 @@ Both models follow the five steps of rpsmf_amd/changepoint.py's docstring, hypot
     stable_model    the Cholesky factor L of Sigma per hypothesis: L z = delta by forward substitution, delta^T c delta = s |z|^2 with
                     s = nu kappa / (2 (kappa + 1)), log det c = dim log s - 2 sum log L_jj, a rank-one update of L with
                     sqrt(kappa / (2 (kappa + 1))) delta, and log R with a log-sum-exp per column
-They share the heuristic and nothing of the algebra.  Each returns dict(logpred (T, T) [t][age], NaN where not live; R (T + 1, T + 1)
-[t][age]; R_last; map_run (T,); changepoints (list); discarded (list: hypotheses dropped by each truncation)).
+They share the heuristic and nothing of the algebra.  extended_model is stable_model in np.longdouble (80-bit), every constant formed in
+that type and the lgamma difference from mpmath: the reference of tests/bocpd_net_cases.py and tests/test_hip_bocpd_edges.py, which
+leave the ranges in which two float64 formulations agree to 1e-11.  Each returns dict(logpred (T, T) [t][age], NaN where not live; R (T + 1, T + 1)
+[t][age]; R_last; map_run (T,); changepoints (list); discarded (list: hypotheses dropped by each truncation); declared_at (list: the 0-based step of each declaration)).
 
 A case is a batch of three replicas (seeds 0, 1, 2 of the case's generator), but `many`, which has 300.
     shift   N(base, 1) samples (base = 0 unless given); every channel moves by +shift, then back, ... at the steps of `at`.  At dim 20
@@ -78,22 +80,60 @@ def _lgam(nu, dim):
     return np.array([math.lgamma(0.5 * (v + dim)) - math.lgamma(0.5 * v) for v in nu])
 
 
-def _detect(X, prm, stable):
-    X = np.asarray(X, dtype=np.float64)
+def _ext(v):
+    """an mpmath number as np.longdouble: its float64 rounding plus the float64 rounding of what that leaves (106 bits, then rounded to 64)"""
+    hi = float(v)
+    return np.longdouble(hi) + np.longdouble(float(v - hi))
+
+
+@lru_cache(maxsize=None)
+def _lgam_ext(nu0, dim, n):
+    """lgamma((nu + dim) / 2) - lgamma(nu / 2) for nu = nu0 .. nu0 + n - 1, from mpmath at 120 bits, as np.longdouble"""
+    import mpmath
+
+    with mpmath.workprec(120):
+        out = [_ext(mpmath.loggamma((mpmath.mpf(nu0) + a + dim) / 2) - mpmath.loggamma((mpmath.mpf(nu0) + a) / 2)) for a in range(n)]
+    out = np.array(out, dtype=np.longdouble)
+    out.setflags(write=False)
+    return out
+
+
+# Ways in which a detector can be subtly wrong (tests/test_bocpd_net_cases_cpu.py: each must move the net of tests/bocpd_net_cases.py).
+# `nl` is the chain kernel's lanes per workgroup at the case's dim.
+WRONG = ("coef-kappa", "exponent-nu", "keep-m", "block-edge", "map-live", "stale-ld")
+
+
+def _detect(X, prm, stable, dtype=np.float64, wrong=None, nl=0):
+    ext = dtype is not np.float64
+    assert stable or not (ext or wrong)
+    if ext:
+        import mpmath
+
+        assert np.finfo(dtype).eps < 1.1e-19, "the extended model needs an 80-bit (or wider) long double"
+        with mpmath.workprec(120):
+            pi = _ext(mpmath.pi)
+    else:
+        pi = np.pi
+    F = dtype
+    X = np.asarray(X, dtype=F)
     dim, T = X.shape
-    h = 1.0 / prm["lam"]
-    kappa0, nu0, sigma0 = prm["kappa0"], prm["nu0"], prm["sigma0"]
+    h = F(1.0) / F(prm["lam"])
+    kappa0, nu0, sigma0 = F(prm["kappa0"]), F(prm["nu0"]), F(prm["sigma0"])
     drop, settle, confirm = prm["drop"], prm["settle"], prm["confirm"]
-    mu = np.zeros((1, dim))
-    S = sigma0 * np.eye(dim)[None]                      # literal: Sigma per hypothesis
-    L = math.sqrt(sigma0) * np.eye(dim)[None]           # stable: its Cholesky factor
-    col = np.array([0.0 if stable else 1.0])            # column t as stored (log R when stable)
+    sqrt_sigma0 = np.sqrt(sigma0) if ext else math.sqrt(sigma0)
+    log_h, log_1mh = (np.log(h), np.log1p(-h)) if ext else (math.log(h), math.log1p(-h))
+    lgam = _lgam_ext(float(nu0), dim, T) if ext else None
+    mu = np.zeros((1, dim), dtype=F)
+    S = sigma0 * np.eye(dim, dtype=F)[None]             # literal: Sigma per hypothesis
+    L = sqrt_sigma0 * np.eye(dim, dtype=F)[None]        # stable: its Cholesky factor
+    Lstale = L
+    col = np.array([0.0 if stable else 1.0], dtype=F)   # column t as stored (log R when stable)
     n = 1
-    logpred = np.full((T, T), np.nan)
-    R = np.zeros((T + 1, T + 1))
+    logpred = np.full((T, T), np.nan, dtype=F)
+    R = np.zeros((T + 1, T + 1), dtype=F)
     R[0, 0] = 1.0
     map_run = np.zeros(T, dtype=np.int64)
-    cps, discarded = [], []
+    cps, discarded, declared_at = [], [], []
     flag = cnt = 0
     with np.errstate(all="ignore"):
         for t in range(T):
@@ -104,26 +144,28 @@ def _detect(X, prm, stable):
             # 1. predictive
             if stable:
                 s = nu * kap / (2.0 * (kap + 1.0))
-                z = np.zeros((n, dim))
+                z = np.zeros((n, dim), dtype=F)
                 u = delta.copy()
                 for k in range(dim):                    # L z = delta, column by column
                     z[:, k] = u[:, k] / L[:, k, k]
                     u[:, k + 1:] -= L[:, k + 1:, k] * z[:, k:k + 1]
                 quad = s * np.sum(z * z, axis=1)
-                logdetc = dim * np.log(s) - 2.0 * np.sum(np.log(np.diagonal(L, axis1=1, axis2=2)), axis=1)
+                Ld = Lstale if wrong == "stale-ld" and t == T // 2 else L
+                logdetc = dim * np.log(s) - 2.0 * np.sum(np.log(np.diagonal(Ld, axis1=1, axis2=2)), axis=1)
             else:
                 c = np.linalg.inv(2.0 * (kap + 1.0)[:, None, None] * S / (nu * kap)[:, None, None])
                 quad = np.einsum("ni,nij,nj->n", delta, c, delta)
                 logdetc = np.log(np.linalg.det(c))
-            logp = _lgam(nu, dim) + 0.5 * logdetc - 0.5 * dim * np.log(nu * np.pi) - 0.5 * (nu + dim) * np.log1p(quad / nu)
+            expo = nu if wrong == "exponent-nu" else nu + dim
+            logp = (lgam[:n] if ext else _lgam(nu, dim)) + 0.5 * logdetc - 0.5 * dim * np.log(nu * pi) - 0.5 * expo * np.log1p(quad / nu)
             logpred[t, :n] = logp
             # 2. growth and change-point mass
-            new = np.empty(n + 1)
+            new = np.empty(n + 1, dtype=F)
             if stable:
                 v = col[:n] + logp
                 M = v.max()
-                new[1:] = v - M - math.log(np.exp(v - M).sum()) + math.log1p(-h)
-                new[0] = math.log(h)
+                new[1:] = v - M - (np.log(np.exp(v - M).sum()) if ext else math.log(np.exp(v - M).sum())) + log_1mh
+                new[0] = log_h
                 R[t + 1, :n + 1] = np.exp(new)
             else:
                 g = col[:n] * np.exp(logp)
@@ -132,7 +174,7 @@ def _detect(X, prm, stable):
                 new = new / new.sum()
                 R[t + 1, :n + 1] = new
             # 3. MAP run length of column t (argmax takes the first of equal maxima: the lowest age)
-            m = 1 + int(np.argmax(col))
+            m = 1 + int(np.argmax(col[:n] if wrong == "map-live" else col))
             map_run[t] = m
             # 4. detection heuristic
             keep = n
@@ -145,14 +187,17 @@ def _detect(X, prm, stable):
                         cnt += 1
                         if cnt > confirm:
                             cps.append((t + 1) - m + 1)
+                            declared_at.append(t)
                             flag = cnt = 0
-                            keep = min(n, max(m - 1, 0))
+                            keep = min(n, m if wrong == "keep-m" else max(m - 1, 0))
                             discarded.append(n - keep)
                     else:
                         flag = cnt = 0
             mu, S, L, kap, delta = mu[:keep], S[:keep], L[:keep], kap[:keep], delta[:keep]
             # 5. ageing
-            coef = kap / (2.0 * (kap + 1.0))
+            coef = kap / (2.0 * (kap if wrong == "coef-kappa" else kap + 1.0))
+            prior = sqrt_sigma0 * np.eye(dim, dtype=F)[None]
+            aged = (kap[:, None] * mu + x[None]) / (kap[:, None] + 1.0)
             if stable:
                 Ln = L.copy()
                 w = np.sqrt(coef)[:, None] * delta
@@ -162,13 +207,16 @@ def _detect(X, prm, stable):
                     Ln[:, k, k] = r
                     Ln[:, k + 1:, k] = (Ln[:, k + 1:, k] + s_[:, None] * w[:, k + 1:]) / c_[:, None]
                     w[:, k + 1:] = c_[:, None] * w[:, k + 1:] - s_[:, None] * Ln[:, k + 1:, k]
-                L = np.concatenate([math.sqrt(sigma0) * np.eye(dim)[None], Ln])
+                if wrong == "block-edge" and keep > 0 and t > 0 and t % nl == 0:      # the birth at a block's first step misses that step's sample
+                    Ln[0], aged[0] = L[0], mu[0]
+                Lstale = np.concatenate([prior, L])
+                L = np.concatenate([prior, Ln])
             else:
                 S = np.concatenate([sigma0 * np.eye(dim)[None], S + coef[:, None, None] * delta[:, :, None] * delta[:, None, :]])
-            mu = np.concatenate([np.zeros((1, dim)), (kap[:, None] * mu + x[None]) / (kap[:, None] + 1.0)])
+            mu = np.concatenate([np.zeros((1, dim), dtype=F), aged])
             col = new
             n = keep + 1
-    return dict(logpred=logpred, R=R, R_last=R[T].copy(), map_run=map_run, changepoints=cps, discarded=discarded)
+    return dict(logpred=logpred, R=R, R_last=R[T].copy(), map_run=map_run, changepoints=cps, discarded=discarded, declared_at=declared_at)
 
 
 def literal_model(X, **prm):
@@ -177,6 +225,13 @@ def literal_model(X, **prm):
 
 def stable_model(X, **prm):
     return _detect(X, {**params(dict(dim=np.shape(X)[0])), **prm}, stable=True)
+
+
+def extended_model(X, wrong=None, nl=0, **prm):
+    """stable_model one precision up: np.longdouble (80-bit: asserted, not assumed) with pi, log h, log1p(-h) and sqrt(sigma0) formed in that
+    type and the lgamma difference from mpmath at 120 bits.  Its logpred, R and R_last are np.longdouble arrays.  `wrong` (one of WRONG)
+    runs a detector with that mistake instead."""
+    return _detect(X, {**params(dict(dim=np.shape(X)[0])), **prm}, stable=True, dtype=np.longdouble, wrong=wrong, nl=nl)
 
 
 @lru_cache(maxsize=None)
