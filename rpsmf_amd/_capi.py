@@ -150,8 +150,25 @@ def dyn_n_theta(kind, r, flags=0, terms=0):
     return 0
 
 
+_POINTERS = {np.dtype(np.float64): _dp, np.dtype(np.uint8): _u8p, np.dtype(np.int32): C.POINTER(C.c_int32)}
+
+
 def _ptr(a):
-    return None if a is None else a.ctypes.data_as(_dp)
+    """a float64, int32 or uint8 array (or None) as the pointer the C ABI takes"""
+    return None if a is None else a.ctypes.data_as(_POINTERS[a.dtype])
+
+
+def raise_for(lib, rc, what, handle=None, typed=True):
+    """The one mapping of a return code to an exception: ERR_NUMERIC -> numpy.linalg.LinAlgError and ERR_ARG -> ValueError, each with
+    the library's message alone; anything else -> PsmfError(`what`: message).  typed=False: a PsmfError whatever the code."""
+    if rc == OK:
+        return
+    msg = lib.psmf_last_error(handle).decode()
+    if typed and rc == ERR_NUMERIC:
+        raise np.linalg.LinAlgError(msg)
+    if typed and rc == ERR_ARG:
+        raise ValueError(msg)
+    raise PsmfError(f"{what}: {msg}")
 
 
 def _f64(a, shape=None):
@@ -219,14 +236,7 @@ class DeviceFilter:
 
     # -- plumbing
     def _check(self, rc):
-        if rc == OK:
-            return
-        msg = self._lib.psmf_last_error(self._h).decode()
-        if rc == ERR_NUMERIC:
-            raise np.linalg.LinAlgError(msg)
-        if rc == ERR_ARG:
-            raise ValueError(msg)
-        raise PsmfError(f"libpsmf_hip error {rc}: {msg}")
+        raise_for(self._lib, rc, f"libpsmf_hip error {rc}", self._h)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -368,7 +378,7 @@ class DeviceFilter:
         M = np.ascontiguousarray(np.asarray(M) != 0, dtype=np.uint8)
         if M.ndim != 2 or M.shape[1] != self.d_local:
             raise ValueError(f"mask must be (T, {self.d_local}) time-major, got {M.shape}")
-        self._check(self._lib.psmf_upload_mask(self._h, M.ctypes.data_as(_u8p), int(t0), M.shape[0]))
+        self._check(self._lib.psmf_upload_mask(self._h, _ptr(M), int(t0), M.shape[0]))
 
     def set_step_size(self, gam):
         """masked = 2 / 3 (MLE-SMF / TMF): step size of the gradient update of C for the runs that follow."""
@@ -381,7 +391,7 @@ class DeviceFilter:
         if Mm.ndim != 2 or Mm.shape[1] != self.d_local:
             raise ValueError(f"held-out mask must be (T, {self.d_local}) time-major, got {Mm.shape}")
         out = np.empty(4)
-        self._check(self._lib.psmf_masked_metrics(self._h, Mm.ctypes.data_as(_u8p), int(t0), Mm.shape[0], float(sig), _ptr(out)))
+        self._check(self._lib.psmf_masked_metrics(self._h, _ptr(Mm), int(t0), Mm.shape[0], float(sig), _ptr(out)))
         return out
 
     def step_scalars(self, t0, nt):
@@ -528,9 +538,7 @@ class DeviceFilter:
     def comm_unique_id():
         lib = load_library()
         buf = C.create_string_buffer(UNIQUE_ID_BYTES)
-        rc = lib.psmf_comm_unique_id(buf)
-        if rc != OK:
-            raise PsmfError("psmf_comm_unique_id failed: " + lib.psmf_last_error(None).decode())
+        raise_for(lib, lib.psmf_comm_unique_id(buf), "psmf_comm_unique_id failed", typed=False)
         return buf.raw
 
     def comm_init(self, nranks, rank, unique_id):
@@ -570,17 +578,14 @@ def measure_copy_bandwidth(device=0, nbytes=1 << 30, iters=20):
     """GB/s (read + written) of a streaming copy kernel on `device`."""
     lib = load_library()
     v = C.c_double()
-    rc = lib.psmf_measure_copy_bandwidth(int(device), int(nbytes), int(iters), C.byref(v))
-    if rc != OK:
-        raise PsmfError("psmf_measure_copy_bandwidth failed: " + lib.psmf_last_error(None).decode())
+    raise_for(lib, lib.psmf_measure_copy_bandwidth(int(device), int(nbytes), int(iters), C.byref(v)), "psmf_measure_copy_bandwidth failed", typed=False)
     return v.value
 
 
 def device_pci_bus_id(device=0):
+    lib = load_library()
     buf = C.create_string_buffer(32)
-    rc = load_library().psmf_device_pci_bus_id(int(device), buf, 32)
-    if rc != OK:
-        raise PsmfError("psmf_device_pci_bus_id failed: " + load_library().psmf_last_error(None).decode())
+    raise_for(lib, lib.psmf_device_pci_bus_id(int(device), buf, 32), "psmf_device_pci_bus_id failed", typed=False)
     return buf.value.decode()
 
 

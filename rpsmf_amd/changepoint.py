@@ -99,17 +99,10 @@ def mvbocpd_batch(X, *, lam=200.0, kappa0=1.0, nu0=None, sigma0=1.0, drop=10, se
                                 confirm=int(confirm), max_changepoints=maxcp, want_R=int(want_R), want_logpred=int(want_logpred),
                                 lam=float(lam), kappa0=float(kappa0), nu0=float(nu0), sigma0=float(sigma0))
     ms = C.c_float()
-    dp = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
-    ip = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
+    ptr = _capi._ptr
     lib = _capi.load_library()
-    rc = lib.psmf_bocpd_run(C.byref(cfg), dp(Xt), ip(map_run), ip(cps), ip(ncp), dp(R_last), dp(R), dp(lp), ip(st), C.byref(ms))
-    if rc != _capi.OK:
-        msg = lib.psmf_last_error(None).decode()
-        if rc == _capi.ERR_NUMERIC:
-            raise np.linalg.LinAlgError(msg)
-        if rc == _capi.ERR_ARG:
-            raise ValueError(msg)
-        raise _capi.PsmfError(f"psmf_bocpd_run failed ({rc}): {msg}")
+    rc = lib.psmf_bocpd_run(C.byref(cfg), ptr(Xt), ptr(map_run), ptr(cps), ptr(ncp), ptr(R_last), ptr(R), ptr(lp), ptr(st), C.byref(ms))
+    _capi.raise_for(lib, rc, f"psmf_bocpd_run failed ({rc})")
     found = [cps[b, :min(int(ncp[b]), maxcp)].copy() for b in range(B)]
     return dict(map_run=map_run, changepoints=found, n_changepoints=ncp, R_last=R_last, R=R, logpred=lp, status=st, elapsed_ms=ms.value)
 

@@ -39,7 +39,8 @@
 // No atomics, no flags between workgroups; the error flag of a series is a plain store of 1 (every writer stores the same value).
 // Limits: dim <= 32, T <= 4096.  Scratch (the table: T * T doubles per series) is allocated per call; a batch whose scratch does not fit
 // what is free on the device is processed in chunks of series.
-#include "psmf_host.h"        // g_create_error, HIP_TRY, ALLOC_TRY, Dev<>, Event
+#include "psmf_host.h"        // Switches
+#include "psmf_batch.h"       // EntryFail, open_device, typed transfers, TimedLaunch, replica_status
 
 #include <algorithm>
 #include <cmath>
@@ -246,34 +247,25 @@ __global__ __launch_bounds__(BOCPD_POST_WG) void psmf_bocpd_post_kernel(BocpdPar
 
 namespace {
 
-struct BocpdFail {
-  int operator()(int code, const std::string& msg) const { g_create_error = "psmf_bocpd_run: " + msg; return code; }
-  int operator()(psmf_handle, int code, const std::string& msg) const { return (*this)(code, msg); }
-};
-
 template <int DIM>
-int bocpd_launch_chain(const BocpdFail& fail, const BocpdParams& bp, int nser) {
+int bocpd_launch_chain(const EntryFail& fail, const BocpdParams& bp, int nser) {
   if constexpr (DIM > BOCPD_MAX_DIM) {
     return fail(PSMF_ERR_ARG, "no chain kernel for this dim");
   } else {
     if (bp.dim != DIM) return bocpd_launch_chain<DIM + 1>(fail, bp, nser);
-    const psmf_handle w = nullptr;
     constexpr int NL = bocpd_lanes(DIM);
-    constexpr size_t lds = (size_t)(DIM * (DIM + 1) / 2) * 8 * NL;
+    constexpr size_t lds = (size_t)(DIM * (DIM + 1) / 2) * sizeof(double) * NL;
     static_assert(lds <= BOCPD_LDS_MAX, "the factors of a workgroup's lanes fit the LDS");
     const void* kern = (const void*)psmf_bocpd_chain_kernel<DIM>;
-    if (lds > 48 * 1024) HIP_TRY(w, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    PSMF_TRY(lds_opt_in(fail, kern, lds));
     BocpdParams q = bp;
-    void* args[] = {&q};
-    HIP_TRY(w, hipLaunchKernel(kern, dim3((bp.T + NL - 1) / NL, nser), dim3(NL < 64 ? 64 : NL), args, lds, 0));
-    return PSMF_OK;
+    return launch(fail, kern, dim3((bp.T + NL - 1) / NL, nser), dim3(NL < 64 ? 64 : NL), &q, lds);
   }
 }
 
 int bocpd_run(const psmf_bocpd_config* cfg, const double* X, int32_t* map_run, int32_t* changepoints, int32_t* n_changepoints,
               double* R_last, double* R, double* logpred, int32_t* status, float* elapsed_ms) {
-  const BocpdFail fail{};
-  const psmf_handle w = nullptr;
+  const EntryFail fail{"psmf_bocpd_run"};
   const Switches sw;      // no handle here: read at entry, on every call
   if (!cfg || !X || !map_run || !n_changepoints) return fail(PSMF_ERR_ARG, "null argument");
   if (cfg->abi_version != PSMF_ABI_VERSION) return fail(PSMF_ERR_ARG, "ABI version mismatch");
@@ -308,16 +300,13 @@ int bocpd_run(const psmf_bocpd_config* cfg, const double* X, int32_t* map_run, i
     for (size_t i = 0; i < (size_t)T * dim; ++i)
       if (!std::isfinite(x[i])) { herr[b] = 1; break; }
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(PSMF_ERR_NO_DEVICE, "no HIP device visible");
-  if (cfg->device < 0 || cfg->device >= ndev) return fail(PSMF_ERR_ARG, "bad device ordinal");
-  HIP_TRY(w, hipSetDevice(cfg->device));
+  PSMF_TRY(open_device(fail, cfg->device));
 
   // series per chunk: the scratch and the outputs of a chunk take at most half of what is free, and at most 16 GiB
-  const size_t per_series = ((size_t)T * T + (size_t)T * dim + (wantR ? (size_t)(T + 1) * (T + 1) : 0) + (wantLp ? (size_t)T * T : 0) + (T + 1)) * 8 +
-                            ((size_t)T + maxcp + 2) * 4;
+  const size_t per_series = ((size_t)T * T + (size_t)T * dim + (wantR ? (size_t)(T + 1) * (T + 1) : 0) + (wantLp ? (size_t)T * T : 0) + (T + 1)) * sizeof(double) +
+                            ((size_t)T + maxcp + 2) * sizeof(int);
   size_t free_b = 0, total_b = 0;
-  HIP_TRY(w, hipMemGetInfo(&free_b, &total_b));
+  PSMF_TRY(HIP_OK(fail, hipMemGetInfo(&free_b, &total_b)));
   size_t budget = free_b / 2;
   if (budget > ((size_t)16 << 30)) budget = (size_t)16 << 30;
   if (per_series > budget) return fail(PSMF_ERR_HIP, "one series needs " + std::to_string(per_series) + " bytes of device scratch, more than is free");
@@ -326,21 +315,20 @@ int bocpd_run(const psmf_bocpd_config* cfg, const double* X, int32_t* map_run, i
 
   Dev<double> dX, dCst, dTab, dRl, dR, dLp;
   Dev<int> dMap, dCp, dNcp, dErr;
-  Event e0, e1;
-  const size_t nX = (size_t)T * dim, nTab = (size_t)T * T, nR = (size_t)(T + 1) * (T + 1);
-  ALLOC_TRY(w, dX.alloc(chunk * nX * 8));
-  ALLOC_TRY(w, dCst.alloc((size_t)T * 8));
-  ALLOC_TRY(w, dTab.alloc(chunk * nTab * 8));
-  ALLOC_TRY(w, dMap.alloc((size_t)chunk * T * 4));
-  ALLOC_TRY(w, dCp.alloc(((size_t)chunk * maxcp + 1) * 4));
-  ALLOC_TRY(w, dNcp.alloc((size_t)chunk * 4));
-  ALLOC_TRY(w, dErr.alloc((size_t)chunk * 4));
-  if (R_last) ALLOC_TRY(w, dRl.alloc((size_t)chunk * (T + 1) * 8));
-  if (wantR) ALLOC_TRY(w, dR.alloc(chunk * nR * 8));
-  if (wantLp) ALLOC_TRY(w, dLp.alloc(chunk * nTab * 8));
-  HIP_TRY(w, hipMemcpy(dCst, cst.data(), (size_t)T * 8, hipMemcpyHostToDevice));
-  HIP_TRY(w, hipEventCreate(e0.put()));
-  HIP_TRY(w, hipEventCreate(e1.put()));
+  TimedLaunch timed;
+  const size_t nX = (size_t)T * dim, nTab = (size_t)T * T, nR = (size_t)(T + 1) * (T + 1), nRl = (size_t)T + 1;
+  PSMF_TRY(alloc_n(fail, dX, chunk * nX));
+  PSMF_TRY(alloc_n(fail, dCst, T));
+  PSMF_TRY(alloc_n(fail, dTab, chunk * nTab));
+  PSMF_TRY(alloc_n(fail, dMap, (size_t)chunk * T));
+  PSMF_TRY(alloc_n(fail, dCp, (size_t)chunk * maxcp + 1));
+  PSMF_TRY(alloc_n(fail, dNcp, chunk));
+  PSMF_TRY(alloc_n(fail, dErr, chunk));
+  if (R_last) PSMF_TRY(alloc_n(fail, dRl, chunk * nRl));
+  if (wantR) PSMF_TRY(alloc_n(fail, dR, chunk * nR));
+  if (wantLp) PSMF_TRY(alloc_n(fail, dLp, chunk * nTab));
+  PSMF_TRY(copy_in(fail, dCst, cst.data(), T));
+  PSMF_TRY(timed.create(fail));
 
   BocpdParams bp;
   bp.dim = dim; bp.T = T; bp.drop = cfg->drop; bp.settle = cfg->settle; bp.confirm = cfg->confirm; bp.max_cp = maxcp;
@@ -351,43 +339,35 @@ int bocpd_run(const psmf_bocpd_config* cfg, const double* X, int32_t* map_run, i
   bp.R_last = R_last ? dRl.get() : nullptr; bp.R = wantR ? dR.get() : nullptr; bp.logpred = wantLp ? dLp.get() : nullptr; bp.err = dErr;
 
   float total_ms = 0.0f;
-  for (int s0 = 0; s0 < B; s0 += chunk) {
-    const int ns = std::min(chunk, B - s0);
-    HIP_TRY(w, hipMemcpy(dX, X + s0 * nX, ns * nX * 8, hipMemcpyHostToDevice));
-    HIP_TRY(w, hipMemcpy(dErr, herr.data() + s0, (size_t)ns * 4, hipMemcpyHostToDevice));
-    HIP_TRY(w, hipMemset(dMap, 0, (size_t)ns * T * 4));
-    HIP_TRY(w, hipMemset(dCp, 0, ((size_t)ns * maxcp + 1) * 4));
-    HIP_TRY(w, hipMemset(dNcp, 0, (size_t)ns * 4));
-    if (R_last) HIP_TRY(w, hipMemset(dRl, 0, (size_t)ns * (T + 1) * 8));
-    if (wantR) HIP_TRY(w, hipMemset(dR, 0, ns * nR * 8));
-    if (wantLp) HIP_TRY(w, hipMemset(dLp, 0, ns * nTab * 8));
-    HIP_TRY(w, hipEventRecord(e0, 0));
-    const int rc = bocpd_launch_chain<1>(fail, bp, ns);      // the instance of this dim
-    if (rc != PSMF_OK) return rc;
-    { void* args[] = {&bp}; HIP_TRY(w, hipLaunchKernel((const void*)psmf_bocpd_post_kernel, dim3(ns), dim3(BOCPD_POST_WG), args, 0, 0)); }
-    HIP_TRY(w, hipGetLastError());
-    HIP_TRY(w, hipEventRecord(e1, 0));
-    HIP_TRY(w, hipEventSynchronize(e1));
+  for (int s0 = 0; s0 < B; s0 += chunk) {      // s0: the chunk's first series = its element offset in the host arrays, per series
+    const size_t ns = std::min(chunk, B - s0);
+    PSMF_TRY(copy_in(fail, dX, X, ns * nX, s0 * nX));
+    PSMF_TRY(copy_in(fail, dErr, herr.data(), ns, s0));
+    PSMF_TRY(zero_n(fail, dMap, ns * T));
+    PSMF_TRY(zero_n(fail, dCp, ns * maxcp + 1));
+    PSMF_TRY(zero_n(fail, dNcp, ns));
+    if (R_last) PSMF_TRY(zero_n(fail, dRl, ns * nRl));
+    if (wantR) PSMF_TRY(zero_n(fail, dR, ns * nR));
+    if (wantLp) PSMF_TRY(zero_n(fail, dLp, ns * nTab));
+    PSMF_TRY(timed.start(fail));
+    PSMF_TRY(bocpd_launch_chain<1>(fail, bp, (int)ns));      // the instance of this dim
+    PSMF_TRY(launch(fail, (const void*)psmf_bocpd_post_kernel, dim3((unsigned)ns), dim3(BOCPD_POST_WG), &bp, 0));
     float ms = 0.0f;
-    HIP_TRY(w, hipEventElapsedTime(&ms, e0, e1));
+    PSMF_TRY(timed.finish(fail, &ms));
     total_ms += ms;
-    HIP_TRY(w, hipMemcpy(map_run + (size_t)s0 * T, dMap, (size_t)ns * T * 4, hipMemcpyDeviceToHost));
-    if (maxcp > 0) HIP_TRY(w, hipMemcpy(changepoints + (size_t)s0 * maxcp, dCp, (size_t)ns * maxcp * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(w, hipMemcpy(n_changepoints + s0, dNcp, (size_t)ns * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(w, hipMemcpy(herr.data() + s0, dErr, (size_t)ns * 4, hipMemcpyDeviceToHost));
-    if (R_last) HIP_TRY(w, hipMemcpy(R_last + (size_t)s0 * (T + 1), dRl, (size_t)ns * (T + 1) * 8, hipMemcpyDeviceToHost));
-    if (wantR) HIP_TRY(w, hipMemcpy(R + s0 * nR, dR, ns * nR * 8, hipMemcpyDeviceToHost));
-    if (wantLp) HIP_TRY(w, hipMemcpy(logpred + s0 * nTab, dLp, ns * nTab * 8, hipMemcpyDeviceToHost));
+    PSMF_TRY(copy_out(fail, map_run, dMap, ns * T, (size_t)s0 * T));
+    if (maxcp > 0) PSMF_TRY(copy_out(fail, changepoints, dCp, ns * maxcp, (size_t)s0 * maxcp));
+    PSMF_TRY(copy_out(fail, n_changepoints, dNcp, ns, s0));
+    PSMF_TRY(copy_out(fail, herr.data(), dErr, ns, s0));
+    if (R_last) PSMF_TRY(copy_out(fail, R_last, dRl, ns * nRl, s0 * nRl));
+    if (wantR) PSMF_TRY(copy_out(fail, R, dR, ns * nR, s0 * nR));
+    if (wantLp) PSMF_TRY(copy_out(fail, logpred, dLp, ns * nTab, s0 * nTab));
   }
   if (elapsed_ms) *elapsed_ms = total_ms;
-  // Per-replica outcome, as psmf_ssm_run: a replica with a non-finite sample, a non-finite state or a non-positive pivot gets
-  // PSMF_ERR_NUMERIC; the other replicas are untouched by it.  Without a status array it fails the call.
-  for (int b = 0; b < B; ++b) {
-    const bool bad = herr[b] != 0;
-    if (status) status[b] = bad ? PSMF_ERR_NUMERIC : PSMF_OK;
-    if (bad && !status) return fail(PSMF_ERR_NUMERIC, "non-finite input, a non-finite state or a non-positive pivot in replica " + std::to_string(b));
-  }
-  return PSMF_OK;
+  // Per-replica outcome, as psmf_ssm_run; the other replicas are untouched by a bad one.
+  return replica_status(fail, B, status, [&](int b) { return herr[b] != 0; }, [](int b) {
+    return "non-finite input, a non-finite state or a non-positive pivot in replica " + std::to_string(b);
+  });
 }
 
 }  // namespace

@@ -1,6 +1,7 @@
 // C ABI of libpsmf_hip.so (include/psmf_hip.h): host-side orchestration of the large-d engine.
 // One handle = one HIP stream, one device-resident filter (or row shard), one hipGraph of
 // per-step launches replayed over the series.  No torch, no hipBLAS: plain HIP + RCCL.
+// The batched entry points without a handle (psmf_impute_*, psmf_ssm_*, psmf_bocpd_run) live in the units of their engines.
 #include "psmf_host.h"
 #include "psmf_kernels.hip"
 #include "psmf_masked.hip"
@@ -1450,99 +1451,3 @@ int psmf_comm_init_host(psmf_handle h, int nranks, int rank, psmf_allreduce_fn f
 }
 
 }  // extern "C"
-
-
-// psmf_impute_run beyond one workgroup's LDS (d > 512 or r > 16): the replicas one after the other on the masked per-step engine
-// of the large-d handle (psmf_masked.hip), float64 storage.  ExperimentImpute/PSMF.py:59-95, rPSMF.py:75-148: the prior mean of
-// column 0 is X[:, n - 1] (the initial X on pass 0, the last posterior afterwards -- i.e. the running mean), C, V, P carry over the
-// passes, rPSMF restarts Q, rho, lambda at every pass; X[:, t] is the posterior mean of column t (the mean history).
-int impute_run_large(const psmf_impute_config* cfg, const double* YorgInt, const uint8_t* M, const uint8_t* Mmiss, double* C, double* X,
-                     const double* V, const double* P, const double* Q, double rho, double* Epred, double* Efull, double* inside,
-                     double* Yrec, double* YrecL, double* YrecH, int32_t* status, float* elapsed_ms) {
-  auto failc = [&](int code, const std::string& msg) { g_create_error = "psmf_impute_run: " + msg; return code; };
-  (void)failc;
-  const int d = cfg->d, n = cfg->n, r = cfg->r, B = cfg->batch, robust = cfg->method == 1, meth = cfg->method;
-  psmf_config pc;
-  memset(&pc, 0, sizeof(pc));
-  pc.abi_version = PSMF_ABI_VERSION; pc.d = d; pc.r = r; pc.row0 = 0; pc.d_local = d; pc.robust = robust;
-  pc.coef_update = 1; pc.eta_full = 1; pc.pbar_predict = 1; pc.dyn_kind = PSMF_DYN_RANDOM_WALK; pc.n_theta = 0;
-  pc.storage = PSMF_F64; pc.store_y_pred = 1; pc.update_every = 1; pc.device = cfg->device; pc.use_graph = 1; pc.engine = 1; pc.masked = meth >= 2 ? meth : 1;
-  pc.alpha = pc.beta = 1.0; pc.adam_lr = 1e-3; pc.adam_b1 = 0.9; pc.adam_b2 = 0.999;
-  psmf_handle h = nullptr;
-  int rc = psmf_create(&h, &pc);
-  if (rc) return rc;               // (g_create_error holds the message)
-  auto bail = [&](int code) { g_create_error = std::string("psmf_impute_run: ") + psmf_last_error(h); psmf_destroy(h); return code; };
-  rc = psmf_upload_series(h, YorgInt, PSMF_F64, 0, n, n);
-  if (rc) return bail(rc);
-  const size_t nd = (size_t)n * d;
-  const double qnan = std::numeric_limits<double>::quiet_NaN();
-  std::vector<double> yp, sc;
-  double total_ms = 0.0;
-  for (int b = 0; b < B; ++b) {
-    double* Cb = C + (size_t)b * d * r;
-    double* Xb = X + (size_t)b * n * r;
-    rc = psmf_upload_mask(h, M + (size_t)b * nd, 0, n);
-    if (rc) return bail(rc);
-    if (meth == 3) {       // TMF (TMF.py:47,60): Pbar = I / nu at every step, nu = 2 -- as Q with P = 0 (the serial stage keeps P at 0); V unused
-      std::vector<double> Inu((size_t)r * r, 0.0), Zr((size_t)r * r, 0.0), Iv((size_t)r * r, 0.0);
-      for (int i = 0; i < r; ++i) { Inu[(size_t)i * r + i] = 0.5; Iv[(size_t)i * r + i] = 1.0; }
-      rc = psmf_set_state(h, Cb, Iv.data(), Zr.data(), Inu.data(), Xb + (size_t)(n - 1) * r, 1.0, 0.0, nullptr);
-    } else {
-      rc = psmf_set_state(h, Cb, V, P, Q, Xb + (size_t)(n - 1) * r, rho, robust ? cfg->lambda0 : 0.0, nullptr);
-    }
-    if (rc) return bail(rc);
-    bool bad = false;
-    double m4[4] = {0, 0, 0, 0};
-    const auto t_start = std::chrono::steady_clock::now();
-    for (int it = 0; it < cfg->n_iter && !bad; ++it) {
-      if (it > 0 && robust) {        // rPSMF.py:77-79: Q, R, lambda restart; V, P, C and the mean carry over
-        rc = psmf_set_state(h, nullptr, nullptr, nullptr, Q, nullptr, rho, cfg->lambda0, nullptr);
-        if (rc) return bail(rc);
-      }
-      if (meth >= 2) {       // gam = 1e-6 / (pass + 1)^0.7  (MLESMF.py:59-60, TMF.py:46-48)
-        rc = psmf_set_step_size(h, 1e-6 / std::pow((double)(it + 1), 0.7));
-        if (rc) return bail(rc);
-      }
-      rc = psmf_run(h, 0, n);
-      if (rc) return bail(rc);
-      rc = psmf_masked_metrics(h, Mmiss + (size_t)b * nd, 0, n, meth == 3 ? 0.0 : cfg->sig, m4);
-      if (rc == PSMF_ERR_NUMERIC) { bad = true; break; }
-      if (rc) return bail(rc);
-      Epred[(size_t)b * cfg->n_iter + it] = std::sqrt(m4[0] / m4[3]);
-      Efull[(size_t)b * cfg->n_iter + it] = std::sqrt(m4[1] / m4[3]);
-      if (!std::isfinite(m4[0]) || !std::isfinite(m4[1])) bad = true;
-    }
-    total_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
-    if (!bad) {
-      inside[b] = m4[2] / m4[3];
-      rc = psmf_get_state(h, Cb, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-      if (!rc) rc = psmf_download_mu(h, Xb, 1, n);
-      if (!rc && cfg->want_bands) {
-        yp.resize(nd); sc.resize((size_t)2 * n);
-        rc = psmf_download_y_pred(h, yp.data(), PSMF_F64, 0, n);
-        if (!rc) rc = psmf_download_step_scalars(h, sc.data(), 0, n);
-        if (!rc) {
-          const uint8_t* Mb = M + (size_t)b * nd;
-          for (int t = 0; t < n; ++t)
-            for (int i = 0; i < d; ++i) {
-              const size_t at = (size_t)b * nd + (size_t)t * d + i;
-              const double yh = yp[(size_t)t * d + i];
-              const double band = meth == 3 ? 0.0 : cfg->sig * std::sqrt(robust ? (Mb[(size_t)t * d + i] ? sc[2 * t] : 0.0) + sc[2 * t + 1] : sc[2 * t] + sc[2 * t + 1]);
-              Yrec[at] = yh; YrecL[at] = yh - band; YrecH[at] = yh + band;
-            }
-        }
-      }
-      if (rc == PSMF_ERR_NUMERIC) bad = true;
-      else if (rc) return bail(rc);
-    }
-    if (status) status[b] = bad ? PSMF_ERR_NUMERIC : PSMF_OK;
-    if (bad) {
-      if (!status) return bail(PSMF_ERR_NUMERIC);
-      for (int it = 0; it < cfg->n_iter; ++it) Epred[(size_t)b * cfg->n_iter + it] = Efull[(size_t)b * cfg->n_iter + it] = qnan;
-      inside[b] = qnan;
-    }
-  }
-  if (elapsed_ms) *elapsed_ms = (float)total_ms;
-  psmf_destroy(h);
-  return PSMF_OK;
-}

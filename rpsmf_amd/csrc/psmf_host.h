@@ -1,6 +1,7 @@
 // Host side of libpsmf_hip.so, shared by its translation units (psmf_capi.hip, psmf_series.hip, psmf_blocked.hip, psmf_filter34.hip,
-// psmf_impute.hip): the handle, the switch table, the error helpers and the few host functions that cross unit boundaries.  A kernel is launched --
-// and its LDS opt-in is made -- only in the unit that defines it (the rule of psmf_pstep.h); across units only these functions are called.
+// psmf_impute.hip, psmf_ssm.hip, psmf_bocpd.hip): the handle, the switch table, the error helpers and the few host functions that cross
+// unit boundaries.  A kernel is launched -- and its LDS opt-in is made -- only in the unit that defines it (the rule of psmf_pstep.h);
+// across units only these functions are called; the entry points without a handle (the last three units) stand on psmf_batch.h.
 #pragma once
 #include "../../include/psmf_hip.h"
 #include "psmf_block.h"       // BlockParams
@@ -257,9 +258,6 @@ int rot_rows(psmf_filter* h, const void* src, void* dst, long long n, bool fwd);
 // psmf_series.hip: the series buffers (resident or a ring), their uploads, downloads and reductions
 int ring_run(psmf_filter* h, int64_t k_begin, int64_t k_end);      // psmf_run on a ring handle
 int sq_error_sum(psmf_filter* h, hipStream_t stream, int storage, const void* yp, const void* y, size_t n, double* part_d, double* acc);
-int impute_run_large(const psmf_impute_config* cfg, const double* YorgInt, const uint8_t* M, const uint8_t* Mmiss, double* C, double* X,
-                     const double* V, const double* P, const double* Q, double rho, double* Epred, double* Efull, double* inside,
-                     double* Yrec, double* YrecL, double* YrecH, int32_t* status, float* elapsed_ms);
 // psmf_blocked.hip: the blocked engine
 FilterKernel select_filter_kernel(const psmf_filter* h);
 int init_blocked(psmf_filter* h);

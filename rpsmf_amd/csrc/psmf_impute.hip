@@ -16,7 +16,8 @@
 // (PSMF.py:30-36), the Kalman update of x, the rank-1 updates of C and V, error bands.
 // Everything is latency-bound; inputs of column t+1 are prefetched while column t is processed, and the barriers inside the
 // column loop order LDS only (solve_barrier<true>): the prefetch and the per-column stores (X, bands) stay in flight across them.
-#include "psmf_host.h"        // Switches, g_create_error
+#include "psmf_host.h"        // Switches
+#include "psmf_batch.h"       // EntryFail, open_device, typed transfers, TimedLaunch, replica_status
 #include "psmf_impute3.hip"    // (and, through it, psmf_impute2.hip)
 
 #include <cmath>
@@ -44,19 +45,104 @@ extern "C" int psmf_impute_kernel_id(const psmf_impute_config* cfg) {
 }
 
 namespace {
+// psmf_impute_run beyond one workgroup's LDS (d > 512 or r > 16): the replicas one after the other on the masked per-step engine
+// of the large-d handle (psmf_masked.hip), float64 storage, through the public ABI alone.  ExperimentImpute/PSMF.py:59-95,
+// rPSMF.py:75-148: the prior mean of column 0 is X[:, n - 1] (the initial X on pass 0, the last posterior afterwards -- i.e. the
+// running mean), C, V, P carry over the passes, rPSMF restarts Q, rho, lambda at every pass; X[:, t] is the posterior mean of column t
+// (the mean history).
+hipError_t destroy_filter(psmf_handle h) { psmf_destroy(h); return hipSuccess; }
+using OwnedFilter = Owned<psmf_handle, destroy_filter>;
+
+int impute_run_large(const psmf_impute_config* cfg, const double* YorgInt, const uint8_t* M, const uint8_t* Mmiss, double* C, double* X,
+                     const double* V, const double* P, const double* Q, double rho, double* Epred, double* Efull, double* inside,
+                     double* Yrec, double* YrecL, double* YrecH, int32_t* status, float* elapsed_ms) {
+  const int d = cfg->d, n = cfg->n, r = cfg->r, B = cfg->batch, robust = cfg->method == 1, meth = cfg->method;
+  psmf_config pc;
+  memset(&pc, 0, sizeof(pc));
+  pc.abi_version = PSMF_ABI_VERSION; pc.d = d; pc.r = r; pc.row0 = 0; pc.d_local = d; pc.robust = robust;
+  pc.coef_update = 1; pc.eta_full = 1; pc.pbar_predict = 1; pc.dyn_kind = PSMF_DYN_RANDOM_WALK; pc.n_theta = 0;
+  pc.storage = PSMF_F64; pc.store_y_pred = 1; pc.update_every = 1; pc.device = cfg->device; pc.use_graph = 1; pc.engine = 1; pc.masked = meth >= 2 ? meth : 1;
+  pc.alpha = pc.beta = 1.0; pc.adam_lr = 1e-3; pc.adam_b1 = 0.9; pc.adam_b2 = 0.999;
+  OwnedFilter h;                   // released on every return, after `bail` has read its message
+  PSMF_TRY(psmf_create(h.put(), &pc));      // (g_create_error holds the message)
+  // a failed call's code, with the handle's message left where a caller without a handle looks for it
+  auto bail = [&](int code) { if (code) g_create_error = std::string("psmf_impute_run: ") + psmf_last_error(h); return code; };
+  PSMF_TRY(bail(psmf_upload_series(h, YorgInt, PSMF_F64, 0, n, n)));
+  const size_t nd = (size_t)n * d;
+  const double qnan = std::numeric_limits<double>::quiet_NaN();
+  std::vector<double> yp, sc;
+  double total_ms = 0.0;
+  for (int b = 0; b < B; ++b) {
+    double* Cb = C + (size_t)b * d * r;
+    double* Xb = X + (size_t)b * n * r;
+    PSMF_TRY(bail(psmf_upload_mask(h, M + (size_t)b * nd, 0, n)));
+    int rc;
+    if (meth == 3) {       // TMF (TMF.py:47,60): Pbar = I / nu at every step, nu = 2 -- as Q with P = 0 (the serial stage keeps P at 0); V unused
+      std::vector<double> Inu((size_t)r * r, 0.0), Zr((size_t)r * r, 0.0), Iv((size_t)r * r, 0.0);
+      for (int i = 0; i < r; ++i) { Inu[(size_t)i * r + i] = 0.5; Iv[(size_t)i * r + i] = 1.0; }
+      rc = psmf_set_state(h, Cb, Iv.data(), Zr.data(), Inu.data(), Xb + (size_t)(n - 1) * r, 1.0, 0.0, nullptr);
+    } else {
+      rc = psmf_set_state(h, Cb, V, P, Q, Xb + (size_t)(n - 1) * r, rho, robust ? cfg->lambda0 : 0.0, nullptr);
+    }
+    PSMF_TRY(bail(rc));
+    bool bad = false;
+    double m4[4] = {0, 0, 0, 0};
+    const auto t_start = std::chrono::steady_clock::now();
+    for (int it = 0; it < cfg->n_iter && !bad; ++it) {
+      if (it > 0 && robust) {        // rPSMF.py:77-79: Q, R, lambda restart; V, P, C and the mean carry over
+        PSMF_TRY(bail(psmf_set_state(h, nullptr, nullptr, nullptr, Q, nullptr, rho, cfg->lambda0, nullptr)));
+      }
+      if (meth >= 2) {       // gam = 1e-6 / (pass + 1)^0.7  (MLESMF.py:59-60, TMF.py:46-48)
+        PSMF_TRY(bail(psmf_set_step_size(h, 1e-6 / std::pow((double)(it + 1), 0.7))));
+      }
+      PSMF_TRY(bail(psmf_run(h, 0, n)));
+      rc = psmf_masked_metrics(h, Mmiss + (size_t)b * nd, 0, n, meth == 3 ? 0.0 : cfg->sig, m4);
+      if (rc == PSMF_ERR_NUMERIC) { bad = true; break; }
+      PSMF_TRY(bail(rc));
+      Epred[(size_t)b * cfg->n_iter + it] = std::sqrt(m4[0] / m4[3]);
+      Efull[(size_t)b * cfg->n_iter + it] = std::sqrt(m4[1] / m4[3]);
+      if (!std::isfinite(m4[0]) || !std::isfinite(m4[1])) bad = true;
+    }
+    total_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    if (!bad) {
+      inside[b] = m4[2] / m4[3];
+      rc = psmf_get_state(h, Cb, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+      if (!rc) rc = psmf_download_mu(h, Xb, 1, n);
+      if (!rc && cfg->want_bands) {
+        yp.resize(nd); sc.resize((size_t)2 * n);
+        rc = psmf_download_y_pred(h, yp.data(), PSMF_F64, 0, n);
+        if (!rc) rc = psmf_download_step_scalars(h, sc.data(), 0, n);
+        if (!rc) {
+          const uint8_t* Mb = M + (size_t)b * nd;
+          for (int t = 0; t < n; ++t)
+            for (int i = 0; i < d; ++i) {
+              const size_t at = (size_t)b * nd + (size_t)t * d + i;
+              const double yh = yp[(size_t)t * d + i];
+              const double band = meth == 3 ? 0.0 : cfg->sig * std::sqrt(robust ? (Mb[(size_t)t * d + i] ? sc[2 * t] : 0.0) + sc[2 * t + 1] : sc[2 * t] + sc[2 * t + 1]);
+              Yrec[at] = yh; YrecL[at] = yh - band; YrecH[at] = yh + band;
+            }
+        }
+      }
+      if (rc == PSMF_ERR_NUMERIC) bad = true;
+      else PSMF_TRY(bail(rc));
+    }
+    if (status) status[b] = bad ? PSMF_ERR_NUMERIC : PSMF_OK;
+    if (bad) {
+      if (!status) return bail(PSMF_ERR_NUMERIC);
+      for (int it = 0; it < cfg->n_iter; ++it) Epred[(size_t)b * cfg->n_iter + it] = Efull[(size_t)b * cfg->n_iter + it] = qnan;
+      inside[b] = qnan;
+    }
+  }
+  if (elapsed_ms) *elapsed_ms = (float)total_ms;
+  return PSMF_OK;
+}
+
 // psmf_impute_run (rho_rows == nullptr: R = rho I) and psmf_impute_run_rows (R = diag(rho_rows), entries not all equal; `rho` unused)
-int impute_run_impl(const char* who, const psmf_impute_config* cfg, const double* YorgInt, const uint8_t* M,
+int impute_run_impl(const EntryFail& fail, const psmf_impute_config* cfg, const double* YorgInt, const uint8_t* M,
                     const uint8_t* Mmiss, double* C, double* X, const double* V, const double* P,
                     const double* Q, double rho, const double* rho_rows, double* Epred, double* Efull, double* inside,
                     double* Yrec, double* YrecL, double* YrecH, int32_t* status, float* elapsed_ms) {
   using namespace psmf;
-  // every message starts with `who`; there is no handle here, and the three-argument form is the one HIP_TRY / ALLOC_TRY call
-  const struct {
-    const char* who;
-    int operator()(int code, const std::string& msg) const { g_create_error = std::string(who) + ": " + msg; return code; }
-    int operator()(psmf_handle, int code, const std::string& msg) const { return (*this)(code, msg); }
-  } fail{who};
-  const psmf_handle w = nullptr;
   if (!cfg || !YorgInt || !M || !Mmiss || !C || !X || !V || !P || !Q || !Epred || !Efull || !inside)
     return fail(PSMF_ERR_ARG, "null argument");
   if (cfg->abi_version != PSMF_ABI_VERSION) return fail(PSMF_ERR_ARG, "ABI version mismatch");
@@ -76,47 +162,24 @@ int impute_run_impl(const char* who, const psmf_impute_config* cfg, const double
   if (sel == 4)       // beyond one workgroup's LDS: the replicas one after the other on the masked per-step engine (psmf_masked.hip)
     return impute_run_large(cfg, YorgInt, M, Mmiss, C, X, V, P, Q, rho, Epred, Efull, inside, Yrec, YrecL, YrecH, status, elapsed_ms);
   const bool v3 = sel >= 300;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(PSMF_ERR_NO_DEVICE, "no HIP device visible");
-  if (cfg->device < 0 || cfg->device >= ndev) return fail(PSMF_ERR_ARG, "bad device ordinal");
+  PSMF_TRY(open_device(fail, cfg->device));
 
-  const size_t nd = (size_t)n * d, bnd = (size_t)B * nd;
+  const size_t nd = (size_t)n * d, bnd = (size_t)B * nd, nC = (size_t)B * d * r, nX = (size_t)B * n * r, rr = (size_t)r * r;
+  const size_t ni = cfg->n_iter, nbands = cfg->want_bands ? bnd : 0;
   Dev<double> dY, dC, dX, dV, dP, dQ, dEp, dEf, dIn, dYr, dYl, dYh, dRho;
   Dev<uint8_t> dM, dMm;
   Dev<int> dErr;
-  Event e0, e1;
+  TimedLaunch timed;
   std::vector<int> herr(B, 0);
   ImputeParams ip;
-  HIP_TRY(w, hipSetDevice(cfg->device));
-  ALLOC_TRY(w, dY.alloc(nd * 8));
-  ALLOC_TRY(w, dM.alloc(bnd));
-  ALLOC_TRY(w, dMm.alloc(bnd));
-  ALLOC_TRY(w, dC.alloc((size_t)B * d * r * 8));
-  ALLOC_TRY(w, dX.alloc((size_t)B * n * r * 8));
-  ALLOC_TRY(w, dV.alloc(r * r * 8));
-  ALLOC_TRY(w, dP.alloc(r * r * 8));
-  ALLOC_TRY(w, dQ.alloc(r * r * 8));
-  ALLOC_TRY(w, dEp.alloc((size_t)B * cfg->n_iter * 8));
-  ALLOC_TRY(w, dEf.alloc((size_t)B * cfg->n_iter * 8));
-  ALLOC_TRY(w, dIn.alloc((size_t)B * 8));
-  ALLOC_TRY(w, dErr.alloc((size_t)B * 4));
-  if (cfg->want_bands) {
-    ALLOC_TRY(w, dYr.alloc(bnd * 8));
-    ALLOC_TRY(w, dYl.alloc(bnd * 8));
-    ALLOC_TRY(w, dYh.alloc(bnd * 8));
-  }
-  if (rw) {
-    ALLOC_TRY(w, dRho.alloc((size_t)d * 8));
-    HIP_TRY(w, hipMemcpy(dRho, rho_rows, (size_t)d * 8, hipMemcpyHostToDevice));
-  }
-  HIP_TRY(w, hipMemcpy(dY, YorgInt, nd * 8, hipMemcpyHostToDevice));
-  HIP_TRY(w, hipMemcpy(dM, M, bnd, hipMemcpyHostToDevice));
-  HIP_TRY(w, hipMemcpy(dMm, Mmiss, bnd, hipMemcpyHostToDevice));
-  HIP_TRY(w, hipMemcpy(dC, C, (size_t)B * d * r * 8, hipMemcpyHostToDevice));
-  HIP_TRY(w, hipMemcpy(dX, X, (size_t)B * n * r * 8, hipMemcpyHostToDevice));
-  HIP_TRY(w, hipMemcpy(dV, V, r * r * 8, hipMemcpyHostToDevice));
-  HIP_TRY(w, hipMemcpy(dP, P, r * r * 8, hipMemcpyHostToDevice));
-  HIP_TRY(w, hipMemcpy(dQ, Q, r * r * 8, hipMemcpyHostToDevice));
+  const auto io = std::make_tuple(      // buffer, filled from, read back to, elements
+      slot(dY, YorgInt, nullptr, nd), slot(dM, M, nullptr, bnd), slot(dMm, Mmiss, nullptr, bnd),
+      slot(dC, C, C, nC), slot(dX, X, X, nX), slot(dV, V, nullptr, rr), slot(dP, P, nullptr, rr), slot(dQ, Q, nullptr, rr),
+      slot(dEp, nullptr, Epred, B * ni), slot(dEf, nullptr, Efull, B * ni), slot(dIn, nullptr, inside, B), slot(dErr, nullptr, herr.data(), B),
+      slot(dYr, nullptr, Yrec, nbands), slot(dYl, nullptr, YrecL, nbands), slot(dYh, nullptr, YrecH, nbands));
+  PSMF_TRY(alloc_all(fail, io));
+  if (rw) PSMF_TRY(alloc_copy_in(fail, dRho, rho_rows, d));
+  PSMF_TRY(copy_in_all(fail, io));
   ip.d = d; ip.n = n; ip.r = r; ip.n_iter = cfg->n_iter; ip.robust = cfg->method == 1; ip.method = cfg->method; ip.want_bands = cfg->want_bands;
   ip.sig = cfg->sig; ip.lambda0 = cfg->lambda0; ip.rho0 = rho;
   ip.Yorg = dY; ip.M = dM; ip.Mmiss = dMm; ip.C = dC; ip.X = dX; ip.V0 = dV; ip.P0 = dP; ip.Q0 = dQ;
@@ -130,40 +193,23 @@ int impute_run_impl(const char* who, const psmf_impute_config* cfg, const double
     ip.q_iso = iso ? 1 : 0;
   }
   const void* const kern = v3 ? impute3_kernel(d, rw) : (rw ? (const void*)psmf_impute_kernel2w : (const void*)psmf_impute_kernel2);
-  if (lds > 48 * 1024) HIP_TRY(w, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  HIP_TRY(w, hipEventCreate(e0.put()));
-  HIP_TRY(w, hipEventCreate(e1.put()));
-  HIP_TRY(w, hipEventRecord(e0, 0));
-  { void* args[] = {&ip}; HIP_TRY(w, hipLaunchKernel(kern, dim3(B), dim3(WG), args, lds, 0)); }
-  HIP_TRY(w, hipGetLastError());
-  HIP_TRY(w, hipEventRecord(e1, 0));
-  HIP_TRY(w, hipEventSynchronize(e1));
-  if (elapsed_ms) HIP_TRY(w, hipEventElapsedTime(elapsed_ms, e0, e1));
-  HIP_TRY(w, hipMemcpy(C, dC, (size_t)B * d * r * 8, hipMemcpyDeviceToHost));
-  HIP_TRY(w, hipMemcpy(X, dX, (size_t)B * n * r * 8, hipMemcpyDeviceToHost));
-  HIP_TRY(w, hipMemcpy(Epred, dEp, (size_t)B * cfg->n_iter * 8, hipMemcpyDeviceToHost));
-  HIP_TRY(w, hipMemcpy(Efull, dEf, (size_t)B * cfg->n_iter * 8, hipMemcpyDeviceToHost));
-  HIP_TRY(w, hipMemcpy(inside, dIn, (size_t)B * 8, hipMemcpyDeviceToHost));
-  HIP_TRY(w, hipMemcpy(herr.data(), dErr, (size_t)B * 4, hipMemcpyDeviceToHost));
-  if (cfg->want_bands) {
-    HIP_TRY(w, hipMemcpy(Yrec, dYr, bnd * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(w, hipMemcpy(YrecL, dYl, bnd * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(w, hipMemcpy(YrecH, dYh, bnd * 8, hipMemcpyDeviceToHost));
-  }
+  PSMF_TRY(timed.run(fail, kern, dim3(B), dim3(WG), &ip, lds, elapsed_ms));
+  PSMF_TRY(copy_out_all(fail, io));
   // Per-replica outcome (the reference records NaN for a diverged repeat and carries on, ExperimentImpute/rPSMF.py:236-243): a
   // replica whose r x r system lost positive definiteness -- or whose errors are not finite -- gets status PSMF_ERR_NUMERIC and NaN
   // results; the other replicas are untouched by it (one workgroup each).  Without a status array the call fails as a whole.
   for (int b = 0; b < B; ++b)
     if (herr[b] == 9) return fail(PSMF_ERR_HIP, "internal error: the wave programs of the column loop executed different numbers of barriers (imp_barrier_check)");
-  for (int b = 0; b < B; ++b) {
-    bool bad = herr[b] != 0;
-    for (int it = 0; it < cfg->n_iter && !bad; ++it)
-      bad = !std::isfinite(Epred[(size_t)b * cfg->n_iter + it]) || !std::isfinite(Efull[(size_t)b * cfg->n_iter + it]);
-    if (status) status[b] = bad ? PSMF_ERR_NUMERIC : PSMF_OK;
-    if (!bad) continue;
-    if (!status) return fail(PSMF_ERR_NUMERIC, "singular r x r system in replica " + std::to_string(b));
-    const double qnan = std::numeric_limits<double>::quiet_NaN();
-    for (int it = 0; it < cfg->n_iter; ++it) Epred[(size_t)b * cfg->n_iter + it] = Efull[(size_t)b * cfg->n_iter + it] = qnan;
+  const auto bad = [&](int b) {
+    bool nf = herr[b] != 0;
+    for (size_t i = b * ni; i < (b + 1) * ni && !nf; ++i) nf = !std::isfinite(Epred[i]) || !std::isfinite(Efull[i]);
+    return nf;
+  };
+  PSMF_TRY(replica_status(fail, B, status, bad, [](int b) { return "singular r x r system in replica " + std::to_string(b); }));
+  const double qnan = std::numeric_limits<double>::quiet_NaN();
+  for (int b = 0; status && b < B; ++b) {      // (without a status array a bad replica has failed the call above)
+    if (status[b] == PSMF_OK) continue;
+    for (size_t i = b * ni; i < (b + 1) * ni; ++i) Epred[i] = Efull[i] = qnan;
     inside[b] = qnan;
   }
   return PSMF_OK;
@@ -174,7 +220,7 @@ extern "C" int psmf_impute_run(const psmf_impute_config* cfg, const double* Yorg
                                const uint8_t* Mmiss, double* C, double* X, const double* V, const double* P,
                                const double* Q, double rho, double* Epred, double* Efull, double* inside,
                                double* Yrec, double* YrecL, double* YrecH, int32_t* status, float* elapsed_ms) {
-  return impute_run_impl("psmf_impute_run", cfg, YorgInt, M, Mmiss, C, X, V, P, Q, rho, nullptr, Epred, Efull, inside, Yrec, YrecL, YrecH,
+  return impute_run_impl(EntryFail{"psmf_impute_run"}, cfg, YorgInt, M, Mmiss, C, X, V, P, Q, rho, nullptr, Epred, Efull, inside, Yrec, YrecL, YrecH,
                          status, elapsed_ms);
 }
 
@@ -186,18 +232,16 @@ extern "C" int psmf_impute_run_rows(const psmf_impute_config* cfg, const double*
                                     const uint8_t* Mmiss, double* C, double* X, const double* V, const double* P,
                                     const double* Q, const double* rho_rows, double* Epred, double* Efull, double* inside,
                                     double* Yrec, double* YrecL, double* YrecH, int32_t* status, float* elapsed_ms) {
-  const char* who = "psmf_impute_run_rows";
-  if (!cfg || !rho_rows) { g_create_error = std::string(who) + ": null argument"; return PSMF_ERR_ARG; }
-  if (cfg->abi_version != PSMF_ABI_VERSION) { g_create_error = std::string(who) + ": ABI version mismatch"; return PSMF_ERR_ARG; }
-  if (cfg->d < 1) { g_create_error = std::string(who) + ": need d >= 1"; return PSMF_ERR_ARG; }
+  const EntryFail fail{"psmf_impute_run_rows"};
+  if (!cfg || !rho_rows) return fail(PSMF_ERR_ARG, "null argument");
+  if (cfg->abi_version != PSMF_ABI_VERSION) return fail(PSMF_ERR_ARG, "ABI version mismatch");
+  if (cfg->d < 1) return fail(PSMF_ERR_ARG, "need d >= 1");
   bool uniform = true;
   for (int i = 0; i < cfg->d; ++i) {
-    if (!std::isfinite(rho_rows[i]) || rho_rows[i] < 0.0) {
-      g_create_error = std::string(who) + ": the entries of diag(R) must be finite and >= 0 (row " + std::to_string(i) + ")";
-      return PSMF_ERR_ARG;
-    }
+    if (!std::isfinite(rho_rows[i]) || rho_rows[i] < 0.0)
+      return fail(PSMF_ERR_ARG, "the entries of diag(R) must be finite and >= 0 (row " + std::to_string(i) + ")");
     uniform = uniform && rho_rows[i] == rho_rows[0];
   }
-  return impute_run_impl(who, cfg, YorgInt, M, Mmiss, C, X, V, P, Q, rho_rows[0], (uniform || cfg->method == 3) ? nullptr : rho_rows,
+  return impute_run_impl(fail, cfg, YorgInt, M, Mmiss, C, X, V, P, Q, rho_rows[0], (uniform || cfg->method == 3) ? nullptr : rho_rows,
                          Epred, Efull, inside, Yrec, YrecL, YrecH, status, elapsed_ms);
 }

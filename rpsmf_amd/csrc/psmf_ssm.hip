@@ -19,7 +19,8 @@
 // in flight across them.  G and h come from the augmented [C | e] product on the float64 matrix cores, recomputed every step, as in
 // psmf_impute2.hip; the p x p and p x r products of the step (A P_prev, its product with A^T, Pbar H^T, its product with W, the update
 // of P) run there too, one 16 x 16 output tile per wave.  Limits: d <= 512, r <= 16, r <= p <= 32.
-#include "psmf_host.h"        // g_create_error, HIP_TRY, Dev<>, Event
+#include "psmf_host.h"        // WG and the device headers
+#include "psmf_batch.h"       // EntryFail, open_device, typed transfers, TimedLaunch, replica_status
 #include "psmf_sweep.h"       // solve_barrier
 #include "psmf_wave16.hip"    // wave_sweep16m, Sw16K
 
@@ -511,16 +512,9 @@ namespace psmf {
 namespace {
 
 // psmf_ssm_run (ex = false: `scalars` is batch x n x 2, no mask, not robust) and psmf_ssm_run_ex (batch x n x 4)
-int ssm_run(const char* who, bool ex, const psmf_ssm_config_ex* cfg, const double* Y, const uint8_t* mask, double* C, double* V, double* x,
+int ssm_run(const EntryFail& fail, bool ex, const psmf_ssm_config_ex* cfg, const double* Y, const uint8_t* mask, double* C, double* V, double* x,
             double* P, const double* A, const double* Q, const double* H, double rho, double* robust_state, double* X, double* Ypred,
             double* scalars, int32_t* status, float* elapsed_ms) {
-  struct Fail {
-    const char* who;
-    int operator()(int code, const std::string& msg) const { g_create_error = std::string(who) + ": " + msg; return code; }
-    int operator()(psmf_handle, int code, const std::string& msg) const { return (*this)(code, msg); }
-  };
-  const Fail fail{who};
-  const psmf_handle w = nullptr;
   if (!cfg || !Y || !C || !V || !x || !P || !A || !Q || !H || !X) return fail(PSMF_ERR_ARG, "null argument");
   if (cfg->abi_version != PSMF_ABI_VERSION) return fail(PSMF_ERR_ARG, "ABI version mismatch");
   const bool robust = cfg->robust != 0, masked = mask != nullptr;
@@ -581,46 +575,27 @@ int ssm_run(const char* who, bool ex, const psmf_ssm_config_ex* cfg, const doubl
         }
       }
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(PSMF_ERR_NO_DEVICE, "no HIP device visible");
-  if (cfg->device < 0 || cfg->device >= ndev) return fail(PSMF_ERR_ARG, "bad device ordinal");
+  PSMF_TRY(open_device(fail, cfg->device));
 
   const size_t nY = (size_t)B * n * d, nC = (size_t)B * d * r, nV = (size_t)B * r * r, nx = (size_t)B * np, nP = (size_t)B * np * np;
+  const size_t pp = (size_t)np * np, rp = (size_t)r * np;
   const bool plain = !robust && !masked;       // the plain instance writes two scalars per step
   const size_t nX = (size_t)B * n * np, nS = (size_t)B * n * (plain ? 2 : 4);
   Dev<double> dY, dC, dV, dx, dP, dA, dQ, dH, dX, dYp, dSc, dRs;
   Dev<unsigned char> dM;
   Dev<int> dErr;
-  Event e0, e1;
+  TimedLaunch timed;
   std::vector<int> herr(B, 0);
-  HIP_TRY(w, hipSetDevice(cfg->device));
-  ALLOC_TRY(w, dY.alloc(nY * 8));
-  ALLOC_TRY(w, dC.alloc(nC * 8));
-  ALLOC_TRY(w, dV.alloc(nV * 8));
-  ALLOC_TRY(w, dx.alloc(nx * 8));
-  ALLOC_TRY(w, dP.alloc(nP * 8));
-  ALLOC_TRY(w, dA.alloc((size_t)np * np * 8));
-  ALLOC_TRY(w, dQ.alloc((size_t)np * np * 8));
-  ALLOC_TRY(w, dH.alloc((size_t)r * np * 8));
-  ALLOC_TRY(w, dX.alloc(nX * 8));
-  ALLOC_TRY(w, dErr.alloc((size_t)B * 4));
-  if (cfg->want_pred) ALLOC_TRY(w, dYp.alloc(nY * 8));
-  if (scalars) ALLOC_TRY(w, dSc.alloc(nS * 8));
-  HIP_TRY(w, hipMemcpy(dY, Y, nY * 8, hipMemcpyHostToDevice));
-  HIP_TRY(w, hipMemcpy(dC, C, nC * 8, hipMemcpyHostToDevice));
-  HIP_TRY(w, hipMemcpy(dV, V, nV * 8, hipMemcpyHostToDevice));
-  HIP_TRY(w, hipMemcpy(dx, x, nx * 8, hipMemcpyHostToDevice));
-  HIP_TRY(w, hipMemcpy(dP, P, nP * 8, hipMemcpyHostToDevice));
-  HIP_TRY(w, hipMemcpy(dA, A, (size_t)np * np * 8, hipMemcpyHostToDevice));
-  HIP_TRY(w, hipMemcpy(dQ, Q, (size_t)np * np * 8, hipMemcpyHostToDevice));
-  HIP_TRY(w, hipMemcpy(dH, H, (size_t)r * np * 8, hipMemcpyHostToDevice));
-  if (masked) {
-    ALLOC_TRY(w, dM.alloc(nY));
-    HIP_TRY(w, hipMemcpy(dM, mask, nY, hipMemcpyHostToDevice));
-  }
+  const auto io = std::make_tuple(      // buffer, filled from, read back to, elements
+      slot(dY, Y, nullptr, nY), slot(dC, C, C, nC), slot(dV, V, V, nV), slot(dx, x, x, nx), slot(dP, P, P, nP),
+      slot(dA, A, nullptr, pp), slot(dQ, Q, nullptr, pp), slot(dH, H, nullptr, rp), slot(dX, nullptr, X, nX), slot(dErr, nullptr, nullptr, B),
+      slot(dYp, nullptr, Ypred, cfg->want_pred ? nY : 0), slot(dSc, nullptr, scalars, scalars ? nS : 0));
+  PSMF_TRY(alloc_all(fail, io));
+  PSMF_TRY(copy_in_all(fail, io));
+  if (masked) PSMF_TRY(alloc_copy_in(fail, dM, mask, nY));
   if (robust) {
-    ALLOC_TRY(w, dRs.alloc((size_t)B * 2 * 8));
-    if (!cfg->first_step) HIP_TRY(w, hipMemcpy(dRs, robust_state, (size_t)B * 2 * 8, hipMemcpyHostToDevice));
+    PSMF_TRY(alloc_n(fail, dRs, (size_t)B * 2));
+    if (!cfg->first_step) PSMF_TRY(copy_in(fail, dRs, robust_state, (size_t)B * 2));
   }
   SsmParamsEx sp;
   sp.d = d; sp.n = n; sp.r = r; sp.p = np; sp.carry_P = cfg->carry_P != 0; sp.first_step = cfg->first_step != 0; sp.rho = rho;
@@ -631,39 +606,25 @@ int ssm_run(const char* who, bool ex, const psmf_ssm_config_ex* cfg, const doubl
   SsmParams sp0 = sp;       // what the plain instance takes
   const void* const kern = robust ? (masked ? (const void*)psmf_ssm_kernel<true, true> : (const void*)psmf_ssm_kernel<true, false>)
                                   : (masked ? (const void*)psmf_ssm_kernel<false, true> : (const void*)psmf_ssm_kernel<false, false>);
-  if (lds > 48 * 1024) HIP_TRY(w, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  HIP_TRY(w, hipEventCreate(e0.put()));
-  HIP_TRY(w, hipEventCreate(e1.put()));
-  HIP_TRY(w, hipEventRecord(e0, 0));
-  { void* args[] = {plain ? (void*)&sp0 : (void*)&sp}; HIP_TRY(w, hipLaunchKernel(kern, dim3(B), dim3(WG), args, lds, 0)); }
-  HIP_TRY(w, hipGetLastError());
-  HIP_TRY(w, hipEventRecord(e1, 0));
-  HIP_TRY(w, hipEventSynchronize(e1));
-  if (elapsed_ms) HIP_TRY(w, hipEventElapsedTime(elapsed_ms, e0, e1));
-  HIP_TRY(w, hipMemcpy(C, dC, nC * 8, hipMemcpyDeviceToHost));
-  HIP_TRY(w, hipMemcpy(V, dV, nV * 8, hipMemcpyDeviceToHost));
-  HIP_TRY(w, hipMemcpy(x, dx, nx * 8, hipMemcpyDeviceToHost));
-  HIP_TRY(w, hipMemcpy(P, dP, nP * 8, hipMemcpyDeviceToHost));
-  HIP_TRY(w, hipMemcpy(X, dX, nX * 8, hipMemcpyDeviceToHost));
-  if (cfg->want_pred) HIP_TRY(w, hipMemcpy(Ypred, dYp, nY * 8, hipMemcpyDeviceToHost));
-  if (scalars) HIP_TRY(w, hipMemcpy(scalars, dSc, nS * 8, hipMemcpyDeviceToHost));
+  PSMF_TRY(timed.run(fail, kern, dim3(B), dim3(WG), plain ? (void*)&sp0 : (void*)&sp, lds, elapsed_ms));
+  PSMF_TRY(copy_out_all(fail, io));
   if (scalars && ex && plain)       // (s, eta) -> (s, eta, omega = 1, phi = 1), in place from the back
     for (size_t i = (size_t)B * n; i-- > 0;) {
       const double s0 = scalars[2 * i], s1 = scalars[2 * i + 1];
       scalars[4 * i] = s0; scalars[4 * i + 1] = s1; scalars[4 * i + 2] = 1.0; scalars[4 * i + 3] = 1.0;
     }
-  if (robust) HIP_TRY(w, hipMemcpy(robust_state, dRs, (size_t)B * 2 * 8, hipMemcpyDeviceToHost));
-  HIP_TRY(w, hipMemcpy(herr.data(), dErr, (size_t)B * 4, hipMemcpyDeviceToHost));
-  // Per-replica outcome, as psmf_impute_run: a replica whose r x r system lost positive definiteness, or whose state is not finite, gets
-  // PSMF_ERR_NUMERIC; the other replicas are untouched by it (one workgroup each).  Without a status array it fails the call.
-  for (int b = 0; b < B; ++b) {
-    bool bad = herr[b] != 0;
-    for (int i = 0; i < np && !bad; ++i) bad = !std::isfinite(x[(size_t)b * np + i]);
-    for (size_t i = 0; i < (size_t)d * r && !bad; ++i) bad = !std::isfinite(C[(size_t)b * d * r + i]);
-    if (status) status[b] = bad ? PSMF_ERR_NUMERIC : PSMF_OK;
-    if (bad && !status) return fail(PSMF_ERR_NUMERIC, "the r x r system lost positive definiteness, or the state is not finite, in replica " + std::to_string(b));
-  }
-  return PSMF_OK;
+  if (robust) PSMF_TRY(copy_out(fail, robust_state, dRs, (size_t)B * 2));
+  PSMF_TRY(copy_out(fail, herr.data(), dErr, B));
+  // Per-replica outcome, as psmf_impute_run; the other replicas are untouched by a bad one (one workgroup each).
+  const auto bad = [&](int b) {
+    bool nf = herr[b] != 0;
+    for (int i = 0; i < np && !nf; ++i) nf = !std::isfinite(x[(size_t)b * np + i]);
+    for (size_t i = 0; i < (size_t)d * r && !nf; ++i) nf = !std::isfinite(C[(size_t)b * d * r + i]);
+    return nf;
+  };
+  return replica_status(fail, B, status, bad, [](int b) {
+    return "the r x r system lost positive definiteness, or the state is not finite, in replica " + std::to_string(b);
+  });
 }
 
 }  // namespace
@@ -677,11 +638,11 @@ extern "C" int psmf_ssm_run(const psmf_ssm_config* cfg, const double* Y, double*
     c.abi_version = cfg->abi_version; c.d = cfg->d; c.n = cfg->n; c.r = cfg->r; c.p = cfg->p; c.batch = cfg->batch; c.device = cfg->device;
     c.carry_P = cfg->carry_P; c.first_step = cfg->first_step; c.want_pred = cfg->want_pred;
   }
-  return psmf::ssm_run("psmf_ssm_run", false, cfg ? &c : nullptr, Y, nullptr, C, V, x, P, A, Q, H, rho, nullptr, X, Ypred, scalars, status, elapsed_ms);
+  return psmf::ssm_run(EntryFail{"psmf_ssm_run"}, false, cfg ? &c : nullptr, Y, nullptr, C, V, x, P, A, Q, H, rho, nullptr, X, Ypred, scalars, status, elapsed_ms);
 }
 
 extern "C" int psmf_ssm_run_ex(const psmf_ssm_config_ex* cfg, const double* Y, const uint8_t* mask, double* C, double* V, double* x,
                                double* P, const double* A, const double* Q, const double* H, double rho, double* robust_state, double* X,
                                double* Ypred, double* scalars, int32_t* status, float* elapsed_ms) {
-  return psmf::ssm_run("psmf_ssm_run_ex", true, cfg, Y, mask, C, V, x, P, A, Q, H, rho, robust_state, X, Ypred, scalars, status, elapsed_ms);
+  return psmf::ssm_run(EntryFail{"psmf_ssm_run_ex"}, true, cfg, Y, mask, C, V, x, P, A, Q, H, rho, robust_state, X, Ypred, scalars, status, elapsed_ms);
 }

@@ -157,19 +157,12 @@ def impute_batch(YorgInt, M, Mmiss, C0, X0, V, Q, R, P, sig, Iter, robust=False,
                                  sig=float(sig), lambda0=float(lambda0))
     ms = C.c_float()
     status = np.zeros(B, dtype=np.int32)
-    dp = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
-    up = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint8))
-    run, noise = (lib.psmf_impute_run, rho) if rho_rows is None else (lib.psmf_impute_run_rows, dp(rho_rows))
-    rc = run(C.byref(cfg), dp(Yt), up(Mt), up(Mmt), dp(Cb), dp(Xb), dp(Vm), dp(Pm), dp(Qm),
-             noise, dp(Epred), dp(Efull), dp(inside), dp(bands[0]), dp(bands[1]),
-             dp(bands[2]), status.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(ms))
-    if rc != _capi.OK:
-        msg = lib.psmf_last_error(None).decode()
-        if rc == _capi.ERR_NUMERIC:
-            raise np.linalg.LinAlgError(msg)
-        if rc == _capi.ERR_ARG:
-            raise ValueError(msg)
-        raise _capi.PsmfError(f"psmf_impute_run failed ({rc}): {msg}")
+    ptr = _capi._ptr
+    run, noise = (lib.psmf_impute_run, rho) if rho_rows is None else (lib.psmf_impute_run_rows, ptr(rho_rows))
+    rc = run(C.byref(cfg), ptr(Yt), ptr(Mt), ptr(Mmt), ptr(Cb), ptr(Xb), ptr(Vm), ptr(Pm), ptr(Qm),
+             noise, ptr(Epred), ptr(Efull), ptr(inside), ptr(bands[0]), ptr(bands[1]),
+             ptr(bands[2]), ptr(status), C.byref(ms))
+    _capi.raise_for(lib, rc, f"psmf_impute_run failed ({rc})")
     # a replica whose r x r system broke down has NaN results and status != 0; the others are complete (the reference's
     # repeats loop records NaN for such a repeat and carries on, ExperimentImpute/rPSMF.py:236-243)
     out = dict(Epred=Epred, Efull=Efull, inside=inside, C=Cb, X=np.transpose(Xb, (0, 2, 1)), elapsed_ms=ms.value, status=status,

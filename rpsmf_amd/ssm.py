@@ -156,8 +156,7 @@ def linear_psmf_batch(Y, C0, x0, V0, P0, A, Q, H, rho, *, carry_P=True, first_st
     cfg = _capi.PsmfSsmConfig(abi_version=_capi.ABI_VERSION, d=d, n=n, r=r, p=p, batch=B, device=int(device), carry_P=int(bool(carry_P)),
                               first_step=int(bool(first_step)), want_pred=int(bool(want_pred)))
     ms = C.c_float()
-    dp = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
-    stp = None if st is None else st.ctypes.data_as(C.POINTER(C.c_int32))
+    dp = _capi._ptr
     if ex:
         robust = bool(robust)
         if robust:
@@ -178,23 +177,14 @@ def linear_psmf_batch(Y, C0, x0, V0, P0, A, Q, H, rho, *, carry_P=True, first_st
                                     carry_P=int(bool(carry_P)), first_step=int(bool(first_step)), want_pred=int(bool(want_pred)),
                                     robust=int(robust), fixed_lambda=int(bool(fixed_lambda)), lambda0=float(lambda0) if robust else 0.0,
                                     alpha=float(alpha), beta=float(beta))
-        lib = _capi.load_library()
-        rc = lib.psmf_ssm_run_ex(C.byref(cfx), dp(Yt), None if Mb is None else Mb.ctypes.data_as(C.POINTER(C.c_uint8)), dp(Cb), dp(Vb),
-                                 dp(xb), dp(Pb), dp(A), dp(Q), dp(H), float(rho), dp(rs) if robust else None, dp(Xb), dp(Yp), dp(sc), stp,
-                                 C.byref(ms))
-        name = "psmf_ssm_run_ex"
+        name, args = "psmf_ssm_run_ex", (C.byref(cfx), dp(Yt), dp(Mb), dp(Cb), dp(Vb), dp(xb), dp(Pb), dp(A), dp(Q), dp(H), float(rho),
+                                         dp(rs) if robust else None, dp(Xb), dp(Yp), dp(sc), dp(st), C.byref(ms))
     else:
-        lib = _capi.load_library()
-        rc = lib.psmf_ssm_run(C.byref(cfg), dp(Yt), dp(Cb), dp(Vb), dp(xb), dp(Pb), dp(A), dp(Q), dp(H), float(rho), dp(Xb), dp(Yp), dp(sc),
-                              stp, C.byref(ms))
-        name = "psmf_ssm_run"
-    if rc != _capi.OK:
-        msg = lib.psmf_last_error(None).decode()
-        if rc == _capi.ERR_NUMERIC:
-            raise np.linalg.LinAlgError(msg)
-        if rc == _capi.ERR_ARG:
-            raise ValueError(msg)
-        raise _capi.PsmfError(f"{name} failed ({rc}): {msg}")
+        name, args = "psmf_ssm_run", (C.byref(cfg), dp(Yt), dp(Cb), dp(Vb), dp(xb), dp(Pb), dp(A), dp(Q), dp(H), float(rho), dp(Xb), dp(Yp), dp(sc),
+                                      dp(st), C.byref(ms))
+    lib = _capi.load_library()
+    rc = getattr(lib, name)(*args)
+    _capi.raise_for(lib, rc, f"{name} failed ({rc})")
     out = dict(X=np.transpose(Xb, (0, 2, 1)), C=Cb, V=Vb, P=Pb, x=xb, Ypred=None if Yp is None else np.transpose(Yp, (0, 2, 1)),
                scalars=sc, status=st, elapsed_ms=ms.value)
     if ex:
