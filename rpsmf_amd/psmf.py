@@ -22,9 +22,13 @@ in addition to dense matrices (dense d x d is unusable at d >= 10^4); derivative
 nonlinearity are analytic / complex-step instead of autograd.
 """
 
+from functools import cached_property
+
 import numpy as np
 
-from . import _capi
+from . import _capi, _noise
+from ._noise import diag_of as _diag_of
+from ._session import DeviceSession, _content_hash, _Lazy, _StateDict  # noqa: F401  (names other modules import from here)
 from .learning_rate import BaseLearningRate, ConstantLearningRate
 from .linop import InverseInnovation
 from .nonlinearities import BaseNonLinearity, wrap_nonlinearity
@@ -52,30 +56,6 @@ HIP_MODE_HOOKS = {
 }
 # drive-level methods the fused loop replaces as a whole
 FUSED_METHODS = ("inner", "_store_gradient", "_set_gradient", "_reset_gradient", "_carry_theta")
-
-
-class _Lazy:
-    """A value that lives on the device until somebody asks for it."""
-
-    def __init__(self, owner, name, epoch):
-        self.owner, self.name, self.epoch = owner, name, epoch
-
-    def fetch(self):
-        return self.owner._fetch_device(self.name, self.epoch)
-
-
-class _StateDict(dict):
-    """dict k -> array whose values may be device-resident (_Lazy) until first read."""
-
-    def __getitem__(self, k):
-        v = dict.__getitem__(self, k)
-        if isinstance(v, _Lazy):
-            v = v.fetch()
-            dict.__setitem__(self, k, v)
-        return v
-
-    def raw(self, k):
-        return dict.__getitem__(self, k)
 
 
 class _MuHist(_StateDict):
@@ -118,46 +98,10 @@ class _YPred(dict):
         return dict.__contains__(self, k) or (self._owner is not None and 1 <= k <= self._T)
 
 
-def _diag_of(R, d):
-    """diag(R) as scalar or (d,) vector, or None if R is a non-diagonal d x d matrix.  Accepted shapes: scalar, (1,),
-    (1, 1), (d,), (d, 1), (1, d), (d, d); anything else raises (a silently broadcast R would give wrong numbers)."""
-    if np.ndim(R) == 0:
-        return float(R)
-    R = np.asarray(R)
-    if R.size == 1:
-        return float(R.reshape(()))
-    if R.shape in ((d,), (d, 1), (1, d)):
-        return R.reshape(-1).astype(float)
-    if R.shape != (d, d):
-        raise ValueError(f"R has shape {R.shape}: expected a scalar, a (d,) diagonal or a (d, d) matrix with d = {d}")
-    dg = np.diagonal(R)
-    if np.count_nonzero(R) != np.count_nonzero(dg):
-        return None
-    return dg.astype(float)
-
-
-def _content_hash(a):
-    try:
-        import xxhash
-
-        return xxhash.xxh3_128_hexdigest(a.data)
-    except ImportError:
-        import hashlib
-
-        return hashlib.blake2b(a.data, digest_size=16).hexdigest()
-
-
 def _recognise_default():
     import os
 
     return os.environ.get("PSMF_RECOGNISE", "1").strip().lower() not in ("0", "false", "off", "no")
-
-
-def _as_scalar_if_uniform(rho):
-    if np.ndim(rho) == 0:
-        return float(rho)
-    rho = np.asarray(rho)
-    return float(rho[0]) if np.all(rho == rho[0]) else None
 
 
 class PSMFIter:
@@ -196,10 +140,8 @@ class PSMFIter:
         self._theta = {0: theta0}
         self._y_pred = {}
         self._gradsum = np.zeros(np.asarray(theta0).shape)
-        self._dev = None
         self._dev_opts = dict(device=device, storage=storage, gram_refresh=gram_refresh, engine=engine)
-        self._dev_epoch = 0
-        self._series_key = None
+        self._session = DeviceSession(self)      # (created here, so that a probe object of modes.py has its own; no handle yet)
         if backend == "hip":
             self._check_hip_configuration()
 
@@ -207,10 +149,7 @@ class PSMFIter:
     def run(self, y, T, n_iter, n_pred, mask=None):
         self.optim_init()
         for i in range(1, n_iter + 1):
-            if mask is None:
-                self.step(y, i, T)
-            else:
-                self.step(y, i, T, mask=mask)
+            self.step(y, i, T, **({} if mask is None else dict(mask=mask)))      # (a step() written against the reference takes no mask)
             self.predict(i, T, n_pred)
             self.optim_update(i)
 
@@ -236,12 +175,18 @@ class PSMFIter:
         if mask is not None and self.backend != "hip":
             raise NotImplementedError('mask=: backend="numpy" executes the reference\'s hooks, which know no missing entries; use backend="hip"')
         if self.backend == "hip":
-            return self._step_hip(y, i, T, mask)
+            self._device_epoch(i, T, y, mask)
+            return
         self.step_reset()
         for k in range(1, T + 1):
             self.inner(i, k, np.asarray(y[k]).reshape(-1, 1))     # y[k], k = 1..T: dict or array-like (row 0 unused)
 
     def inner(self, i, k, yk):
+        self._filter_step(i, k, yk)
+        self._prune(k)
+
+    def _filter_step(self, i, k, yk):
+        """The hook sequence of one step, in the reference's order (psmf.py:90-101; the recursive inner(), psmf.py:288-298, calls it with i = k)."""
         mu_bar = self._predictive_mean(i, k)
         P_bar = self._predictive_covariance(i, k)
         self._y_pred[k] = self._predict_measurement(k, mu_bar)
@@ -253,7 +198,6 @@ class PSMFIter:
         self._update_coefficient_mean(k, yk, Skinv, mu_bar, P_bar)
         self._update_coefficient_covariance(k, Skinv, P_bar, yk)
         self._store_gradient(i, k, yk, eta_k)
-        self._prune(k)
 
     # ------------------------------------------------------------------ hooks (numpy backend)
     def _q_at(self, k):
@@ -441,287 +385,166 @@ class PSMFIter:
         if self._r > _capi.RMAX:
             raise ValueError(f"r = {self._r} > {_capi.RMAX}")
 
-    def _rho_of(self, Rk):
-        dg = _diag_of(Rk, self._d)
-        rho = None if dg is None else _as_scalar_if_uniform(dg)
-        if rho is None:
-            if dg is not None and self._dense_noise() is None and np.array_equal(dg, self._row_noise()):
-                return 1.0          # the scalar in front of diag(rho_rows) (psmf_set_row_noise)
-            if dg is None and self._dense_noise() is not None and (Rk is self._first_R() or np.array_equal(Rk, self._first_R())):
-                return 1.0          # the scalar in front of U diag(lam) U^T (psmf_set_noise_rotation)
-            raise NotImplementedError("the device path needs R_k = rho_k * I, or ONE constant matrix R (a non-uniform diagonal or a "
-                                      "symmetric positive semi-definite dense matrix); use backend='numpy'")
-        return rho
+    _dev = property(lambda self: self._session.dev, doc="The DeviceFilter this object runs on; None before the first device epoch.")
 
-    def _dense_noise(self):
-        """(lam, U) of a NON-DIAGONAL R = U diag(lam) U^T (the reference's dense branch, psmf.py:150-152) or None.  The device
-        keeps the series and C in the eigenbasis of R, where the step is the non-uniform-diagonal one (psmf_set_noise_rotation);
-        the O(d^3) symmetric eigen-decomposition is done once, here, by LAPACK."""
-        if not hasattr(self, "_dense_noise_cache"):
-            R = self._first_R()
-            out = None
-            if np.ndim(R) == 2 and np.shape(R) == (self._d, self._d) and self._d > 1 and _diag_of(R, self._d) is None:
-                R = np.asarray(R, dtype=float)
-                if not np.allclose(R, R.T, rtol=1e-12, atol=1e-14 * np.max(np.abs(R))):
-                    raise NotImplementedError("the device path needs a symmetric R (a covariance); use backend='numpy'")
-                lam, U = np.linalg.eigh(0.5 * (R + R.T))
-                if lam[0] < -1e-12 * max(lam[-1], 0.0) or not lam[-1] > 0.0:
-                    raise NotImplementedError("the device path needs a positive semi-definite R (a covariance); use backend='numpy'")
-                out = (np.maximum(lam, 0.0), np.ascontiguousarray(U))
-            self._dense_noise_cache = out
-        return self._dense_noise_cache
-
+    # what R and Q are to the device: _noise.py; the structure of R is worked out once per object
     def _first_R(self):
         R = self._R
         return R[1 if 1 in R else min(R.keys())] if isinstance(R, dict) else R
 
-    def _row_noise(self):
-        """diag(R) as a (d,) vector when R is a NON-uniform diagonal (the device then weights every row, per-step engine), else None."""
-        if not hasattr(self, "_row_noise_cache"):
-            dn = self._dense_noise()
-            if dn is not None:          # a non-diagonal R: diagonal in its eigenbasis, where the device works
-                self._row_noise_cache = dn[0]
-            else:
-                dg = _diag_of(self._first_R(), self._d)
-                self._row_noise_cache = None if (dg is None or np.ndim(dg) == 0 or _as_scalar_if_uniform(dg) is not None) else np.asarray(dg, dtype=float)
-        return self._row_noise_cache
+    @cached_property
+    def _R_structure(self):
+        """(dense, rows): (lam, U) of a NON-DIAGONAL R = U diag(lam) U^T or None, and what _row_noise() returns (_noise.structure_of)."""
+        return _noise.structure_of(self._first_R(), self._d)
 
-    def _q_matrix(self, Qk):
-        Q = np.asarray(Qk, dtype=float)
-        return float(Q) * np.eye(self._r) if Q.ndim == 0 else Q.reshape(self._r, self._r)
+    def _row_noise(self):
+        """diag(R) as a (d,) vector when R is a NON-uniform diagonal (or its eigenvalues when it is dense), else None."""
+        return self._R_structure[1]
+
+    def _rho_of(self, Rk):
+        return _noise.rho_of(Rk, self._d, self._first_R(), *self._R_structure)
 
     def _device_rho_q(self, T=None):
-        """(rho, Q, rho_sched, q_sched) for the device: PSMFIter reads R[k], Q[k] of step k (psmf.py:115,123,141).
-        Constant dictionaries give (rho, Q, None, None); R_k = rho_k I and Q_k = q_k Q_1 give per-step scalar schedules
-        (index k, entry 0 unused); a Q[k] that is not a multiple of Q[1] returns q_sched = "host" (the host-stepped mode
-        forms P_bar itself and takes any Q[k])."""
-        R, Q = self._R, self._Q
-        ks = list(range(1, (T or 0) + 1))
-        if not isinstance(R, dict):
-            R = {k: R for k in [0] + ks}
-        if not isinstance(Q, dict):
-            Q = {k: Q for k in [0] + ks}
-        # which R a step reads: the full filter R[k] (psmf.py:123,141); the simplified hooks R[k - 1]
-        # (synthetic_psmf.py:86-87: eta = tr(R[k-1]) / d).  The device applies rho_sched[k] at step k either way.
-        off = 1 if self.hip_mode == "simplified" else 0
-        k1 = (1 - off) if (1 - off) in R else min(R.keys())
-        rho1 = self._rho_of(R[k1])
-        Q1 = self._q_matrix(Q[1 if 1 in Q else min(Q.keys())])
-        rho_s = q_s = None
-        seen_R, seen_Q = {id(R[k1]): rho1}, {}
-        kq1 = 1 if 1 in Q else min(Q.keys())
-        for k in ks:
-            Rk = R.get(k - off, R[k1])    # (a dictionary without the step's key: the constant it was built from)
-            if id(Rk) not in seen_R:
-                seen_R[id(Rk)] = self._rho_of(Rk)
-            rk = seen_R[id(Rk)]
-            if rk != rho1 and rho_s is None:
-                rho_s = np.full(len(ks) + 1, rho1)
-            if rho_s is not None:
-                rho_s[k] = rk
-            Qk = Q.get(k, Q[kq1])
-            if id(Qk) not in seen_Q:
-                Qm = self._q_matrix(Qk)
-                if np.array_equal(Qm, Q1):
-                    seen_Q[id(Qk)] = 1.0
-                else:
-                    nz = np.flatnonzero(Q1)
-                    c = Qm.reshape(-1)[nz[0]] / Q1.reshape(-1)[nz[0]] if nz.size else np.nan
-                    seen_Q[id(Qk)] = float(c) if np.isfinite(c) and np.allclose(Qm, c * Q1, rtol=1e-14, atol=0.0) else "host"
-            qk = seen_Q[id(Qk)]
-            if qk == "host":
-                q_s = "host"
-            elif not isinstance(q_s, str):
-                if qk != 1.0 and q_s is None:
-                    q_s = np.ones(len(ks) + 1)
-                if q_s is not None:
-                    q_s[k] = qk
-        return rho1, Q1, rho_s, q_s
-
-    def _host_stepped(self):
-        """True when f is evaluated on the host, one device step at a time (psmf_step_host): arbitrary callables and what
-        psmf_dyn.hip does not hold (a Fourier basis of more than 4 + 4 terms), or a Q[k] schedule of matrices too large to
-        upload.  The recognised kinds run inside the device time loop on either engine (scaled walk / sinusoid / Fourier at
-        r > 32 or with a non-uniform R: the per-step engine's serial stage)."""
-        return self._nl.device_kind is None or getattr(self, "_force_host_stepped", False)
-
-    def _device_kwargs(self):
-        coef, eta_full, pbar = HIP_MODES[self.hip_mode]
-        kw = dict(robust=self.robust, coef_update=coef, eta_full=eta_full, pbar_predict=pbar, **self._dev_opts)
-        if self._host_stepped():
-            kw.update(dyn_kind=_capi.DYN_HOST, engine="step")
-        else:
-            kw.update(dyn_kind=self._nl.device_kind, dyn_flags=self._nl.device_flags, dyn_terms=self._nl.device_terms)
-        if self._row_noise() is not None or getattr(self, "_q_matrix_sched", False):
-            kw.update(engine="step")
-        if self._row_noise() is not None:
-            kw.update(nonuniform_R=True)
-        if getattr(self, "_masked", False):
-            kw.update(masked=_capi.MASKED_DYNAMICS, engine="step")
-        return kw
+        """(rho, Q, rho_sched, q_sched) for the device: PSMFIter reads R[k], Q[k] of step k (psmf.py:115,123,141), the simplified
+        hooks R[k - 1] (synthetic_psmf.py:86-87); q_sched = "host": a Q[k] that is not a multiple of Q[1] (_noise.rho_q_schedules)."""
+        return _noise.rho_q_schedules(self._R, self._Q, T, self._r, 1 if self.hip_mode == "simplified" else 0, self._rho_of)
 
     # a Q[k] schedule of matrices (not multiples of Q[1]) goes to the device as [T + 1, r, r] up to this size, else host-stepped
     _Q_MATRIX_SCHEDULE_MAX_BYTES = 1 << 31
 
     def _q_matrices(self, T):
-        Q = self._Q
-        k1 = 1 if 1 in Q else min(Q.keys())
-        out = np.empty((T + 1, self._r, self._r))
-        out[0] = self._q_matrix(Q[k1])
-        for k in range(1, T + 1):
-            out[k] = self._q_matrix(Q.get(k, Q[k1]))
-        return out
+        return _noise.q_matrices(self._Q, T, self._r)
 
-    def _ensure_device(self, ring=None):
-        """The device handle: resident series buffers (step) or a series ring of `ring` = (chunk, n_slots) (step_stream).  A
-        handle of the other kind is closed and replaced: a ring cannot be taken off a handle, nor put on after an upload."""
-        if self._dev is not None and self._dev.ring != ring:
-            self._C[0]                  # (fetches a device-resident C before its handle goes)
-            self._dev.close()
-            self._dev, self._series_key, self._sched_key = None, None, (None, None)
-            if hasattr(self, "_qmat_key"):
-                self._qmat_key = None
-        if self._dev is None:
-            self._mask_key = None
-            self._dev = _capi.DeviceFilter(self._d, self._r, **self._device_kwargs())
-            if self._dense_noise() is not None:
-                lam, U = self._dense_noise()
-                self._dev.set_noise_rotation(U, lam)
-            elif self._row_noise() is not None:
-                self._dev.set_row_noise(self._row_noise())
-            if ring is not None:
-                self._dev.series_ring(*ring)
-        return self._dev
+    def _host_stepped(self):
+        """True when f is evaluated on the host, one device step at a time (psmf_step_host): arbitrary callables and what
+        psmf_dyn.hip does not hold (a Fourier basis of more than 4 + 4 terms), or a Q[k] schedule of matrices too large to
+        upload.  The recognised kinds run inside the device time loop on either engine (scaled walk / sinusoid / Fourier at
+        r > 32 or with a non-uniform R: the per-step engine's serial stage).  The recursive classes: also when the in-loop optimiser
+        is not one the device implements."""
+        return (self._nl.device_kind is None or self._session.kind.host_forced
+                or (self._in_loop_optimiser and np.asarray(self.theta0).size > 0 and _device_optimiser(self) is None))
 
-    def _fetch_device(self, name, epoch):
-        if epoch != self._dev_epoch:
-            raise RuntimeError(f"stale device reference to {name} (the device state has moved on)")
-        if name == "C":
-            return self._dev.get_state(want_C=True)["C"]
-        raise KeyError(name)
-
-    def _upload_series(self, y, T):
-        """y[k], k = 1..T, onto the device -- dict {k: (d, 1)} as in the reference, or any array-like indexed the same way
-        (row 0 unused), exactly what the numpy back end reads.  The resident copy is reused only if the CONTENT is
-        unchanged (a checksum of the T observations; object identity says nothing: ids are recycled and containers are
-        refilled in place)."""
-        if isinstance(y, dict):
-            Y = np.concatenate([np.asarray(y[k]).reshape(1, -1) for k in range(1, T + 1)], axis=0)
+    def _device_kwargs(self):
+        coef, eta_full, pbar = HIP_MODES[self.hip_mode]
+        kind = self._session.kind
+        kw = dict(robust=self.robust, coef_update=coef, eta_full=eta_full, pbar_predict=pbar, **self._dev_opts)
+        if self._host_stepped():
+            kw.update(dyn_kind=_capi.DYN_HOST, engine="step")
         else:
-            Y = np.asarray(y)[1:T + 1].reshape(T, -1)
-        if Y.shape != (T, self._d):
-            raise ValueError(f"series: expected {T} observations of length {self._d}, got an array of shape {Y.shape}")
-        Y = np.ascontiguousarray(Y)
-        key = (T, Y.dtype.str, _content_hash(Y))
-        if self._series_key == key:
-            return
-        self._dev.upload_series(Y, t0=0, T_total=T)
-        self._series_key = key
+            kw.update(dyn_kind=self._nl.device_kind, dyn_flags=self._nl.device_flags, dyn_terms=self._nl.device_terms)
+        if self._row_noise() is not None or kind.q_matrices:
+            kw.update(engine="step")
+        if self._row_noise() is not None:
+            kw.update(nonuniform_R=True)
+        if kind.masked:
+            kw.update(masked=_capi.MASKED_DYNAMICS, engine="step")
+        if self._in_loop_optimiser and kw["dyn_kind"] != _capi.DYN_HOST:
+            # the in-loop optimiser's configuration (psmf.py:224-248,299-304): recursive = 1 Adam, 2 SGD.  (Host-stepped: theta and
+            # its optimiser, any schedule, stay on the host.)
+            kw.update(update_every=self._update_every, adam_b1=getattr(self, "adam_b1", 0.9),
+                      adam_b2=getattr(self, "adam_b2", 0.999), **_device_optimiser(self))
+        return kw
 
-    def _select_masked(self, mask, T):
-        """A masked epoch runs on a masked handle (cfg.masked = PSMF_MASKED_DYNAMICS, per-step engine), an unmasked one on the handle it always had:
-        going from one to the other replaces the handle.  What a masked handle cannot run is refused here, by name."""
-        want = mask is not None
-        if want:
+    def _open_device(self, ring):
+        """A new handle of the session's kind (DeviceSession.ensure): resident series buffers, or a series ring of `ring` = (chunk, n_slots)."""
+        dev = _capi.DeviceFilter(self._d, self._r, **self._device_kwargs())
+        dense, rows = self._R_structure
+        if dense is not None:
+            dev.set_noise_rotation(dense[1], dense[0])
+        elif rows is not None:
+            dev.set_row_noise(rows)
+        if ring is not None:
+            dev.series_ring(*ring)
+        return dev
+
+    def _select_device(self, mask, T, ring=None):
+        """The handle this epoch runs on.  A masked epoch runs on a masked handle (cfg.masked = PSMF_MASKED_DYNAMICS, per-step engine), an
+        unmasked one on the handle it always had; a stream on a handle with a series ring; a Q[k] of matrices on yet another kind.  Going
+        from one to the other replaces the handle (DeviceSession.ensure).  What a masked handle cannot run is refused here, by name."""
+        kind = self._session.kind._replace(masked=mask is not None, ring=ring)
+        if mask is not None:
             if self._host_stepped():
                 raise NotImplementedError("mask=: host-stepped callables (a nonlinearity or learning-rate schedule evaluated on the host) "
                                           "would need the masked gradient g_f on the host; use one of the built-in nonlinearities")
             if HIP_MODES[self.hip_mode] != (True, True, True):
                 raise NotImplementedError(f"mask=: the masked filter is the full filter; hip_mode {self.hip_mode!r} is not")
             _rho, _Q, rho_s, q_s = self._device_rho_q(T)
-            if rho_s is not None or q_s is not None or getattr(self, "_q_matrix_sched", False):
+            if rho_s is not None or q_s is not None or kind.q_matrices:
                 raise NotImplementedError("mask=: R / Q schedules that vary with k are not run on masked handles (a constant R = rho I or "
                                           "diagonal R, a constant Q)")
-            if self._dense_noise() is not None:
+            if self._R_structure[0] is not None:
                 raise NotImplementedError("mask=: a dense (non-diagonal) R is run in its eigenbasis, where a mask over the rows means nothing")
             if self._row_noise() is not None and np.asarray(self.theta0).size > 0:
                 raise NotImplementedError("mask=: a non-uniform diagonal R with learned theta (the device then carries sum m_i rho_i in "
                                           "place of the observed count the masked gradient needs); use R = rho I")
-        if want != getattr(self, "_masked", False):
-            if self._dev is not None:
-                self._C[0]                  # (fetches a device-resident C before its handle goes)
-                self._dev.close()
-                self._dev, self._series_key, self._sched_key = None, None, (None, None)
-            self._masked = want
-
-    def _upload_mask(self, mask, T):
-        """mask[k], k = 1..T, onto the device behind the series; as _upload_series, the resident copy is reused only if the content
-        (and the series it belongs to) is unchanged."""
-        if isinstance(mask, dict):
-            M = np.concatenate([np.asarray(mask[k]).reshape(1, -1) for k in range(1, T + 1)], axis=0)
-        else:
-            M = np.asarray(mask)[1:T + 1].reshape(T, -1)
-        if M.shape != (T, self._d):
-            raise ValueError(f"mask: expected {T} rows of length {self._d}, got an array of shape {M.shape}")
-        M = np.ascontiguousarray(M != 0, dtype=np.uint8)
-        key = (self._series_key, _content_hash(M))
-        if getattr(self, "_mask_key", None) == key:
-            return
-        self._dev.upload_mask(M)
-        self._mask_key = key
-
-    def _push_state(self, i, T=None):
-        dev = self._dev
-        C0 = self._C.raw(0)
-        same_C = isinstance(C0, _Lazy) and C0.owner is self and C0.epoch == self._dev_epoch
-        rho, Q, rho_s, q_s = self._device_rho_q(T)
-        theta = np.asarray(self._theta[i - 1], dtype=float).reshape(-1)
-        dev.set_state(None if same_C else np.asarray(C0, dtype=float), self._V[0], self._P[0], Q,
-                      np.asarray(self._mu[0]).reshape(-1), rho=rho, lambda0=self._device_lambda0(),
-                      theta=theta if (theta.size and dev.n_theta) else None)
-        sched = (None if rho_s is None else tuple(rho_s), None if (q_s is None or isinstance(q_s, str)) else tuple(q_s))
-        if sched != getattr(self, "_sched_key", (None, None)):
-            dev.set_schedules(rho_s, None if isinstance(q_s, str) else q_s)
-            self._sched_key = sched
-        if getattr(self, "_q_matrix_sched", False) and not self._host_stepped():
-            Qm = self._q_matrices(T)
-            key = (Qm.shape, _content_hash(Qm))
-            if key != getattr(self, "_qmat_key", None):
-                dev.set_q_matrix_schedule(Qm)
-                self._qmat_key = key
+        if (ring is None and not self._in_loop_optimiser and not self._host_stepped() and not self.robust and not kind.q_matrices
+                and isinstance(self._device_rho_q(T)[3], str)):
+            # Q[k] is not a scalar multiple of Q[1]: uploaded matrix by matrix, P_bar = F P F^T + Q_k formed in the per-step
+            # engine's serial stage (psmf_set_q_matrix_schedule) -- or, beyond _Q_MATRIX_SCHEDULE_MAX_BYTES, by the host, one
+            # device step at a time.  Either way another kind of handle, from here on.
+            fits = (T + 1) * self._r * self._r * 8 <= self._Q_MATRIX_SCHEDULE_MAX_BYTES
+            kind = kind._replace(q_matrices=fits, host_forced=not fits)
+        return self._session.ensure(kind)
 
     def _device_lambda0(self):
         return 0.0
 
     def _pull_state(self, T):
-        s = self._dev.get_state(want_C=False)
-        self._dev_epoch += 1
-        ep = self._dev_epoch
-        self._C = _StateDict({T: _Lazy(self, "C", ep)})
-        self._V = _StateDict({T: s["V"]})
-        self._P = _StateDict({T: s["P"]})
+        s, C = self._session.pull_state()
+        self._C, self._V, self._P = _StateDict({T: C}), _StateDict({T: s["V"]}), _StateDict({T: s["P"]})
         self._mu = _MuHist(self, T, s["mu"].reshape(-1, 1))
         if s["gradsum"].size == np.asarray(self.theta0).size and s["gradsum"].size:
             self._gradsum = s["gradsum"].reshape(np.asarray(self.theta0).shape)
         self._y_pred = _YPred(self, T)
         return s
 
-    def _step_hip(self, y, i, T, mask=None):
+    _in_loop_optimiser, _update_every = False, 1      # the recursive classes: theta takes an optimiser step inside the time loop, every so many steps
+
+    def _device_epoch(self, i, T, y=None, mask=None, stream=None, keep_y_pred=False):
+        """One epoch on the device, for step() of every class and step_stream(): epoch reset, the handle this epoch needs, series and
+        state onto it, the fused time loop (or the host-stepped one), state back, the recognised nonlinearity re-checked.  Returns T.
+        `y`, `mask`: the resident series, run(0, T).  `stream` = (chunks, chunk, n_slots) instead: through a series ring; `T` going in
+        is then only how far the R / Q dictionaries reach, the T coming out what the stream held, and of `_mu` / `_y_pred` only the last
+        mean and what keep_y_pred collects are kept.  The recursive classes start from theta_0 whatever `i` and take theta_T back."""
+        rec = self._in_loop_optimiser
         self.step_reset()
-        self._select_masked(mask, T)
-        if (not self._host_stepped() and not self.robust and not getattr(self, "_q_matrix_sched", False)
-                and isinstance(self._device_rho_q(T)[3], str)):
-            # Q[k] is not a scalar multiple of Q[1]: uploaded matrix by matrix, P_bar = F P F^T + Q_k formed in the per-step
-            # engine's serial stage (psmf_set_q_matrix_schedule) -- or, beyond _Q_MATRIX_SCHEDULE_MAX_BYTES, by the host, one
-            # device step at a time.  Either way another kind of handle.
-            if (T + 1) * self._r * self._r * 8 <= self._Q_MATRIX_SCHEDULE_MAX_BYTES:
-                self._q_matrix_sched = True
-            else:
-                self._force_host_stepped = True
-            if self._dev is not None:
-                self._dev.close()
-                self._dev, self._series_key, self._sched_key = None, None, (None, None)
-        self._ensure_device()
-        self._upload_series(y, T)
-        if mask is not None:
-            self._upload_mask(mask, T)
-        self._push_state(i, T)
+        dev = self._select_device(mask, T, ring=None if stream is None else (int(stream[1]), int(stream[2])))
+        if stream is None:
+            self._session.upload_series(y, T, self._d)
+            if mask is not None:
+                self._session.upload_mask(mask, T, self._d)
+        else:
+            self._session.series_key = None
+        if rec:
+            self._theta, i = {0: self._theta[0]}, 1
+        theta, mu0 = self._theta[i - 1], np.asarray(self._mu[0], dtype=float).reshape(-1, 1)
+        rho, Q, rho_s, q_s = self._device_rho_q(T)
+        Qm = self._q_matrices(T) if (self._session.kind.q_matrices and not self._host_stepped()) else None
+        self._session.push_state(self._C.raw(0), self._V[0], self._P[0], Q, mu0.reshape(-1), rho, self._device_lambda0(),
+                                 np.asarray(theta, dtype=float).reshape(-1), rho_s, q_s, Qm)
         if self._host_stepped():
-            return self._after_device_epoch(self._run_host_stepped(i, T), T)
-        self._dev.zero_gradsum()
-        self._dev.run(0, T)
-        self._after_device_epoch(self._pull_state(T), T)
-        self._verify_recognised_nonlinearity(self._theta[i - 1], T)
+            self._after_device_epoch(self._run_host_stepped(i, T, recursive=rec), T)
+            return T
+        dev.zero_gradsum()
+        if rec and self.optim == "adam":
+            dev.set_adam(self.adam_m.reshape(-1), self.adam_v.reshape(-1))
+        if stream is None:
+            dev.run(0, T)
+        else:
+            kept, T = {}, 0
+            for kb, ke, yp in dev.run_stream(stream[0]):
+                T = ke
+                if keep_y_pred and yp is not None:
+                    kept.update((k + 1, yp[k - kb].reshape(-1, 1)) for k in range(kb, ke))
+        s = self._pull_state(T)
+        if stream is not None:
+            self._mu, self._y_pred = _StateDict({T: s["mu"].reshape(-1, 1)}), kept
+        if rec:
+            self._theta[T] = s["theta"].reshape(np.asarray(self.theta0).shape)
+        self._after_device_epoch(s, T)
+        # theta moves inside the recursive loop: only step 1 has a known theta; a stream keeps no mean history: step 1, from the mean it began with
+        self._verify_recognised_nonlinearity(theta, T, ks=[1] if (rec or stream is not None) else None, mu0=None if stream is None else mu0)
+        return T
 
     def step_stream(self, chunks, chunk, n_slots=2, i=1, keep_y_pred=False):
         """One pass over a stream that need not fit on the device, nor have a known length: `chunks` is an iterable of
@@ -735,51 +558,20 @@ class PSMFIter:
         if self._host_stepped():
             raise NotImplementedError("step_stream: host-stepped callables (a nonlinearity or learning-rate schedule evaluated on "
                                       "the host, one device step at a time) are not streamed; use step()")
-        if self._dense_noise() is not None:
+        if self._R_structure[0] is not None:
             raise NotImplementedError("step_stream: a non-diagonal R keeps the series rotated on the device; use step()")
         t_max = max([k for D in (self._R, self._Q) if isinstance(D, dict) for k in D] + [0])
         _rho, _Q, rho_s, q_s = self._device_rho_q(t_max)
-        if rho_s is not None or q_s is not None or getattr(self, "_q_matrix_sched", False):
+        if rho_s is not None or q_s is not None or self._session.kind.q_matrices:
             raise NotImplementedError("step_stream: R / Q schedules that vary with k are indexed by step and not windowed; use step()")
-        recursive = hasattr(type(self), "_step_hip_recursive")
-        self.step_reset()
-        self._select_masked(None, None)      # (a stream carries no mask through the classes)
-        dev = self._ensure_device(ring=(int(chunk), int(n_slots)))
-        self._series_key = None
-        if recursive:
-            self._theta, i = {0: self._theta[0]}, 1
-        theta0, mu0 = self._theta[i - 1], np.asarray(self._mu[0], dtype=float).reshape(-1, 1)
-        self._push_state(i, t_max)
-        dev.zero_gradsum()
-        if recursive and self.optim == "adam":
-            dev.set_adam(self.adam_m.reshape(-1), self.adam_v.reshape(-1))
-        kept, T = {}, 0
-        for kb, ke, yp in dev.run_stream(chunks):
-            T = ke
-            if keep_y_pred and yp is not None:
-                for k in range(kb, ke):
-                    kept[k + 1] = yp[k - kb].reshape(-1, 1)
-        s = self._pull_state(T)
-        self._mu = _StateDict({T: s["mu"].reshape(-1, 1)})
-        self._y_pred = kept
-        if recursive:
-            self._theta[T] = s["theta"].reshape(np.asarray(self.theta0).shape)
-        self._after_device_epoch(s, T)
-        fn = getattr(self._nl, "recognised_from", None)
-        if fn is not None and T >= 1:       # (the mean history is not kept: the recognised family is re-checked at step 1 only)
-            from .modes import nonlinearity_mismatch
-
-            if nonlinearity_mismatch(fn, self._nl, theta0, mu0, 1):
-                raise RuntimeError(f"the nonlinearity {getattr(fn, '__name__', fn)!r} was recognised as {type(self._nl).__name__} on probe "
-                                   "inputs but differs from it at step 1 of this stream.  Construct with recognise=False.")
-        return T
+        return self._device_epoch(i, t_max, stream=(chunks, chunk, n_slots), keep_y_pred=keep_y_pred)
 
     def _q_for_step(self, k, Q_running):
         """Q entering P_bar of step k: PSMFIter reads Q[k] (psmf.py:115); rPSMFIter its running Q_{k-1} (rpsmf.py:123)."""
         if self.robust:
             return Q_running
         Q = self._Q[k] if isinstance(self._Q, dict) else self._Q
-        return self._q_matrix(Q)
+        return _noise.q_matrix(Q, self._r)
 
     def _run_host_stepped(self, i, T, recursive=False):
         """The time loop with f on the host: per step the host evaluates mu_bar = f(theta, mu, k), F = df/dx and
@@ -787,11 +579,11 @@ class PSMFIter:
         and the theta gradient is accumulated as J_theta^T g_f from the g_f the device returns (psmf.py:167-177)."""
         dev, nl, r = self._dev, self._nl, self._r
         pbar_predict = HIP_MODES[self.hip_mode][2]
-        theta = self._theta[i - 1] if not recursive else self._theta[0]
+        theta = self._theta[i - 1]           # (the recursive classes: i = 1)
         n_th = np.asarray(theta).size
         mu = np.asarray(self._mu[0], dtype=float).reshape(-1, 1)
         P = np.asarray(self._P[0], dtype=float)
-        Qrun = self._q_matrix(self.Q0) if self.robust else None
+        Qrun = _noise.q_matrix(self.Q0, self._r) if self.robust else None
         grad = np.zeros(np.asarray(self.theta0).shape)
         for k in range(1, T + 1):
             mu_bar = np.asarray(nl(theta, mu, k), dtype=float).reshape(-1)
@@ -824,11 +616,11 @@ class PSMFIter:
     def _after_device_epoch(self, s, T):
         pass
 
-    def _verify_recognised_nonlinearity(self, theta, T, ks=None):
+    def _verify_recognised_nonlinearity(self, theta, T, ks=None, mu0=None):
         """A plain callable that the constructor matched to a closed-form family (modes.recognise_nonlinearity) ran inside
         the device loop as that family.  Re-check the match where it matters: at (theta, mu_{k-1}, k) for step indices spread
-        over the epoch just filtered (the mean history is on the device).  A mismatch means the epoch was filtered with the
-        wrong f: raise, naming the way out."""
+        over the epoch just filtered (the mean history is on the device; `mu0`: a stream, which kept none: step 1 only).  A mismatch
+        means the epoch was filtered with the wrong f: raise, naming the way out."""
         fn = getattr(self._nl, "recognised_from", None)
         if fn is None or T < 1:
             return
@@ -837,11 +629,12 @@ class PSMFIter:
         if ks is None:
             ks = sorted({1, 2, T, *np.linspace(1, T, num=min(T, 24), dtype=int).tolist()})
         for k in ks:
-            if nonlinearity_mismatch(fn, self._nl, theta, self._mu[k - 1], k):
+            if nonlinearity_mismatch(fn, self._nl, theta, self._mu[k - 1] if mu0 is None else mu0, k):
                 raise RuntimeError(
                     f"the nonlinearity {getattr(fn, '__name__', fn)!r} was recognised as {type(self._nl).__name__} on probe inputs "
-                    f"but differs from it at step {k} of this run: the device evaluated the wrong function.  Construct with "
-                    "recognise=False (or PSMF_RECOGNISE=0) so that the callable is host-stepped.")
+                    f"but differs from it at step {k} of this " + ("stream.  Construct with recognise=False." if mu0 is not None else
+                    "run: the device evaluated the wrong function.  Construct with "
+                    "recognise=False (or PSMF_RECOGNISE=0) so that the callable is host-stepped."))
 
     def _predict_hip(self, i, T, n_pred):
         if self._host_stepped():
@@ -866,31 +659,14 @@ def _device_optimiser(obj):
     """Keyword arguments of the in-loop optimiser the device implements -- Adam (psmf.py:224-242) or plain SGD (psmf.py:244-248),
     each with a constant or an exponentially decaying learning rate (learning_rate.py:13-27) -- or None: custom learning-rate
     schedules keep theta and its optimiser on the host (host-stepped device loop)."""
-    if obj.optim == "adam":
-        gam, kind = getattr(obj, "adam_gam", ConstantLearningRate(1e-3)), 1
-    elif obj.optim == "sgd":
-        gam, kind = getattr(obj, "sgd_gam", ConstantLearningRate(1e-3)), 2
-    else:
+    if obj.optim not in ("adam", "sgd"):
         return None
+    gam, kind = getattr(obj, obj.optim + "_gam", ConstantLearningRate(1e-3)), 1 if obj.optim == "adam" else 2
     if isinstance(gam, ConstantLearningRate):
         return dict(recursive=kind, adam_lr=gam.lr)
     if hasattr(gam, "lr_start") and hasattr(gam, "lr_end") and hasattr(gam, "steps"):
         return dict(recursive=kind, adam_lr=gam.lr_start, adam_lr_end=gam.lr_end, adam_lr_steps=gam.steps)
     return None
-
-
-def _recursive_kwargs(obj, kw):
-    """Adds the in-loop optimiser's configuration (psmf.py:224-248,299-304) to the device options: recursive = 1 Adam, 2 SGD."""
-    if kw.get("dyn_kind") == _capi.DYN_HOST:
-        return kw               # host-stepped: theta and its optimiser (any schedule) stay on the host
-    kw.update(update_every=getattr(obj, "_update_every", 1),
-              adam_b1=getattr(obj, "adam_b1", 0.9), adam_b2=getattr(obj, "adam_b2", 0.999), **_device_optimiser(obj))
-    return kw
-
-
-def _recursive_host_stepped(obj, base):
-    """Recursive classes: also host-stepped when the in-loop optimiser is not one the device implements."""
-    return base or (np.asarray(obj.theta0).size > 0 and _device_optimiser(obj) is None)
 
 
 class PSMFIterMissing(PSMFIter):
@@ -908,36 +684,27 @@ class PSMFRecursive(PSMFIter):
     """Online variant: theta takes an optimiser step inside the time loop every `update_every`
     observations (pypsmf/psmf/psmf.py:275-331)."""
 
+    # device: Adam and plain SGD run inside the time loop of either engine; custom learning-rate schedules: host-stepped
+    _in_loop_optimiser = True
+
     def run(self, y, T, n_pred, update_every=1, mask=None):
         self._update_every = update_every
         self.optim_init()
-        if mask is None:
-            self.step(y, T)
-        else:
-            self.step(y, T, mask=mask)
+        self.step(y, T, **({} if mask is None else dict(mask=mask)))
         self.predict(T, n_pred)
 
     def step(self, y, T, mask=None):
         if mask is not None and self.backend != "hip":
             raise NotImplementedError('mask=: backend="numpy" executes the reference\'s hooks, which know no missing entries; use backend="hip"')
         if self.backend == "hip":
-            return self._step_hip_recursive(y, T, mask)
+            self._device_epoch(1, T, y, mask)
+            return
         self.step_reset()
         for k in range(1, T + 1):
             self.inner(k, np.asarray(y[k]).reshape(-1, 1))
 
     def inner(self, k, yk):
-        mu_bar = self._predictive_mean(k, k)
-        P_bar = self._predictive_covariance(k, k)
-        self._y_pred[k] = self._predict_measurement(k, mu_bar)
-        eta_k = self._compute_eta_k(k, P_bar)
-        Nk = self._compute_dictionary_innovation(k, eta_k, mu_bar, P_bar)
-        self._update_dictionary_mean(k, yk, Nk, mu_bar)
-        self._update_dictionary_covariance(k, Nk, mu_bar, yk)
-        Skinv = self._compute_inverse_coefficient_innovation(k, mu_bar, P_bar)
-        self._update_coefficient_mean(k, yk, Skinv, mu_bar, P_bar)
-        self._update_coefficient_covariance(k, Skinv, P_bar, yk)
-        self._store_gradient(k, k, yk, eta_k)
+        self._filter_step(k, k, yk)
         if k % self._update_every == 0:
             self.optim_update(k)
             self._reset_gradient()
@@ -955,40 +722,7 @@ class PSMFRecursive(PSMFIter):
         self._store_gradient(k, k, yk, eta_k)
 
     def predict(self, T, n_pred):
-        if self.backend == "hip" and self._dev is not None and isinstance(self._y_pred, _YPred):
-            return self._predict_hip(T + 1, T, n_pred)        # rolls forward with theta_T (psmf.py:324-331)
-        last_theta = self._theta[T]
-        self._mu_pred = {T: self._mu[T]}
-        for k in range(T + 1, T + n_pred + 1):
-            self._mu_pred[k] = self._nl(last_theta, self._mu_pred[k - 1], k)
-            self._y_pred[k] = self._C[T] @ self._mu_pred[k]
-
-    # device: Adam and plain SGD run inside the time loop of either engine; custom learning-rate schedules: host-stepped
-    def _host_stepped(self):
-        return _recursive_host_stepped(self, super()._host_stepped())
-
-    def _device_kwargs(self):
-        return _recursive_kwargs(self, super()._device_kwargs())
-
-    def _step_hip_recursive(self, y, T, mask=None):
-        self.step_reset()
-        self._select_masked(mask, T)
-        self._ensure_device()
-        self._upload_series(y, T)
-        if mask is not None:
-            self._upload_mask(mask, T)
-        self._theta = {0: self._theta[0]}
-        self._push_state(1, T)
-        if self._host_stepped():
-            return self._after_device_epoch(self._run_host_stepped(1, T, recursive=True), T)
-        self._dev.zero_gradsum()
-        if self.optim == "adam":
-            self._dev.set_adam(self.adam_m.reshape(-1), self.adam_v.reshape(-1))
-        self._dev.run(0, T)
-        s = self._pull_state(T)
-        self._theta[T] = s["theta"].reshape(np.asarray(self.theta0).shape)
-        self._after_device_epoch(s, T)
-        self._verify_recognised_nonlinearity(self._theta[0], T, ks=[1])      # theta moves inside the loop: only step 1 has a known theta
+        return PSMFIter.predict(self, T + 1, T, n_pred)        # rolls forward with theta_T (psmf.py:324-331)
 
 
 rPSMF_BASE = PSMFIter          # rebound by rpsmf.py once rPSMFIter exists

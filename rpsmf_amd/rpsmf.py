@@ -11,6 +11,7 @@ from collections import defaultdict
 
 import numpy as np
 
+from . import _noise
 from . import psmf as _psmf
 from .psmf import PSMFIter, _StateDict
 
@@ -103,7 +104,7 @@ class rPSMFIter(PSMFIter):
 
     def _device_rho_q(self, T=None):
         # the epoch starts from R0, Q0 (step_reset) and runs on the omega-scaled Q_{k-1}, R_{k-1}: no schedules
-        return self._rho_of(self.R0), self._q_matrix(self.Q0), None, None
+        return self._rho_of(self.R0), _noise.q_matrix(self.Q0, self._r), None, None
 
     def _device_kwargs(self):
         kw = super()._device_kwargs()
@@ -134,13 +135,7 @@ class rPSMFRecursive(rPSMFIter):
     predict = _psmf.PSMFRecursive.predict
     _reset_gradient = _psmf.PSMFRecursive._reset_gradient
     _carry_theta = _psmf.PSMFRecursive._carry_theta
-    _step_hip_recursive = _psmf.PSMFRecursive._step_hip_recursive
-
-    def _host_stepped(self):
-        return _psmf._recursive_host_stepped(self, rPSMFIter._host_stepped(self))
-
-    def _device_kwargs(self):
-        return _psmf._recursive_kwargs(self, rPSMFIter._device_kwargs(self))
+    _in_loop_optimiser = _psmf.PSMFRecursive._in_loop_optimiser
 
 
 _psmf.rPSMF_BASE = rPSMFIter

@@ -58,15 +58,14 @@ class TrackingMixin:
 
     def _device_norms(self, y, T, n_pred):
         """(train^2, pred^2) from device reductions, or None when the device does not hold what is being compared."""
-        dev = getattr(self, "_dev", None)
-        if getattr(self, "backend", None) != "hip" or dev is None or not dev.store_y_pred or getattr(self, "_host_stepped", lambda: True)():
-            return None
-        from .psmf import _YPred, _content_hash
+        from .psmf import PSMFIter, _YPred
 
-        if not isinstance(self._y_pred, _YPred) or self._y_pred._T != T or self._series_key is None:
+        if not isinstance(self, PSMFIter) or self.backend != "hip":     # (the mixin also serves classes that have no device side)
             return None
-        Yt = np.ascontiguousarray(self._stack(y, 1, T))
-        if (T, Yt.dtype.str, _content_hash(Yt)) != self._series_key:      # the norms are against THIS y: it must be the resident series
+        dev = self._dev
+        if dev is None or not dev.store_y_pred or self._host_stepped() or not isinstance(self._y_pred, _YPred) or self._y_pred._T != T:
+            return None
+        if not self._session.holds_series(np.ascontiguousarray(self._stack(y, 1, T)), T):      # the norms are against THIS y: it must be the resident series
             return None
         if any(dict.__contains__(self._y_pred, k) is False for k in range(T + 1, T + n_pred + 1)):
             return None                                                     # predict() has not been called for this window

@@ -401,6 +401,31 @@ def test_arbitrary_Q_schedule(where, monkeypatch):
     assert relerr(f._C[T], st.C) < 1e-9 and relerr(f._P[T], st.P) < 1e-9
 
 
+def test_Q_matrix_schedule_met_in_a_later_epoch_keeps_C():
+    """Q[k] constant up to T1 and matrices that are no multiples of Q[1] beyond it: epoch 1 over y[1..T1] runs on the handle of a
+    constant Q, epoch 2 over y[1..T2] needs a Q-matrix schedule, so another handle.  The C epoch 1 left on the device has to come
+    to the host before its handle is closed and go to the new one (the state is carried from epoch to epoch as run() does)."""
+    d, r, T1, T2 = 24, 3, 5, 9
+    Y, C0 = _problem(d, r, T2, 41)
+    rng = np.random.default_rng(11)
+    Qs = {k: 0.05 * np.eye(r) for k in range(T1 + 1)}
+    for k in range(T1 + 1, T2 + 1):
+        A = rng.standard_normal((r, r))
+        Qs[k] = 0.05 * np.eye(r) + 0.01 * A @ A.T
+    V0, P0 = 0.1 * np.eye(r), np.eye(r)
+    f = psmf.PSMFIter(np.zeros((0, 1)), C0, V0, np.zeros((r, 1)), P0, Qs, {k: 2.0 for k in range(T2 + 1)}, psmf.RandomWalk(), storage="f64", engine="step")
+    f.optim_init()
+    f.step(ydict(Y[:T1]), 1, T1)
+    first = f._dev
+    f.optim_update(1)
+    f.step(ydict(Y), 2, T2)
+    assert f._dev is not first and f._dev.geometry()["filter_kernel"] == "psmf_sweep_solve"
+    st = O.State(C=C0, V=V0, mu=np.zeros(r), P=P0, Q=Qs[1], rho=2.0, lam=0.0)
+    for T in (T1, T2):
+        st, _, _ = O.run_epoch(st, Y[:T], O.Mode(), O.RandomWalkDyn(), Qs=lambda k: Qs[k])
+    assert relerr(f._C[T2], st.C) < 1e-9 and relerr(f._P[T2], st.P) < 1e-9
+
+
 def test_tracking_error_norms_on_device():
     """TrackingMixin.errors_update (tracking.py:63-76): the three Frobenius norms of Y_pred - Y (full / train / pred windows)
     reduced on the device, against the host computation from `_y_pred`."""

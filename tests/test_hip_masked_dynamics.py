@@ -350,12 +350,12 @@ def test_PSMFIter_run_with_a_mask():
     errs += [(f"theta{i}", D.relerr(f._theta[i].reshape(-1), ref["records"][i - 1][1]), b["theta"]) for i in range(1, D.EPOCHS + 1)]
     report("PSMFIter.run(mask=)", errs)
     # the array form of y and mask (row 0 unused), and the unchanged content: nothing is uploaded again, the same numbers
-    key = (f._series_key, f._mask_key)
+    key = (f._session.series_key, f._session.mask_key)
     f2 = psmf.PSMFIter(pb["theta0"].reshape(-1, 1), pb["C0"], pb["V0"], pb["mu0"].reshape(-1, 1), pb["P0"], pb["Q"], pb["rho"], pb["nl"], storage="f64")
     f2.optim_init()
     Y1, M1 = np.vstack([np.zeros((1, d)), pb["Y"]]), np.vstack([np.ones((1, d)), pb["M"]])
     f2.step(Y1, 1, T, mask=M1)
-    assert (f2._series_key, f2._mask_key) == key
+    assert (f2._session.series_key, f2._session.mask_key) == key
     assert D.relerr(f2._gradsum.reshape(-1), ref["records"][0][0]) < b["gradsum"]
 
 

@@ -49,5 +49,5 @@ def test_q_schedule_classification_and_matrices():
     assert g._device_rho_q(T)[3] == "host"
     Qm = g._q_matrices(T)
     assert Qm.shape == (T + 1, r, r) and all(np.array_equal(Qm[k], Qs[k]) for k in range(1, T + 1)) and np.array_equal(Qm[0], Qs[1])
-    g._q_matrix_sched = True
+    g._session.kind = g._session.kind._replace(q_matrices=True)
     assert g._device_kwargs()["engine"] == "step" and not g._host_stepped()
