@@ -15,6 +15,8 @@ Reference: pypsmf/psmf/psmf.py:85-180,287-304, rpsmf.py:116-184, nonlinearities.
 
 import numpy as np
 
+import netlib
+from netlib import relerr  # noqa: F401  (the device tests and tools take it from here)
 from oracle import psmf_oracle as O
 
 N_CASES = 171            # 3 x len(TARGETS)
@@ -333,17 +335,11 @@ def problem(cs, perturb=None):
     if cs["sched"]:
         rho_k, q_k = 0.5 + rng.random(T + 1), 0.5 + rng.random(T + 1)
         q_k[1] = 1.0
-    f32 = cs["storage"] == "f32"
+    f32 = ("Y", "C0") if cs["storage"] == "f32" else ()
     if f32:
-        Y, C0 = Y.astype(np.float32).astype(np.float64), C0.astype(np.float32).astype(np.float64)
+        Y, C0 = netlib.f32_round(Y), netlib.f32_round(C0)
     if perturb is not None:
-        prng = np.random.default_rng(perturb[0])
-        eps = perturb[1]
-        Y = Y * (1.0 + eps * prng.uniform(-1, 1, Y.shape))
-        C0 = C0 * (1.0 + eps * prng.uniform(-1, 1, C0.shape))
-        theta = theta * (1.0 + eps * prng.uniform(-1, 1, theta.shape))
-        if f32:
-            Y, C0 = Y.astype(np.float32).astype(np.float64), C0.astype(np.float32).astype(np.float64)
+        Y, C0, theta = netlib.perturbed(dict(Y=Y, C0=C0, theta=theta), *perturb, f32=f32).values()
     return dict(nl=nl, Y=Y, C0=C0, V0=cs["v0"] * np.eye(r), P0=np.eye(r), Q=Q, mu0=mu0, theta=theta, rho_k=rho_k, q_k=q_k,
                 rho=1.0, lam=1.8)
 
@@ -399,12 +395,13 @@ def reference(cs, pb):
     return out, rollout
 
 
-def relerr(a, b):
-    """conftest.relerr: max |a - b| / max |b|"""
-    a, b = np.asarray(a, dtype=float), np.asarray(b, dtype=float)
-    if a.size == 0:
-        return 0.0
-    return float(np.max(np.abs(a - b))) / max(float(np.max(np.abs(b))), 1e-300)
+STATE_KEYS = ("C", "V", "mu", "P", "y_pred")
+
+
+def grad_response(ref0, ref1):
+    """netlib.response on the gradient sums, over the parts where the oracle's is not zero (not just restarted by the optimiser)"""
+    live = [(p0, p1) for p0, p1 in zip(ref0, ref1) if p0["gradsum"].size and np.max(np.abs(p0["gradsum"])) > 0]
+    return netlib.response([p0 for p0, _ in live], [p1 for _, p1 in live], ("gradsum",))
 
 
 def sensitivity(cs):
@@ -414,33 +411,17 @@ def sensitivity(cs):
     ref0, roll0 = reference(cs, problem(cs))
     ref1, roll1 = reference(cs, problem(cs, perturb=(cs["seed"] ^ 0x5EED, eps)))
     for part in ref0:
-        for k in ("C", "V", "mu", "P", "y_pred", "gradsum"):
-            if not np.all(np.isfinite(part[k])):
-                raise FloatingPointError(f"case {cs['i']}: non-finite {k} in the oracle")
-    state = max([relerr(p1[k], p0[k]) for p0, p1 in zip(ref0, ref1) for k in ("C", "V", "mu", "P", "y_pred") if p0[k].size] + [0.0])
-    grad = max([relerr(p1["gradsum"], p0["gradsum"]) for p0, p1 in zip(ref0, ref1) if p0["gradsum"].size and np.max(np.abs(p0["gradsum"])) > 0] + [0.0])
-    return state, grad
+        netlib.require_finite(part, STATE_KEYS + ("gradsum",), f"case {cs['i']}")
+    return netlib.response(ref0, ref1, STATE_KEYS), grad_response(ref0, ref1)
 
 
 def admissible(cs):
     state, grad = sensitivity(cs)
-    return state <= bar(cs) / 16 and grad <= gradsum_bar(cs) / 16, state, grad
+    return state <= bar(cs) / 16 and grad <= gradsum_bar(cs) / 16, f"sensitivity {state:.2e} (bar {bar(cs):.0e}), gradsum {grad:.2e}"
 
 
-def resolve(i):
-    """Case i as the device runs it: the draw itself when the oracle's own sensitivity sits 16 x inside the bars, else the same
-    case over half the horizon (at most twice, not below B + 1), else the next salt.  Returns ((salt, times shortened), log)."""
-    log = []
-    for salt in range(8):
-        cs = case(i, salt)
-        while cs is not None:
-            ok, state, grad = admissible(cs)
-            if ok:
-                return (salt, cs["shortened"]), log
-            log.append(f"case {i} salt {salt} T={cs['T']} {cs['storage']} {cs['dyn']} {cs['hooks']}: sensitivity {state:.2e} "
-                       f"(bar {bar(cs):.0e}), gradsum {grad:.2e}")
-            cs = shorten(cs)
-    raise AssertionError(f"case {i}: no admissible configuration in 8 salts: {log}")
+def describe(cs):
+    return f"T={cs['T']} {cs['storage']} {cs['dyn']} {cs['hooks']}"
 
 
 # What `resolve` answers for the cases it does not leave alone, {i: (salt, times shortened)}: recorded here so that the device
@@ -448,9 +429,10 @@ def resolve(i):
 RESOLUTION = {16: (0, 1), 31: (0, 1), 37: (1, 0), 50: (1, 0), 97: (1, 0), 106: (1, 0), 130: (0, 1), 133: (0, 2), 151: (1, 0), 170: (1, 0)}
 
 
+def resolve(i):
+    """netlib.resolve on this net (halving not below B + 1): ((salt, times shortened), log)"""
+    return netlib.resolve(i, case, shorten, admissible, describe)
+
+
 def device_case(i):
-    salt, n = RESOLUTION.get(i, (0, 0))
-    cs = case(i, salt)
-    for _ in range(n):
-        cs = shorten(cs)
-    return cs
+    return netlib.device_case(i, case, shorten, RESOLUTION.get(i, (0, 0)))

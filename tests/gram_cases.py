@@ -23,6 +23,8 @@ Reference: ExperimentImpute/PSMF.py:40-95, rPSMF.py:40-148, MLESMF.py:40-92, TMF
 
 import numpy as np
 
+import netlib
+from netlib import f32_round, relerr, spd  # noqa: F401  (the device tests take relerr from here)
 from oracle import psmf_oracle as O
 from oracle.impute_oracle import impute_filter, mle_smf_filter, tmf_filter
 
@@ -252,15 +254,6 @@ SHARD_BAR = 1e-11          # sharded against unsharded, float64 storage
 
 
 # ---- the problem of a case
-def _spd(rng, r, base):
-    B = rng.standard_normal((r, r))
-    return base * (np.eye(r) + 0.3 * (B @ B.T) / r)
-
-
-def _f32(a):
-    return a.astype(np.float32).astype(np.float64)
-
-
 def mask_of(cs, rng):
     """The observation mask (d, T): 60 % observed; row 3 never; column 0: one whole wave's slab unobserved; column 1: no
     observation (`empty_col`); column 2: the rows of the last slab alone; column 3: every row; column 4, where a wave takes two
@@ -298,7 +291,7 @@ def problem(cs, perturb=None):
         Mmiss = ((1 - M) * (rng.random((d, T)) > 0.1)).astype(float)
         Mmiss[3, 0] = 1.0
         C0, X0 = rng.random((d, r)), rng.random((r, T))
-        pb = dict(M=M, Mmiss=Mmiss, X0=X0, V0=_spd(rng, r, 2.0), P0=_spd(rng, r, 1.0), Q=_spd(rng, r, 0.05) if cs["general_Q"] else 0.1 * np.eye(r))
+        pb = dict(M=M, Mmiss=Mmiss, X0=X0, V0=spd(rng, r, 2.0), P0=spd(rng, r, 1.0), Q=spd(rng, r, 0.05) if cs["general_Q"] else 0.1 * np.eye(r))
     else:
         Ct = rng.standard_normal((d, r))
         x = rng.standard_normal(r)
@@ -308,18 +301,14 @@ def problem(cs, perturb=None):
             Y[t] = Ct @ x + 0.3 * (rng.standard_t(3.0, d) if cs["robust"] else rng.standard_normal(d))
         C0 = 0.1 * rng.standard_normal((d, r))
         rho_rows = 10.0 ** (3.0 * rng.random(d) - 1.5) if cs["wide_rho"] else 0.3 + 2.0 * rng.random(d)
-        pb = dict(V0=_spd(rng, r, 0.02 if f32 else 0.1), P0=_spd(rng, r, 1.0), Q=_spd(rng, r, 0.05) if cs["general_Q"] else 0.1 * np.eye(r),
+        pb = dict(V0=spd(rng, r, 0.02 if f32 else 0.1), P0=spd(rng, r, 1.0), Q=spd(rng, r, 0.05) if cs["general_Q"] else 0.1 * np.eye(r),
                   mu0=0.2 * rng.standard_normal(r), rho_rows=rho_rows)
         if cs["rotated"]:
             pb["U"] = np.linalg.qr(rng.standard_normal((d, d)))[0]
     if f32:
-        Y, C0 = _f32(Y), _f32(C0)
+        Y, C0 = f32_round(Y), f32_round(C0)
     if perturb is not None:
-        prng = np.random.default_rng(perturb[0])
-        Y = Y * (1.0 + perturb[1] * prng.uniform(-1, 1, Y.shape))
-        C0 = C0 * (1.0 + perturb[1] * prng.uniform(-1, 1, C0.shape))
-        if f32:
-            Y, C0 = _f32(Y), _f32(C0)
+        Y, C0 = netlib.perturbed(dict(Y=Y, C0=C0), *perturb, f32=("Y", "C0") if f32 else ()).values()
     pb.update(Y=Y, C0=C0)
     return pb
 
@@ -358,14 +347,6 @@ def reference(cs, pb):
     return out
 
 
-def relerr(a, b):
-    """conftest.relerr: max |a - b| / max |b|"""
-    a, b = np.asarray(a, dtype=float), np.asarray(b, dtype=float)
-    if a.size == 0:
-        return 0.0
-    return float(np.max(np.abs(a - b))) / max(float(np.max(np.abs(b))), 1e-300)
-
-
 WEIGHTED_KEYS = ("C", "V", "mu", "P", "y_pred")
 MASKED_KEYS = ("C", "X", "V", "P", "Yrec", "YrecL", "YrecH", "Epred", "Efull")
 
@@ -379,39 +360,23 @@ def sensitivity(cs):
         ref1 = reference(cs, problem(cs, perturb=(cs["seed"] ^ 0x5EED, eps)))
     if cs["masked"]:
         keys = [k for k in MASKED_KEYS if k in ref0]
-        for k in keys:
-            if not np.all(np.isfinite(ref0[k])):
-                raise FloatingPointError(f"case {cs['i']}: non-finite {k} in the oracle")
-        return max(relerr(ref1[k], ref0[k]) for k in keys), abs(ref1["coverage"] - ref0["coverage"]) if "coverage" in ref0 else 0.0
+        netlib.require_finite(ref0, keys, f"case {cs['i']}")
+        return netlib.response(ref0, ref1, keys), abs(ref1["coverage"] - ref0["coverage"]) if "coverage" in ref0 else 0.0
     for part in ref0:
-        for k in WEIGHTED_KEYS:
-            if not np.all(np.isfinite(part[k])):
-                raise FloatingPointError(f"case {cs['i']}: non-finite {k} in the oracle")
-    return max(relerr(p1[k], p0[k]) for p0, p1 in zip(ref0, ref1) for k in WEIGHTED_KEYS), 0.0
+        netlib.require_finite(part, WEIGHTED_KEYS, f"case {cs['i']}")
+    return netlib.response(ref0, ref1, WEIGHTED_KEYS), 0.0
 
 
 def admissible(cs):
     try:
         state, cov = sensitivity(cs)
     except (np.linalg.LinAlgError, FloatingPointError, ZeroDivisionError) as e:
-        return False, float("inf"), f"{type(e).__name__}: {e}"
-    return state <= bar(cs) / 16 and cov <= coverage_bar(cs) / 16, state, cov
+        return False, f"{type(e).__name__}: {e}"
+    return state <= bar(cs) / 16 and cov <= coverage_bar(cs) / 16, f"sensitivity {state:.2e} (bar {bar(cs):.0e}), coverage {cov}"
 
 
-def resolve(i):
-    """Case i as the device runs it: the draw itself when the oracle's own sensitivity sits 16 x inside the bars, else the same
-    case over half the horizon and a pass less (at most twice), else the next salt.  Returns ((salt, times shortened), log)."""
-    log = []
-    for salt in range(8):
-        cs = case(i, salt)
-        while cs is not None:
-            ok, state, cov = admissible(cs)
-            if ok:
-                return (salt, cs["shortened"]), log
-            log.append(f"case {i} salt {salt} {cs['method']} T={cs['T']} passes={cs['passes']} d={cs['d']} r={cs['r']} {cs['storage']}: "
-                       f"sensitivity {state:.2e} (bar {bar(cs):.0e}), coverage {cov}")
-            cs = shorten(cs)
-    raise AssertionError(f"case {i}: no admissible configuration in 8 salts: {log}")
+def describe(cs):
+    return f"{cs['method']} T={cs['T']} passes={cs['passes']} d={cs['d']} r={cs['r']} {cs['storage']}"
 
 
 # What `resolve` answers for the cases it does not leave alone, {i: (salt, times shortened)}: recorded here so that the device
@@ -419,9 +384,10 @@ def resolve(i):
 RESOLUTION = {45: (1, 0), 50: (0, 1)}
 
 
+def resolve(i):
+    """netlib.resolve on this net (halving the horizon, with a pass less): ((salt, times shortened), log)"""
+    return netlib.resolve(i, case, shorten, admissible, describe)
+
+
 def device_case(i):
-    salt, n = RESOLUTION.get(i, (0, 0))
-    cs = case(i, salt)
-    for _ in range(n):
-        cs = shorten(cs)
-    return cs
+    return netlib.device_case(i, case, shorten, RESOLUTION.get(i, (0, 0)))

@@ -19,6 +19,8 @@ oracle/impute_oracle.py)."""
 
 import numpy as np
 
+import netlib
+from netlib import relerr  # noqa: F401  (the device test takes it from here)
 from oracle.impute_oracle import impute_filter, mle_smf_filter, tmf_filter
 
 METHODS = ("psmf", "rpsmf", "mle_smf", "tmf")
@@ -191,11 +193,6 @@ ERR_BAR, INSIDE_BAR = 1e-8, 1e-12          # Epred / Efull (relative), coverage 
 
 
 # ---- the problem of a case
-def _spd(rng, r, base):
-    B = rng.standard_normal((r, r))
-    return base * (np.eye(r) + 0.3 * (B @ B.T) / r)
-
-
 def empty_column(cs):
     """Does every replica of the case have a column with no observation?  d >= 12, n >= 4, not MLE-SMF (its reference divides by
     eta = 0 there, MLESMF.py:79), and r >= 3: in such a column eta = 0, N = s, and V - w w^T / s loses the direction x_p for good, so
@@ -242,11 +239,10 @@ def problem(cs, perturb=None):
     masks = [_mask(rng, cs) for _ in range(B)]
     C0 = rng.random((B, d, r))
     X0 = rng.random((B, r, n))
-    Q = _spd(rng, r, 0.05) if cs["general_Q"] else 0.1 * np.eye(r)
-    V, P = (_spd(rng, r, 2.0), _spd(rng, r, 1.0)) if cs["dense"] else (2.0 * np.eye(r), np.eye(r))
+    Q = netlib.spd(rng, r, 0.05) if cs["general_Q"] else 0.1 * np.eye(r)
+    V, P = (netlib.spd(rng, r, 2.0), netlib.spd(rng, r, 1.0)) if cs["dense"] else (2.0 * np.eye(r), np.eye(r))
     if perturb is not None:
-        prng = np.random.default_rng(perturb[0])
-        Yorig, C0, X0 = (a * (1.0 + perturb[1] * prng.uniform(-1, 1, a.shape)) for a in (Yorig, C0, X0))
+        Yorig, C0, X0 = netlib.perturbed(dict(Yorig=Yorig, C0=C0, X0=X0), *perturb).values()
     return dict(Yorig=Yorig, M=np.stack([m for m, _ in masks]), Mmiss=np.stack([mm for _, mm in masks]), C0=C0, X0=X0, V=V, P=P, Q=Q,
                 R=noise(cs))
 
@@ -278,12 +274,6 @@ def oracle(cs, pb):
     return out
 
 
-def relerr(a, b):
-    """conftest.relerr: max |a - b| / max |b|"""
-    a, b = np.asarray(a, dtype=float), np.asarray(b, dtype=float)
-    return float(np.max(np.abs(a - b))) / max(float(np.max(np.abs(b))), 1e-300)
-
-
 def sensitivity(cs):
     """(relerr between the oracle on the case's inputs and on inputs moved by a relative 2^-50: the worst over C, X, Yrec, YrecL,
     YrecH of every replica; the same for Epred, Efull; the smallest distance of a held-out entry from a band edge, in units of
@@ -294,11 +284,9 @@ def sensitivity(cs):
     state = errs = 0.0
     margin = np.inf
     for b, (r0, r1) in enumerate(zip(ref0, ref1)):
-        for k, a in r0.items():
-            if a is not None and not np.all(np.isfinite(a)):
-                raise FloatingPointError(f"case {cs['i']}: non-finite {k} in the oracle (replica {b})")
-        state = max([state] + [relerr(r1[k], r0[k]) for k in OUTPUTS if k in r0])
-        errs = max(errs, relerr(r1["Epred"], r0["Epred"]), relerr(r1["Efull"], r0["Efull"]))
+        netlib.require_finite(r0, list(r0), f"case {cs['i']}, replica {b}")
+        state = max(state, netlib.response(r0, r1, [k for k in OUTPUTS if k in r0]))
+        errs = max(errs, netlib.response(r0, r1, ("Epred", "Efull")))
         if r0["inside"] is not None:
             sel = pb["Mmiss"][b] == 1
             y = pb["Yorig"][sel]
@@ -319,20 +307,8 @@ def admissible(cs):
     return ok, f"sensitivity {state:.2e} (bar {bar(cs):.0e}), errors {errs:.2e}, band margin {margin:.2e}"
 
 
-def resolve(i):
-    """Case i as the device runs it: the draw itself when the oracle alone admits it (finite; its own response to a last-bit
-    change of the inputs 16 x inside the bars; no held-out entry within 1e-6 of a band edge), else the same case over half the
-    series (at most twice, not below n = 2), else the next salt.  Returns ((salt, times shortened), log)."""
-    log = []
-    for salt in range(8):
-        cs = case(i, salt)
-        while cs is not None:
-            ok, what = admissible(cs)
-            if ok:
-                return (salt, cs["shortened"]), log
-            log.append(f"case {i} salt {salt} {cs['instance']} {cs['method']} d={cs['d']} r={cs['r']} n={cs['n']}: {what}")
-            cs = shorten(cs)
-    raise AssertionError(f"case {i}: no admissible configuration in 8 salts: {log}")
+def describe(cs):
+    return f"{cs['instance']} {cs['method']} d={cs['d']} r={cs['r']} n={cs['n']}"
 
 
 # What `resolve` answers for the cases it does not leave alone, {i: (salt, times shortened)}: recorded here so that the device
@@ -340,9 +316,11 @@ def resolve(i):
 RESOLUTION = {42: (1, 1)}
 
 
+def resolve(i):
+    """netlib.resolve on this net (halving the series, not below n = 2; admitted: finite, the response to a last-bit change 16 x
+    inside the bars, no held-out entry within 1e-6 of a band edge): ((salt, times shortened), log)"""
+    return netlib.resolve(i, case, shorten, admissible, describe)
+
+
 def device_case(i):
-    salt, n = RESOLUTION.get(i, (0, 0))
-    cs = case(i, salt)
-    for _ in range(n):
-        cs = shorten(cs)
-    return cs
+    return netlib.device_case(i, case, shorten, RESOLUTION.get(i, (0, 0)))

@@ -32,6 +32,7 @@ from functools import lru_cache
 
 import numpy as np
 
+from netlib import f32_round, relerr  # noqa: F401  (the tests take relerr from here)
 from oracle import psmf_oracle as O
 from rpsmf_amd import nonlinearities as NL
 
@@ -85,10 +86,6 @@ class ClosedFormDyn(O.Dynamics):
         return np.asarray(self.nl.jac_theta(theta, x, t), dtype=float)
 
 
-def _f32(a):
-    return a.astype(np.float32).astype(np.float64)
-
-
 def theta_for(nl, rng, r):
     """theta in the regime the experiments use (beijing_psmf.py:117: 0.1 * rand), matrices near a contraction"""
     th = 0.1 * rng.random(nl.n_params)
@@ -119,7 +116,7 @@ def problem(cs, perturb=None):
     nl = cs["make"](r)
     theta0 = theta_for(nl, rng, r)
     if cs["storage"] == "f32":
-        Y, C0 = _f32(Y), _f32(C0)
+        Y, C0 = f32_round(Y), f32_round(C0)
     if perturb is not None:
         prng = np.random.default_rng(perturb[0])
         C0 = C0 * (1.0 + perturb[1] * prng.uniform(-1, 1, C0.shape))
@@ -216,14 +213,6 @@ def _cached(i):
 def reference(cs):
     """(problem, model result) of a case, computed once and shared by the tests that need it: do not modify either"""
     return _cached(CASES.index(cs))
-
-
-def relerr(a, b):
-    """conftest.relerr: max |a - b| / max |b|"""
-    a, b = np.asarray(a, dtype=float), np.asarray(b, dtype=float)
-    if a.size == 0:
-        return 0.0
-    return float(np.max(np.abs(a - b))) / max(float(np.max(np.abs(b))), 1e-300)
 
 
 STATE_KEYS = ("C", "V", "P", "X", "yp")

@@ -16,6 +16,7 @@ from functools import lru_cache
 
 import numpy as np
 
+from netlib import f32_round, relerr  # noqa: F401  (the tests take relerr from here)
 from oracle.impute_oracle import impute_filter, mle_smf_filter
 
 N_WG, SLAB, WGRAM_NW = 256, 16, 8           # kMGramWG and wgram_inst (psmf_capi.hip), mgram_body's slab (psmf_masked.hip)
@@ -48,10 +49,6 @@ def trips(d_local):
     return -(-((d_local + SLAB - 1) // SLAB) // (N_WG * WGRAM_NW))
 
 
-def _f32(a):
-    return a.astype(np.float32).astype(np.float64)
-
-
 def problem(cs, perturb=None):
     """dict(Yorig, M, Mmiss, C0, X0, rho, V, Q, P) of a case, (d, n) as the reference takes them.  `perturb` = (seed, eps): C0 and
     X0 times (1 + eps u), u uniform in [-1, 1] (the oracle's own arithmetic is float64 whatever the device stores)."""
@@ -69,7 +66,7 @@ def problem(cs, perturb=None):
     C0, X0 = rng.random((d, r)), rng.random((r, n))
     rho = 10.0 * 100.0 ** (rng.random(d) - 0.5)
     if cs["storage"] == "f32":
-        Yorig, C0 = _f32(Yorig), _f32(C0)
+        Yorig, C0 = f32_round(Yorig), f32_round(C0)
     if perturb is not None:
         prng = np.random.default_rng(perturb[0])
         C0 = C0 * (1.0 + perturb[1] * prng.uniform(-1, 1, C0.shape))
@@ -100,12 +97,6 @@ def _cached(i):
 def reference(cs):
     """(problem, oracle result) of a case, computed once and shared by the tests that need it: do not modify either"""
     return _cached(CASES.index(cs))
-
-
-def relerr(a, b):
-    """conftest.relerr: max |a - b| / max |b|"""
-    a, b = np.asarray(a, dtype=float), np.asarray(b, dtype=float)
-    return float(np.max(np.abs(a - b))) / max(float(np.max(np.abs(b))), 1e-300)
 
 
 COMPARED = ("C", "X", "Yrec", "YrecL", "YrecH")

@@ -37,6 +37,7 @@ from functools import lru_cache
 
 import numpy as np
 
+import netlib
 import ssm_cases as SC
 import ssm_robust_cases as RC
 
@@ -182,9 +183,7 @@ def problem(cs, perturb=None):
         Vb, Pb = (_spd(rng, r, 0.3, 0.4), _spd(rng, p, 0.5, 0.5)) if cs["own_VP"] else (V, P0)
         mask = _mask(rng, cs)
         if perturb is not None:
-            prng = np.random.default_rng([SEED, i, sub, 100 + b])
-            C0 = C0 * (1.0 + perturb * prng.uniform(-1, 1, C0.shape))
-            x0 = x0 * (1.0 + perturb * prng.uniform(-1, 1, x0.shape))
+            C0, x0 = netlib.perturbed(dict(C0=C0, x0=x0), [SEED, i, sub, 100 + b], perturb).values()
         pbs.append(dict(Y=Y, C0=C0, x0=x0, V=Vb, P0=Pb, A=A, Q=Q, H=H, rho=cs["rho"], mask=mask))
     return pbs
 
@@ -235,15 +234,14 @@ def admission(cs):
 
 
 def resolve(i):
-    """(sub-seed of the first admitted draw of case i, log of the draws it replaced)"""
-    log = []
-    for sub in range(8):
-        cs = case(i, sub)
-        ok, fig = admission(cs)
-        if ok:
-            return sub, log
-        log.append(f"case {i} sub-seed {sub} {describe(cs)}: {fig}")
-    raise AssertionError(f"case {i}: no admitted draw in 8 sub-seeds: {log}")
+    """(sub-seed of the first admitted draw of case i, log of the draws it replaced): netlib.resolve without halving, the salt
+    being the sub-seed"""
+    def admissible(cs):
+        ok, figures = admission(cs)
+        return ok, str(figures)
+
+    (sub, _), log = netlib.resolve(i, case, None, admissible, describe)
+    return sub, log
 
 
 # What `resolve` answers for the cases whose first draw it does not admit, {i: sub-seed}: recorded so that the device test need not
@@ -254,7 +252,7 @@ N_REPLACED = sum(REPLACED.values())       # draws replaced at admission
 
 def device_case(i):
     """case i as the net runs it"""
-    return case(i, REPLACED.get(i, 0))
+    return netlib.device_case(i, case, None, (REPLACED.get(i, 0), 0))
 
 
 @lru_cache(maxsize=None)

@@ -34,7 +34,8 @@ Reference: pypsmf/psmf/psmf.py:85-180,287-304, rpsmf.py:116-184; ExperimentImput
 import numpy as np
 
 import blocked_cases as BC
-from blocked_cases import HOOKS, gradsum_bar, mode_of, relerr, theta_for  # noqa: F401  (the device test takes them from here)
+import netlib
+from blocked_cases import HOOKS, gradsum_bar, mode_of, passes_of, relerr, theta_for  # noqa: F401  (the device test takes them from here)
 from oracle import psmf_oracle as O
 from oracle.impute_oracle import impute_filter
 
@@ -413,20 +414,12 @@ def _masked_problem(cs, perturb):
     Mmiss = ((1 - M) * (rng.random((d, T)) > 0.1)).astype(float)
     Mmiss[3, 0] = 1.0          # (held out whatever the draw: the metrics divide by the count)
     C0, X0 = rng.random((d, r)), rng.random((r, T))
-    f32 = cs["storage"] == "f32"
+    f32 = ("Yorig", "C0") if cs["storage"] == "f32" else ()
     if f32:
-        Yorig, C0 = Yorig.astype(np.float32).astype(np.float64), C0.astype(np.float32).astype(np.float64)
+        Yorig, C0 = netlib.f32_round(Yorig), netlib.f32_round(C0)
     if perturb is not None:
-        prng = np.random.default_rng(perturb[0])
-        Yorig = Yorig * (1.0 + perturb[1] * prng.uniform(-1, 1, Yorig.shape))
-        C0 = C0 * (1.0 + perturb[1] * prng.uniform(-1, 1, C0.shape))
-        if f32:
-            Yorig, C0 = Yorig.astype(np.float32).astype(np.float64), C0.astype(np.float32).astype(np.float64)
+        Yorig, C0 = netlib.perturbed(dict(Yorig=Yorig, C0=C0), *perturb, f32=f32).values()
     return dict(Yorig=Yorig, M=M, Mmiss=Mmiss, C0=C0, X0=X0, V0=2 * np.eye(r), Q=0.1 * np.eye(r), P0=np.eye(r), rho=10.0, lam=1.8, sig=2.0)
-
-
-def passes_of(cs):
-    return 2 if cs["second_pass"] else 1
 
 
 def reference(cs, pb):
@@ -465,17 +458,11 @@ def sensitivity(cs):
     ref0 = reference(cs, problem(cs))
     ref1 = reference(cs, problem(cs, perturb=(cs["seed"] ^ 0x5EED, eps)))
     if cs["masked"]:
-        for k in MASKED_KEYS:
-            if not np.all(np.isfinite(ref0[k])):
-                raise FloatingPointError(f"case {cs['i']}: non-finite {k} in the oracle")
-        return max(relerr(ref1[k], ref0[k]) for k in MASKED_KEYS), abs(ref1["coverage"] - ref0["coverage"])
+        netlib.require_finite(ref0, MASKED_KEYS, f"case {cs['i']}")
+        return netlib.response(ref0, ref1, MASKED_KEYS), abs(ref1["coverage"] - ref0["coverage"])
     for part in ref0:
-        for k in STATE_KEYS + ("gradsum",):
-            if not np.all(np.isfinite(part[k])):
-                raise FloatingPointError(f"case {cs['i']}: non-finite {k} in the oracle")
-    state = max([relerr(p1[k], p0[k]) for p0, p1 in zip(ref0, ref1) for k in STATE_KEYS if p0[k].size] + [0.0])
-    grad = max([relerr(p1["gradsum"], p0["gradsum"]) for p0, p1 in zip(ref0, ref1) if p0["gradsum"].size and np.max(np.abs(p0["gradsum"])) > 0] + [0.0])
-    return state, grad
+        netlib.require_finite(part, STATE_KEYS + ("gradsum",), f"case {cs['i']}")
+    return netlib.response(ref0, ref1, STATE_KEYS), BC.grad_response(ref0, ref1)
 
 
 def coverage_bar(cs):
@@ -485,25 +472,12 @@ def coverage_bar(cs):
 
 def admissible(cs):
     state, second = sensitivity(cs)
-    if cs["masked"]:
-        return state <= bar(cs) / 16 and second <= coverage_bar(cs) / 16, state, second
-    return state <= bar(cs) / 16 and second <= gradsum_bar(cs) / 16, state, second
+    what, second_bar = ("coverage", coverage_bar(cs)) if cs["masked"] else ("gradsum", gradsum_bar(cs))
+    return state <= bar(cs) / 16 and second <= second_bar / 16, f"sensitivity {state:.2e} (bar {bar(cs):.0e}), {what} {second:.2e}"
 
 
-def resolve(i):
-    """Case i as the device runs it: the draw itself when the oracle's own sensitivity sits 16 x inside the bars, else the same
-    case over half the horizon (at most twice), else the next salt.  Returns ((salt, times shortened), log)."""
-    log = []
-    for salt in range(8):
-        cs = case(i, salt)
-        while cs is not None:
-            ok, state, second = admissible(cs)
-            if ok:
-                return (salt, cs["shortened"]), log
-            log.append(f"case {i} salt {salt} T={cs['T']} d={cs['d']} r={cs['r']} {cs['storage']} {cs['dyn']} {cs['hooks']}: sensitivity {state:.2e} "
-                       f"(bar {bar(cs):.0e}), {'coverage' if cs['masked'] else 'gradsum'} {second:.2e}")
-            cs = shorten(cs)
-    raise AssertionError(f"case {i}: no admissible configuration in 8 salts: {log}")
+def describe(cs):
+    return f"T={cs['T']} d={cs['d']} r={cs['r']} {cs['storage']} {cs['dyn']} {cs['hooks']}"
 
 
 # What `resolve` answers for the cases it does not leave alone, {i: (salt, times shortened)}: recorded here so that the device
@@ -511,9 +485,10 @@ def resolve(i):
 RESOLUTION = {117: (0, 1), 130: (0, 1), 131: (0, 1)}
 
 
+def resolve(i):
+    """netlib.resolve on this net (halving not below 2 steps; masked: 3): ((salt, times shortened), log)"""
+    return netlib.resolve(i, case, shorten, admissible, describe)
+
+
 def device_case(i):
-    salt, n = RESOLUTION.get(i, (0, 0))
-    cs = case(i, salt)
-    for _ in range(n):
-        cs = shorten(cs)
-    return cs
+    return netlib.device_case(i, case, shorten, RESOLUTION.get(i, (0, 0)))

@@ -8,15 +8,12 @@ The device route itself: tests/test_hip_dense_R.py."""
 import numpy as np
 import pytest
 
+import netlib
 from conftest import load_golden, relerr
 from oracle import psmf_oracle as O
 import rpsmf_amd as psmf
 
 KEEP = (1, 2, 7, 60)
-
-
-def ydict(Y):
-    return {k + 1: Y[k][:, None].copy() for k in range(Y.shape[0])}
 
 
 def _check(g, ep, k, st, info, robust, tol, R0=None):
@@ -80,9 +77,9 @@ def test_numpy_backend_dense_R_vs_reference(name, robust):
     else:
         f = psmf.PSMFIter(*a, {k: g["Q"] for k in range(T + 1)}, {k: R0 for k in range(T + 1)}, psmf.RandomWalk(), backend="numpy")
     f.optim_init()
-    f.step(ydict(Y), 1, T)
+    f.step(netlib.ydict(Y), 1, T)
     f.optim_update(1)
-    f.step(ydict(Y), 2, T)
+    f.step(netlib.ydict(Y), 2, T)
     p = f"s_e2_k{T}_"
     assert relerr(f._C[T], g[p + "C"]) < 1e-10 and relerr(f._V[T], g[p + "V"]) < 1e-10
     assert relerr(f._P[T], g[p + "P"]) < 1e-10 and relerr(f._mu[T], g[p + "mu"].reshape(-1, 1)) < 1e-10

@@ -9,18 +9,13 @@ filter.  GPU only: `pytest -m gpu`."""
 import numpy as np
 import pytest
 
+import netlib
 from conftest import relerr
 from oracle import psmf_oracle as O
 from oracle.impute_oracle import impute_filter
 from rpsmf_amd import impute
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(600)]
-
-
-def _capi():
-    from rpsmf_amd import _capi
-
-    return _capi
 
 
 def _problem(d, r, T, seed, heavy=False):
@@ -37,7 +32,7 @@ def _problem(d, r, T, seed, heavy=False):
 @pytest.mark.parametrize("robust", [False, True], ids=["PSMF", "rPSMF"])
 @pytest.mark.parametrize("r", [33, 40, 48, 49, 63, 64])
 def test_big_rank_random_walk_vs_oracle(r, robust):
-    c = _capi()
+    c = netlib.capi()
     d, T = 900 + r, 50
     Y, C0 = _problem(d, r, T, 300 + r, robust)
     V0, P0, Q = 0.1 * np.eye(r), np.eye(r), 0.1 * np.eye(r)
@@ -62,7 +57,7 @@ def test_big_rank_random_walk_vs_oracle(r, robust):
 @pytest.mark.parametrize("case", ["general_Q", "nonuniform_R"])
 def test_big_rank_without_the_dual_form(case):
     """A Q that is not a multiple of the identity, a non-uniform diagonal R: the two inversions run one after the other on one wave."""
-    c = _capi()
+    c = netlib.capi()
     d, r, T = 700, 40, 30
     Y, C0 = _problem(d, r, T, 77)
     rng = np.random.default_rng(5)
@@ -124,7 +119,7 @@ def test_persistent_kernel_at_33_to_48_matches_the_launched_form(name, r, opts, 
     a run cut in three."""
     import os
 
-    c = _capi()
+    c = netlib.capi()
     d, T = opts.get("d", 1100 + r), opts.get("T", 36)
     storage = opts.get("storage", "f64")
     Y, C0 = _problem(d, r, T, 900 + r, robust)

@@ -26,10 +26,11 @@ rounding of the print (0.005 us per part); one case per kernel that forms the su
 import hashlib
 import os
 import re
-from contextlib import contextmanager
 
 import numpy as np
 import pytest
+
+import netlib
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(300)]
 
@@ -62,20 +63,6 @@ def cases():
 
 
 CASES = cases()
-
-
-@contextmanager
-def _env(vars_):
-    old = {k: os.environ.get(k) for k in vars_}
-    os.environ.update(vars_)
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 _PROBLEMS = {}
@@ -115,7 +102,7 @@ def drive(c, cs, env=None):
         kw["dyn_kind"] = c.DYN_COS_PHASE
     elif cs["kind"] == "filter5":
         kw.update(coef_update=False, eta_full=False, pbar_predict=False)       # the simplified hooks
-    with _env(env):
+    with netlib.env(env):
         f = c.DeviceFilter(d, r, **kw)
     try:
         f.upload_series(np.ascontiguousarray(pb["Y"]))
@@ -215,7 +202,7 @@ def test_breakdown_inside_the_duration(name, capfd):
     if cs["want"] == "psmf_blk_filter3s":
         env["PSMF_FILTER6_DUAL"] = "0"
     kw = dict(coef_update=False, eta_full=False, pbar_predict=False) if cs["kind"] == "filter5" else {}
-    with _env(env):
+    with netlib.env(env):
         f = c.DeviceFilter(d, r, robust=cs["robust"], storage=cs["storage"], **kw)
         try:
             f.upload_series(np.ascontiguousarray(pb["Y"]))

@@ -25,29 +25,16 @@ import json
 import sys
 
 import os
-from contextlib import contextmanager
 
 import numpy as np
 import pytest
+
+import netlib
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(600)]
 
 STATE_KEYS = ("C", "V", "P", "Q", "mu", "rho", "lam", "s", "eta", "N", "phi", "omega", "k")
 COUNTER_KEYS = ("ns_steps", "sweep_steps", "ns_iterations", "ns_failed", "filter_launches")
-
-
-@contextmanager
-def _env(vars_):
-    old = {k: os.environ.get(k) for k in vars_}
-    os.environ.update(vars_)
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 def _problem(d, r, T, robust, seed, elementwise=False):
@@ -90,7 +77,7 @@ def _run(chain, d, r, T, robust, plan, want, seed, make=None, state_kw=None):
     V0, P0, Q = 0.1 * np.eye(r), np.eye(r), 0.1 * np.eye(r)
     rows = sorted({0, 1, T // 3, T // 2, T - 2, T - 1})
     snaps, counts = [], []
-    with _env(env):
+    with netlib.env(env):
         f = make(c, d, r, robust, T) if make else c.DeviceFilter(d, r, storage="f32", robust=robust)
     try:
         f.upload_series(Y)

@@ -4,29 +4,14 @@ floats through LDS instead of an L2 round trip, no operation and no order of ope
 off (=0, the through-memory path) must agree BIT FOR BIT: every comparison here is np.array_equal.  The same series and initial
 state run in a handle of each kind (switches are read per handle at psmf_create).  GPU only: `pytest -m gpu`."""
 
-import os
-from contextlib import contextmanager
-
 import numpy as np
 import pytest
+
+import netlib
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(600)]
 
 STATE_KEYS = ("C", "V", "P", "Q", "mu", "rho", "lam", "s", "eta", "N", "phi", "omega", "k")
-
-
-@contextmanager
-def _env(vars_):
-    old = {k: os.environ.get(k) for k in vars_}
-    os.environ.update(vars_)
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 def _problem(d, r, T, robust, seed):
@@ -64,7 +49,7 @@ def _run(carry, d, r, T, robust, plan, want, seed, make=None, chained=True):
     V0, P0, Q = 0.1 * np.eye(r), np.eye(r), 0.1 * np.eye(r)
     rows = sorted({0, 1, T // 3, T // 2, T - 2, T - 1})
     snaps, done = [], 0
-    with _env(env):
+    with netlib.env(env):
         f = make(c, d, r, robust, T) if make else c.DeviceFilter(d, r, storage="f32", robust=robust)
     # (the environment is back to what it was: the handle read it at psmf_create, nothing below looks at the environment)
     try:

@@ -12,12 +12,10 @@ float64 storage and a random walk).  The horizons are two or three blocks: the s
 the edges of the LAST block (nb = 1: the Y^T Y indexing at its edge; nb = B - 1: the zeroed K image and the clamped loads), not
 the length of the run.  GPU only: `pytest -m gpu`."""
 
-import os
-from contextlib import contextmanager
-
 import numpy as np
 import pytest
 
+import netlib
 from conftest import relerr
 from oracle import psmf_oracle as O
 
@@ -27,20 +25,6 @@ STATE_KEYS = ("C", "V", "P", "Q", "mu", "rho", "lam", "s", "eta", "N", "phi", "o
 COUNTER_KEYS = ("ns_steps", "sweep_steps", "ns_iterations", "ns_failed")
 TOL = {"f64": 1e-9, "f32": 1e-5}
 HANDLES = {"default": {}, "ahead_off": {"PSMF_XG_AHEAD": "0"}, "unchained": {"PSMF_BLOCK_CHAIN": "0"}}
-
-
-@contextmanager
-def _env(vars_):
-    old = {k: os.environ.get(k) for k in vars_}
-    os.environ.update(vars_)
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 def _block_steps(r):
@@ -80,7 +64,7 @@ def _run(env, Y, C0, r, robust, storage, plan, want):
         env["PSMF_FILTER6_DUAL"] = "0"        # r <= 16 runs psmf_blk_filter6d by default; this puts filter3s in its place
     V0, P0, Q = 0.1 * np.eye(r), np.eye(r), 0.1 * np.eye(r)
     out = []
-    with _env(env):
+    with netlib.env(env):
         f = c.DeviceFilter(d, r, storage=storage, robust=robust)
     try:
         f.upload_series(Y)

@@ -7,21 +7,12 @@ step.  GPU only: `pytest -m gpu`."""
 import numpy as np
 import pytest
 
+import netlib
 from conftest import load_golden, relerr
 from oracle import psmf_oracle as O
 import rpsmf_amd as psmf
 
 pytestmark = pytest.mark.gpu
-
-
-def _capi():
-    from rpsmf_amd import _capi
-
-    return _capi
-
-
-def ydict(Y):
-    return {k + 1: Y[k][:, None].copy() for k in range(Y.shape[0])}
 
 
 def _make(robust, C0, V0, mu0, P0, Q, R0, lam0, T, **kw):
@@ -40,7 +31,7 @@ def test_dense_R_vs_reference_answers(name, robust):
     f = _make(robust, g["C0"], g["V0"], g["mu0"], g["P0"], g["Q"], R0, float(g["lambda0"]), T, storage="f64")
     f.optim_init()
     for i in (1, 2):
-        f.step(ydict(Y), i, T)
+        f.step(netlib.ydict(Y), i, T)
         assert f._dev.geometry()["engine"] == "step"
         p = f"s_e{i}_k{T}_"
         assert relerr(f._C[T], g[p + "C"]) < 1e-9 and relerr(f._V[T], g[p + "V"]) < 1e-9
@@ -75,7 +66,7 @@ def test_dense_R_vs_oracle_dense_step(robust, storage, tol):
     Y, C0, R0 = _dense_problem(d, r, T + n_pred, 5 + robust, robust)
     V0, P0, Q = 0.1 * np.eye(r), np.eye(r), 0.1 * np.eye(r)
     f = _make(robust, C0, V0, np.zeros(r), P0, Q, R0, 1.8, T, storage=storage)
-    f.run(ydict(Y), T, 2, n_pred)
+    f.run(netlib.ydict(Y), T, 2, n_pred)
     st = O.State(C=C0, V=V0, mu=np.zeros(r), P=P0, Q=Q, rho=R0.copy(), lam=1.8)
     for i in (1, 2):
         if robust:
@@ -91,7 +82,7 @@ def test_dense_R_vs_oracle_dense_step(robust, storage, tol):
 def test_rotation_boundary_of_the_handle():
     """psmf_set_noise_rotation at the C-ABI: C goes in as U^T C and comes back as U (U^T C) = C (odd sizes: the GEMM's ragged tiles),
     projections come back in original coordinates, and what the rotation cannot do is refused."""
-    c = _capi()
+    c = netlib.capi()
     d, r = 131, 7
     rng = np.random.default_rng(3)
     A = rng.standard_normal((d, d))
@@ -134,8 +125,8 @@ def test_dense_R_that_the_device_refuses():
     f = psmf.PSMFIter(*a, {k: R0 * (1.0 + 0.1 * k) + 0.01 * np.diag(np.arange(d) * k) for k in range(T + 1)}, psmf.RandomWalk())
     f.optim_init()
     with pytest.raises(NotImplementedError):
-        f.step(ydict(Y), 1, T)
+        f.step(netlib.ydict(Y), 1, T)
     f = psmf.PSMFIter(*a, {k: R0 - 2.0 * np.eye(d) for k in range(T + 1)}, psmf.RandomWalk())
     f.optim_init()
     with pytest.raises(NotImplementedError):
-        f.step(ydict(Y), 1, T)
+        f.step(netlib.ydict(Y), 1, T)

@@ -9,6 +9,7 @@ import os
 import numpy as np
 import pytest
 
+import netlib
 from conftest import load_golden, relerr
 from oracle import psmf_oracle as O
 import rpsmf_amd as psmf
@@ -18,16 +19,6 @@ from rpsmf_amd import nonlinearities as NL
 GENERAL_17_32 = "psmf_blk_filter" if os.environ.get("PSMF_FILTER7") == "0" else "psmf_blk_filter7"
 
 pytestmark = pytest.mark.gpu
-
-
-def _capi():
-    from rpsmf_amd import _capi
-
-    return _capi
-
-
-def ydict(Y):
-    return {k + 1: Y[k][:, None].copy() for k in range(Y.shape[0])}
 
 
 def _problem(d, r, T, seed):
@@ -73,7 +64,7 @@ KINDS = [
 def test_device_dynamics_vs_oracle(name, make, r, robust):
     """mu_bar = f(theta, mu, k), P_bar = F P F^T + Q with the analytic F, and gradsum = sum_k J_theta^T g_f, all inside the
     blocked engine's time loop, against the oracle run on the same callable (complex-step F and J_theta)."""
-    c = _capi()
+    c = netlib.capi()
     d, T = 300, 90
     nl = make(r)
     rng = np.random.default_rng(11 + r)
@@ -128,7 +119,7 @@ def test_fourier_beijing_configuration_on_device():
                 {k: g["Q"] for k in range(T + 1)}, {k: np.eye(d) for k in range(T + 1)}, psmf.FourierBasis(rank=r, N=1), **kw)
         f.adam_init(gam=1e-3)
         for i in range(1, n_iter + 1):
-            f.step(ydict(Y[:T]), i, T)
+            f.step(netlib.ydict(Y[:T]), i, T)
             f.predict(i, T, n_pred)
             f.adam_update(i, project=True)
         theta = np.array([f._theta[i].reshape(-1) for i in range(n_iter + 1)])
@@ -136,7 +127,7 @@ def test_fourier_beijing_configuration_on_device():
         return f, theta, yp
 
     f, theta, yp = run(psmf.PSMFIter, storage="f64")
-    assert f._dev.geometry()["engine"] == "block" and f._dev.dyn_kind == _capi().DYN_FOURIER
+    assert f._dev.geometry()["engine"] == "block" and f._dev.dyn_kind == netlib.capi().DYN_FOURIER
     assert relerr(theta, g["theta"]) < 1e-7 and relerr(yp, g["y_pred_last"]) < 1e-7
     fb, theta_b, yp_b = run(Beijing, storage="f64")
     fn, theta_n, yp_n = run(Beijing, backend="numpy")
@@ -172,13 +163,13 @@ def test_host_stepped_arbitrary_callable(robust):
     st = O.State(C=C0, V=V0, mu=np.zeros(r), P=P0, Q=Q, rho=1.0, lam=1.8, theta=theta0.reshape(-1).copy())
     m = v = np.zeros(theta0.size)
     for i in (1, 2):
-        f.step(ydict(Y[:T]), i, T)
+        f.step(netlib.ydict(Y[:T]), i, T)
         f.predict(i, T, n_pred)
         st.gradsum = np.zeros(theta0.size)
         if robust:
             st.Q, st.rho, st.lam = Q, 1.0, 1.8
         st, Yp, _ = O.run_epoch(st, Y[:T], O.Mode(robust=robust), dyn)
-        assert f._dev.dyn_kind == _capi().DYN_HOST and f._dev.geometry()["engine"] == "step"
+        assert f._dev.dyn_kind == netlib.capi().DYN_HOST and f._dev.geometry()["engine"] == "step"
         assert relerr(f._C[T], st.C) < 1e-8 and relerr(f._P[T], st.P) < 1e-8 and relerr(f._mu[T], st.mu.reshape(-1, 1)) < 1e-8
         assert relerr(f._gradsum.reshape(-1), st.gradsum) < 1e-7
         yp = np.array([f._y_pred[k].reshape(-1) for k in range(1, T + n_pred + 1)])
@@ -200,8 +191,8 @@ def test_general_kind_beyond_r32_runs_in_the_device_loop():
     V0, P0, Q = 0.1 * np.eye(r), np.eye(r), 0.1 * np.eye(r)
     f = psmf.PSMFIter(theta0, C0, V0, np.zeros((r, 1)), P0, {k: Q for k in range(T + 1)}, {k: 1.0 for k in range(T + 1)}, nl, storage="f64")
     f.adam_init()
-    f.step(ydict(Y), 1, T)
-    assert f._dev.dyn_kind == _capi().DYN_SINUSOID and f._dev.geometry()["filter_kernel"] == "psmf_sweep_solve"
+    f.step(netlib.ydict(Y), 1, T)
+    assert f._dev.dyn_kind == netlib.capi().DYN_SINUSOID and f._dev.geometry()["filter_kernel"] == "psmf_sweep_solve"
     st = O.State(C=C0, V=V0, mu=np.zeros(r), P=P0, Q=Q, rho=1.0, lam=0.0, theta=theta0.reshape(-1).copy(), gradsum=np.zeros(nl.n_params))
     st, _, _ = O.run_epoch(st, Y, O.Mode(), O.CallableDyn(nl, nl.n_params))
     assert relerr(f._C[T], st.C) < 1e-8 and relerr(f._gradsum.reshape(-1), st.gradsum) < 1e-7
@@ -227,7 +218,7 @@ STEP_KINDS = [
 @pytest.mark.parametrize("robust", [False, True], ids=["PSMF", "rPSMF"])
 @pytest.mark.parametrize("name,make,r,rows", STEP_KINDS, ids=[k[0] for k in STEP_KINDS])
 def test_device_dynamics_on_the_per_step_engine(name, make, r, rows, robust):
-    c = _capi()
+    c = netlib.capi()
     d, T = 300, (60 if r < 40 else 24)          # (the oracle's complex-step Jacobians of a dense kind at r >= 40 are seconds per 10 timesteps)
     nl = make(r)
     rng = np.random.default_rng(311 + r)
@@ -263,7 +254,7 @@ def test_recursive_general_kind_per_step_engine_matches_the_blocked_engine(optim
     """The in-loop optimiser with a dense-Jacobian kind (psmf.py:287-304 with nonlinearities.py:81-114): the per-step engine's
     serial stage against the blocked engine's general kernel (itself pinned to the reference's run by the cos-phase fixtures and
     to the oracle's gradients above) -- theta after every update enters the next steps, so any difference grows."""
-    c = _capi()
+    c = netlib.capi()
     d, r, T = 300, 12, 80
     nl = NL.Sinusoid(r)
     rng = np.random.default_rng(8)
@@ -294,7 +285,7 @@ def test_recursive_general_kind_per_step_engine_matches_the_blocked_engine(optim
 def test_recursive_adam_both_engines(robust, engine):
     """PSMFRecursive / rPSMFRecursive (theta updated by Adam inside the time loop, psmf.py:287-304) in the blocked engine
     (in-loop optimiser inside the block kernel) and in the per-step engine, against the reference's run."""
-    c = _capi()
+    c = netlib.capi()
     g = load_golden("rpsmf_recursive" if robust else "psmf_recursive")
     T, n_pred, ue = int(g["T"]), int(g["n_pred"]), int(g["update_every"])
     d, r = g["C0"].shape
@@ -317,7 +308,7 @@ def test_recursive_adam_both_engines(robust, engine):
 def test_recursive_sinusoid_vs_oracle():
     """In-loop Adam with a dense-Jacobian kind and update_every = 3: theta (r^2 + 2 r parameters), its moments and the
     gradient restart all live in the block kernel's loop; oracle = step-by-step recursion + adam_update."""
-    c = _capi()
+    c = netlib.capi()
     d, r, T, ue = 200, 6, 50, 3
     nl = NL.Sinusoid(r)
     rng = np.random.default_rng(2)
@@ -362,7 +353,7 @@ def test_per_step_R_and_Q_schedules(engine, r, iso):
     V0, P0 = 0.1 * np.eye(r), np.eye(r)
     f = psmf.PSMFIter(np.zeros((0, 1)), C0, V0, np.zeros((r, 1)), P0, Qs, Rs, psmf.RandomWalk(), storage="f64", engine=engine)
     f.optim_init()
-    f.step(ydict(Y), 1, T)
+    f.step(netlib.ydict(Y), 1, T)
     assert f._dev.geometry()["engine"] == engine
     if engine == "block":      # schedules keep the run off filter3 (rho, q read once per block): filter4 reads them per step
         assert f._dev.geometry()["filter_kernel"] == ("psmf_blk_filter6" if r <= 16 else
@@ -391,11 +382,11 @@ def test_arbitrary_Q_schedule(where, monkeypatch):
         monkeypatch.setattr(psmf.PSMFIter, "_Q_MATRIX_SCHEDULE_MAX_BYTES", 0)
     f = psmf.PSMFIter(np.zeros((0, 1)), C0, V0, np.zeros((r, 1)), P0, Qs, {k: 2.0 for k in range(T + 1)}, psmf.RandomWalk(), storage="f64")
     f.optim_init()
-    f.step(ydict(Y), 1, T)
+    f.step(netlib.ydict(Y), 1, T)
     if where == "host":
-        assert f._dev.dyn_kind == _capi().DYN_HOST
+        assert f._dev.dyn_kind == netlib.capi().DYN_HOST
     else:
-        assert f._dev.dyn_kind == _capi().DYN_RANDOM_WALK and f._dev.geometry()["filter_kernel"] == "psmf_sweep_solve"
+        assert f._dev.dyn_kind == netlib.capi().DYN_RANDOM_WALK and f._dev.geometry()["filter_kernel"] == "psmf_sweep_solve"
     st = O.State(C=C0, V=V0, mu=np.zeros(r), P=P0, Q=Qs[1], rho=2.0, lam=0.0)
     st, _, _ = O.run_epoch(st, Y, O.Mode(), O.RandomWalkDyn(), Qs=lambda k: Qs[k])
     assert relerr(f._C[T], st.C) < 1e-9 and relerr(f._P[T], st.P) < 1e-9
@@ -415,10 +406,10 @@ def test_Q_matrix_schedule_met_in_a_later_epoch_keeps_C():
     V0, P0 = 0.1 * np.eye(r), np.eye(r)
     f = psmf.PSMFIter(np.zeros((0, 1)), C0, V0, np.zeros((r, 1)), P0, Qs, {k: 2.0 for k in range(T2 + 1)}, psmf.RandomWalk(), storage="f64", engine="step")
     f.optim_init()
-    f.step(ydict(Y[:T1]), 1, T1)
+    f.step(netlib.ydict(Y[:T1]), 1, T1)
     first = f._dev
     f.optim_update(1)
-    f.step(ydict(Y), 2, T2)
+    f.step(netlib.ydict(Y), 2, T2)
     assert f._dev is not first and f._dev.geometry()["filter_kernel"] == "psmf_sweep_solve"
     st = O.State(C=C0, V=V0, mu=np.zeros(r), P=P0, Q=Qs[1], rho=2.0, lam=0.0)
     for T in (T1, T2):
@@ -436,7 +427,7 @@ def test_tracking_error_norms_on_device():
 
     d, r, T, n_pred = 1200, 6, 80, 20
     Y, C0 = _problem(d, r, T + n_pred, 31)
-    y_full = ydict(Y)
+    y_full = netlib.ydict(Y)
     y_train = {k: y_full[k] for k in range(1, T + 1)}
     nl = psmf.CosPhase(r)
     theta0 = (1e-3 * np.arange(1, r + 1)).reshape(-1, 1)
@@ -477,11 +468,11 @@ def test_recursive_sgd_in_the_device_loop(robust, engine):
                                    {k: np.eye(d) for k in range(T + 1)}, nl, optim="sgd", **kw)
         f._update_every = ue                 # run() with a small step size: plain SGD at the default 1e-3 moves theta by O(1)
         f.optim_init(gam=1e-7)               # per observation here (gradients of O(10^3)) and the comparison turns chaotic
-        f.step(ydict(g["Y"]), T)
+        f.step(netlib.ydict(g["Y"]), T)
         f.predict(T, n_pred)
         out.append((f._theta[T].reshape(-1), f._C[T], np.array([f._y_pred[k].reshape(-1) for k in range(1, T + n_pred + 1)])))
         if "storage" in kw:
-            assert f._dev.dyn_kind == _capi().DYN_COS_PHASE          # evaluated on the device, theta stepped there
+            assert f._dev.dyn_kind == netlib.capi().DYN_COS_PHASE          # evaluated on the device, theta stepped there
             kern = f._dev.geometry()["filter_kernel"]
             assert kern == ("psmf_pstep_k" if engine == "step" else kern) and kern not in ("psmf_blk_filter4", "psmf_blk_filter4s", "psmf_blk_filter5")
     for a, b in zip(*out):
@@ -507,10 +498,10 @@ def test_recursive_custom_learning_rate_schedule_stays_host_stepped():
                                {k: np.eye(d) for k in range(T + 1)}, psmf.CosPhase(r), optim="sgd", **kw)
         f._update_every = ue
         f.optim_init(gam=Steps())
-        f.step(ydict(g["Y"]), T)
+        f.step(netlib.ydict(g["Y"]), T)
         out.append((f._theta[T].reshape(-1), f._C[T]))
         if "storage" in kw:
-            assert f._dev.dyn_kind == _capi().DYN_HOST
+            assert f._dev.dyn_kind == netlib.capi().DYN_HOST
     for a, b in zip(*out):
         assert relerr(a, b) < 1e-9
 
@@ -533,7 +524,7 @@ def test_nonuniform_diagonal_R_on_device(robust):
     f.optim_init()
     st = O.State(C=C0, V=V0, mu=np.zeros(r), P=P0, Q=Q, rho=rho.copy(), lam=1.8)
     for i in (1, 2):
-        f.step(ydict(Y), i, T)
+        f.step(netlib.ydict(Y), i, T)
         assert f._dev.geometry()["engine"] == "step"
         if robust:
             st.Q, st.rho, st.lam = Q, rho.copy(), 1.8
@@ -552,7 +543,7 @@ def test_simplified_hooks_kernel_vs_oracle(kind, robust, recursive):
     """psmf_blk_filter5: the simplified hook configuration (synthetic_psmf.py:78-100, synthetic_rpsmf.py:82-118) with a
     diagonal-Jacobian f, PSMF and rPSMF, with the gradient summed over the epoch or Adam stepping theta inside the loop
     (update_every = 2) -- against the oracle on the same callable (complex-step derivatives), float64 storage."""
-    c = _capi()
+    c = netlib.capi()
     d, r, T, ue = 500, 12, 110, 2
     nl = NL.CosPhase(r) if kind == "cos_phase" else NL.Sinusoid(r, scaled=False)
     rng = np.random.default_rng(31 + r)
@@ -597,7 +588,7 @@ def test_simplified_hooks_kernel_vs_oracle(kind, robust, recursive):
 def test_q_matrix_schedule_refusals_and_dense_dynamics_with_it():
     """psmf_set_q_matrix_schedule: refused where it cannot hold (blocked engine, rPSMF's own running Q), range-checked by psmf_run,
     dropped again by None; and together with a dense-Jacobian kind (P_bar = F P F^T + Q_k, both in the serial stage) against the oracle."""
-    c = _capi()
+    c = netlib.capi()
     d, r, T = 350, 5, 24
     Y, C0 = _problem(d, r, T, 31)
     rng = np.random.default_rng(4)

@@ -9,18 +9,13 @@ BASELINE.json's north_star states.
 import numpy as np
 import pytest
 
+import netlib
 from conftest import load_golden, relerr
 from oracle import psmf_oracle as O
 
 pytestmark = pytest.mark.gpu
 
 TOL = {"f64": 1e-9, "f32": 1e-5}
-
-
-def _capi():
-    from rpsmf_amd import _capi
-
-    return _capi
 
 
 @pytest.fixture(params=["step", "block"])
@@ -47,7 +42,7 @@ def _compare(dev_state, st, tol, what=("C", "V", "mu", "P")):
 @pytest.mark.parametrize("name,robust", [("psmf_full_rw", False), ("rpsmf_full_rw", True)])
 def test_golden_full_filter(name, robust, storage, engine):
     """PSMFIter / rPSMFIter as shipped (d=20, r=5, T=200, two epochs) against the reference's outputs."""
-    c = _capi()
+    c = netlib.capi()
     g = load_golden(name)
     Y = g["Y"]
     T, d = Y.shape
@@ -91,7 +86,7 @@ def _problem(d, r, T, seed, noise="normal"):
 @pytest.mark.parametrize("d,r,T", [(3000, 20, 150), (777, 7, 60), (4096, 32, 80), (260, 64, 40), (50, 1, 30)])
 def test_full_filter_vs_oracle(d, r, T, robust, storage, engine):
     """Full filter, random walk, ragged shapes (rows not a multiple of the tile, r not a multiple of 4)."""
-    c = _capi()
+    c = netlib.capi()
     if engine == "block" and r > 32:
         pytest.skip("the blocked engine needs r <= 32")
     Y, C0 = _problem(d, r, T, 100 + d + r, "t" if robust else "normal")
@@ -124,7 +119,7 @@ def test_full_filter_vs_oracle(d, r, T, robust, storage, engine):
 def test_simplified_cos_mode(robust, storage, engine):
     """ExperimentSynthetic configuration on the device: P = 0, eta = tr(R)/d, no coefficient update,
     cos dynamics with theta, closed-form theta gradient (synthetic_psmf.py:78-100)."""
-    c = _capi()
+    c = netlib.capi()
     g = load_golden("rpsmf_simplified_cos" if robust else "psmf_simplified_cos")
     T, n_pred = int(g["T"]), int(g["n_pred"])
     Y = g["Y_obs"][:T]
@@ -159,7 +154,7 @@ def test_simplified_cos_mode(robust, storage, engine):
 @pytest.mark.parametrize("robust", [False, True])
 def test_recursive_adam_on_device(robust):
     """PSMFRecursive / rPSMFRecursive: theta updated by Adam inside the device time loop."""
-    c = _capi()
+    c = netlib.capi()
     g = load_golden("rpsmf_recursive" if robust else "psmf_recursive")
     T, n_pred, ue = int(g["T"]), int(g["n_pred"]), int(g["update_every"])
     d, r = g["C0"].shape
@@ -183,7 +178,7 @@ def test_recursive_adam_on_device(robust):
 
 def test_graph_and_eager_agree_bitwise():
     """The hipGraph replay and plain launches run the same kernels: identical bits."""
-    c = _capi()
+    c = netlib.capi()
     d, r, T = 2000, 20, 600   # > one graph chunk of 256 steps
     Y, C0 = _problem(d, r, T, 5)
     outs = []
@@ -199,7 +194,7 @@ def test_graph_and_eager_agree_bitwise():
 
 
 def test_gram_refresh_changes_nothing_material():
-    c = _capi()
+    c = netlib.capi()
     d, r, T = 3000, 16, 300
     Y, C0 = _problem(d, r, T, 9)
     res = []
@@ -217,7 +212,7 @@ def test_gram_refresh_changes_nothing_material():
 def test_collective_path_single_rank_matches_plain(engine):
     """The multi-GPU code path (local reduce kernel -> RCCL all-reduce of h, ee -> serial stage, all
     captured in the hipGraph) run with a one-rank communicator must equal the plain path."""
-    c = _capi()
+    c = netlib.capi()
     d, r, T = 1500, 12, 130   # blocked engine: block length 52 -> 3 pipelined blocks (cross-Gram all-reduce on the bulk stream)
     Y, C0 = _problem(d, r, T, 21)
     full = c.DeviceFilter(d, r, storage="f64", engine=engine)
@@ -246,7 +241,7 @@ def test_collective_path_single_rank_matches_plain(engine):
 
 def test_singular_system_raises_linalgerror(engine):
     """Non-finite state -> the r x r solve has no usable pivot -> LinAlgError, as numpy.linalg.inv would raise."""
-    c = _capi()
+    c = netlib.capi()
     d, r, T = 64, 4, 3
     Y = np.zeros((T, d))
     f = c.DeviceFilter(d, r, storage="f64", engine=engine)
@@ -261,7 +256,7 @@ def test_singular_system_raises_linalgerror(engine):
 def test_engines_agree_and_auto_selects_blocked():
     """The two engines are the same recursion: float64 storage -> agreement to round-off, long series
     (several blocks + a ragged last one)."""
-    c = _capi()
+    c = netlib.capi()
     d, r, T = 5000, 20, 200    # block length 64 - 20 = 44: 4 full blocks + 24
     Y, C0 = _problem(d, r, T, 77)
     out = {}
@@ -289,7 +284,7 @@ def test_engines_agree_and_auto_selects_blocked():
 def test_mean_history_matches_oracle(robust, engine):
     """`_mu[k]`, k = 0..T (what TrackingMixin reads, tracking.py:140-142), against the oracle step by step;
     several blocks and a second run segment appended to the first."""
-    c = _capi()
+    c = netlib.capi()
     d, r, T = 1500, 9, 140
     Y, C0 = _problem(d, r, T, 5, "t" if robust else "normal")
     V0, P0, Q = 0.1 * np.eye(r), np.eye(r), 0.1 * np.eye(r)
@@ -317,7 +312,7 @@ def test_mean_history_matches_oracle(robust, engine):
 
 
 def test_argument_errors():
-    c = _capi()
+    c = netlib.capi()
     with pytest.raises(ValueError):
         c.DeviceFilter(10, 65)
     f = c.DeviceFilter(10, 3)
@@ -334,7 +329,7 @@ def test_streaming_block_kernels_edge_shapes(d, r, T, robust):
     """Role-specialised filter kernel + streaming cross-Gram / apply kernels (f32 storage, d % 4 == 0, 16 <= r <= 32):
     rows not a multiple of the 16-row tile, odd r (identity padding of the 32 x 32 iterates), r < 32 (three column
     tiles of the next series block), a short last block, several passes over the series (carried inverses)."""
-    c = _capi()
+    c = netlib.capi()
     Y, C0 = _problem(d, r, T, 300 + d + r, "t" if robust else "normal")
     Y = Y.astype(np.float32).astype(np.float64)
     C0 = C0.astype(np.float32).astype(np.float64)
@@ -361,7 +356,7 @@ def test_collective_path_single_rank_streaming_kernels():
     (cross-Gram all-reduce of the pipelined blocks on the bulk stream)."""
     import os
 
-    c = _capi()
+    c = netlib.capi()
     d, r, T = 2000, 32, 150
     Y, C0 = _problem(d, r, T, 23)
     Y = Y.astype(np.float32).astype(np.float64)
@@ -390,7 +385,7 @@ def test_split_runs_carry_the_state(robust):
     """A series filtered in two psmf_run calls (split in the middle of a block, state read back in between) equals one call:
     the r x r state travels between blocks / runs as the kernels' register dump, the row-major copies are written by the
     last block of each run (f64 storage: agreement to round-off; different block boundaries, same recursion)."""
-    c = _capi()
+    c = netlib.capi()
     d, r, T, T1 = 2048, 32, 330, 141
     Y, C0 = _problem(d, r, T, 77, "t" if robust else "normal")
     V0, P0, Q = 0.1 * np.eye(r), np.eye(r), 0.1 * np.eye(r)
@@ -427,7 +422,7 @@ def test_chained_blocks_one_launch_per_run(r, T):
     if os.environ.get("PSMF_BLOCK_CHAIN") == "0" or os.environ.get("PSMF_BLOCK_FLAGS") == "0" or os.environ.get("PSMF_BLOCK_PIPE") == "0" \
             or os.environ.get("PSMF_RESERVED_CUS") == "0" or os.environ.get("PSMF_FILTER3") == "0":
         pytest.skip("a fallback was selected in the environment")
-    c = _capi()
+    c = netlib.capi()
     d = 2048
     Y, C0 = _problem(d, r, T, 4242 + r, "normal")
     V0, P0, Q = 0.1 * np.eye(r), np.eye(r), 0.1 * np.eye(r)
@@ -458,7 +453,7 @@ def test_chained_blocks_one_launch_per_run(r, T):
 def test_rpsmf_scaling_factors_and_fixed_lambda(d, r, T, fixed_lambda, engine):
     """rPSMF with use_scaling-style factors alpha, beta != 1 (rpsmf.py:45-51,133-171) and fixed_lambda (rpsmf.py:36-40,170-171):
     every filter kernel of both engines against the oracle (f64 storage)."""
-    c = _capi()
+    c = netlib.capi()
     Y, C0 = _problem(d, r, T, 500 + d + r, "t")
     V0, P0, Q = 0.1 * np.eye(r), np.eye(r), 0.1 * np.eye(r)
     mode = O.Mode(robust=True, alpha=0.93, beta=1.07, fixed_lambda=fixed_lambda)
@@ -484,7 +479,7 @@ def test_start_predictor_saves_iterations_not_accuracy(r, storage, robust):
     import os
     if os.environ.get("PSMF_FILTER3") == "0" or os.environ.get("PSMF_NS") == "0":
         pytest.skip("a fallback was selected in the environment")
-    c = _capi()
+    c = netlib.capi()
     d, T = 3072, 400
     Y, C0 = _problem(d, r, T, 777 + r, "normal")
     V0, P0, Q = 0.1 * np.eye(r), np.eye(r), 0.1 * np.eye(r)
@@ -524,7 +519,7 @@ def test_bulk_kernel_grid_does_not_change_the_result_beyond_rounding():
     shader engines really have (224 on an MI355X with the filter's CUs reserved).  Any grid gives the same
     filter up to the rounding of a different grouping of the cross-Gram's partial sums."""
     import os
-    c = _capi()
+    c = netlib.capi()
     d, r, T = 5000, 32, 130
     Y, C0 = _problem(d, r, T, 99, "normal")
     V0, P0, Q = 0.1 * np.eye(r), np.eye(r), 0.1 * np.eye(r)

@@ -18,13 +18,13 @@ GPU only: `pytest -m gpu`; `-s` shows the counters and error figures of every ca
 
 import hashlib
 import os
-from contextlib import contextmanager
 
 import numpy as np
 import pytest
 
 import blocked_cases as BC
 import decision_path_cases as DP
+import netlib
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(300)]
 
@@ -32,20 +32,6 @@ STATE_KEYS = ("C", "V", "P", "Q", "mu", "rho", "lam", "s", "eta", "N", "phi", "o
 COUNTER_KEYS = ("ns_steps", "sweep_steps", "ns_iterations", "ns_failed", "filter_launches", "filter_kernel_launches")
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "filter3_decision_paths.npz")
 CASES = DP.cases()
-
-
-@contextmanager
-def _env(vars_):
-    old = {k: os.environ.get(k) for k in vars_}
-    os.environ.update(vars_)
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 def digest(a):
@@ -56,7 +42,7 @@ def digest(a):
 def drive(c, cs, pb):
     """The two passes of a case on one handle -> per pass: state, y_pred, mean history, integer counters"""
     r, d, T = cs["r"], cs["d"], cs["T"]
-    with _env(cs["env"]):
+    with netlib.env(cs["env"]):
         f = c.DeviceFilter(d, r, robust=cs["robust"], storage=cs["storage"], engine="block")
     try:
         f.upload_series(np.ascontiguousarray(pb["Y"]))

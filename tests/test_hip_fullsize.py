@@ -10,6 +10,7 @@ series cannot show either.  Tolerance: BASELINE.json north_star, 1e-5 relative (
 import numpy as np
 import pytest
 
+import netlib
 from conftest import load_golden as load_golden_fixture, relerr, relerr_elementwise
 from oracle import psmf_oracle as O
 from oracle.impute_oracle import impute_filter
@@ -25,12 +26,6 @@ TOL = 1e-5
 ELEMENTWISE_FACTOR = 150.0
 
 
-def _capi():
-    from rpsmf_amd import _capi
-
-    return _capi
-
-
 def _bench_problem(d, r, T, robust):
     """The synthetic workload of bench.py / SURVEY 8(d): data.py semantics, C0 = 0.1 randn, V0 = 0.1 I, P0 = I, Q = 0.1 I,
     R = I, mu0 = 0, seeds of the reference Makefile (35853 PSMF, 35833 rPSMF with lambda0 = 1.8, Student-t noise dof 3)."""
@@ -42,7 +37,7 @@ def _bench_problem(d, r, T, robust):
 
 
 def _checkpointed_parity(d, r, T, robust, checkpoints, engine="auto", storage="f32", tol=TOL):
-    c = _capi()
+    c = netlib.capi()
     Y, C0 = _bench_problem(d, r, T, robust)
     V0, P0, Q = 0.1 * np.eye(r), np.eye(r), 0.1 * np.eye(r)
     mode = O.Mode(robust=robust)
@@ -108,7 +103,7 @@ def test_config_E_full_horizon_two_epochs_vs_oracle_fixture(which):
 
     g = load_golden_fixture(f"fullsize_E_{which}")
     d, r, T, robust = int(g["d"]), int(g["r"]), int(g["T"]), bool(g["robust"])
-    c = _capi()
+    c = netlib.capi()
     series = bench.Series(d, r, T, int(g["seed"]), 0, d, robust)
     st0 = bench.init_state(d, r, int(g["seed"]))
     f = c.DeviceFilter(d, r, robust=robust, storage="f32")
@@ -164,7 +159,7 @@ def test_config_E_full_horizon_two_epochs_vs_oracle_fixture(which):
 def test_per_step_engine_tolerance_r40():
     """r > 32 runs on the per-step engine (one rounding of C per timestep with f32 storage would breach 1e-5 around
     k = 300: DESIGN section 5), so the library stores C in float64 there.  d = 20 000, r = 40, T = 1 000."""
-    c = _capi()
+    c = netlib.capi()
     d, r, T = 20_000, 40, 1_000
     worst, geo = _checkpointed_parity(d, r, T, False, (300, 1000), storage="auto")
     assert geo["engine"] in ("step", "block")
@@ -253,7 +248,7 @@ def test_filter4_cos_phase_at_size(robust, q, recursive):
     to 1e-11 at k = 50, 1e-6 at k = 100 and not at all at k = 200: tools/probe_f4g.py, float64 storage) -- the reference itself
     would not reproduce its own run under a different BLAS.  So: float64 storage over 48 timesteps (two blocks) at 1e-6, float32
     storage over the first 30 at 1e-5 (north_star)."""
-    c = _capi()
+    c = netlib.capi()
     d, r, T = 20_000, 20, 48
     Y, C0 = _bench_problem(d, r, T, robust)
     rng = np.random.default_rng(77)
@@ -302,7 +297,7 @@ def test_filter5_simplified_cos_phase_at_size(robust):
     """The ExperimentSynthetic configuration (simplified hooks, f = cos(2 pi theta t + x): synthetic_psmf.py:78-106,
     synthetic_rpsmf.py:82-124) at d = 20 000, r = 20, T = 1 000, f32 storage, on psmf_blk_filter5 -- state, predictions and the
     theta gradient against the oracle.  (Unlike the full filter this recursion is stable: mu_k = mu_bar_k does not see the data.)"""
-    c = _capi()
+    c = netlib.capi()
     d, r, T = 20_000, 20, 1_000
     Y, C0 = _bench_problem(d, r, T, robust)
     theta0 = 1e-3 * np.arange(1, r + 1) + 0.01 * np.random.default_rng(5).random(r)
@@ -334,7 +329,7 @@ def test_filter6_fourier_and_random_walk_at_size(robust):
     default model (random walk, r = 12) on the side-by-side form of the kernel."""
     from rpsmf_amd import nonlinearities as NL
 
-    c = _capi()
+    c = netlib.capi()
     d, T = 10_000, 300          # (the oracle's complex-step Jacobians over 480 parameters set the price of this test)
     for r, nl in ((10, NL.FourierBasis(10, N=2)), (12, NL.RandomWalk())):
         Y, C0 = _bench_problem(d, r, T, robust)

@@ -6,16 +6,13 @@ import json
 import numpy as np
 import pytest
 
+import netlib
 from conftest import load_golden, relerr
 import rpsmf_amd as psmf
 from rpsmf_amd import impute, impute_harness as H
 from oracle.impute_oracle import impute_filter
 
 pytestmark = pytest.mark.gpu
-
-
-def ydict(Y):
-    return {k + 1: Y[k][:, None].copy() for k in range(Y.shape[0])}
 
 
 @pytest.mark.parametrize("name,robust", [("psmf_full_rw", False), ("rpsmf_full_rw", True)])
@@ -33,7 +30,7 @@ def test_classes_full_filter_on_device(name, robust):
         f = psmf.PSMFIter(theta0, g["C0"], g["V0"], mu0, g["P0"], {k: g["Q"] for k in range(T + 1)},
                           {k: np.eye(d) for k in range(T + 1)}, psmf.RandomWalk(), storage="f64")
     f.optim_init()
-    y = ydict(Y)
+    y = netlib.ydict(Y)
     f.step(y, 1, T)
     f.optim_update(1)
     f.step(y, 2, T)
@@ -60,7 +57,7 @@ def test_use_scaling_on_device_vs_reference_run():
                        psmf.RandomWalk(), use_scaling=True, storage="f64")
     assert abs(f._alpha - float(g["alpha"])) < 1e-12 and abs(f._beta - float(g["beta"])) < 1e-12
     f.optim_init()
-    f.step(ydict(Y), 1, T)
+    f.step(netlib.ydict(Y), 1, T)
     assert relerr(f._C[T], g["C_T"]) < 1e-9 and relerr(f._V[T], g["V_T"]) < 1e-9
     assert relerr(f._mu[T], g["mu_T"].reshape(-1, 1)) < 1e-9 and relerr(f._P[T], g["P_T"]) < 1e-9
     yp = np.array([f._y_pred[k].reshape(-1) for k in range(1, T + 1)])
@@ -84,7 +81,7 @@ def test_experiment_synthetic_on_device(name, robust, storage, tol):
             super().step_reset()
             self._V = {0: self.V0}   # V is re-initialised every epoch (synthetic_psmf.py:78-81)
 
-    y_obs = ydict(g["Y_obs"])
+    y_obs = netlib.ydict(g["Y_obs"])
     y_train = {k: y_obs[k] for k in range(1, T + 1)}
     theta0, mu0 = g["theta0"].reshape(-1, 1), g["mu0"].reshape(-1, 1)
     nl = psmf.CosPhase(r)
@@ -118,7 +115,7 @@ def test_recursive_classes_on_device(name, robust):
     else:
         f = psmf.PSMFRecursive(theta0, g["C0"], g["V0"], mu0, g["P0"], {k: g["Q"] for k in range(T + 1)},
                                {k: np.eye(d) for k in range(T + 1)}, nl, storage="f64")
-    f.run(ydict(g["Y"]), T, n_pred, update_every=ue)
+    f.run(netlib.ydict(g["Y"]), T, n_pred, update_every=ue)
     assert relerr(f._theta[T].reshape(-1), g["theta"][-1]) < 1e-6
     assert relerr(f._C[T], g["C_T"]) < 1e-6
     yp = np.array([f._y_pred[k].reshape(-1) for k in range(1, T + n_pred + 1)])

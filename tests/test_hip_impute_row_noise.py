@@ -11,6 +11,7 @@ import os
 import numpy as np
 import pytest
 
+import netlib
 from conftest import ROOT, relerr
 from oracle.impute_oracle import impute_filter, mle_smf_filter
 from rpsmf_amd import impute
@@ -40,18 +41,6 @@ def _err(a, b):
     a, b = np.asarray(a, dtype=float), np.asarray(b, dtype=float)
     assert np.array_equal(np.isnan(a), np.isnan(b))
     return relerr(np.nan_to_num(a), np.nan_to_num(b))
-
-
-def _with_env(name, value, fn):
-    old = os.environ.get(name)
-    os.environ[name] = value
-    try:
-        return fn()
-    finally:
-        if old is None:
-            os.environ.pop(name, None)
-        else:
-            os.environ[name] = old
 
 
 KERNEL3 = [(7, 3), (19, 10), (19, 9), (25, 7), (32, 14), (48, 14), (75, 10), (80, 13), (2, 1)]
@@ -91,11 +80,14 @@ def test_row_noise_vs_oracle(d, r, robust):
     _check(res, ep, ef, ib, st, tol, (0, 2))
     for k in OUTPUTS:
         assert np.array_equal(res[k][0], res[k][2], equal_nan=True), k            # replicas of one problem: the same bits
-    res2 = _with_env("PSMF_IMPUTE_V3", "0", run)
+    with netlib.env({"PSMF_IMPUTE_V3": "0"}):
+        res2 = run()
     assert res2["kernel"] == "psmf_impute_kernel2w"
     _check(res2, ep, ef, ib, st, tol, (0, 2), "PSMF_IMPUTE_V3=0")
     if (d, r) in ((19, 10), (7, 3), (75, 10)):
-        _check(_with_env("PSMF_IMPUTE_PAR", "0", run), ep, ef, ib, st, tol, (0, 2), "PSMF_IMPUTE_PAR=0")
+        with netlib.env({"PSMF_IMPUTE_PAR": "0"}):
+            res3 = run()
+        _check(res3, ep, ef, ib, st, tol, (0, 2), "PSMF_IMPUTE_PAR=0")
 
 
 @pytest.mark.parametrize("robust", [False, True], ids=["PSMF", "rPSMF"])

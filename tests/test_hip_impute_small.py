@@ -3,11 +3,10 @@ CPU oracle and against version 2 of the loop (PSMF_IMPUTE_V3=0) on the same inpu
 even and odd ranks, every LDS row-group instantiation (d <= 12, <= 20, <= 32, <= 48, <= 80), Q = q I (two inversions side by side) and a
 general Q (two sweeps in turn), rows / columns without observations, bands.  GPU only: `pytest -m gpu`."""
 
-import os
-
 import numpy as np
 import pytest
 
+import netlib
 from conftest import relerr
 from oracle.impute_oracle import impute_filter, mle_smf_filter, tmf_filter
 from rpsmf_amd import impute
@@ -39,26 +38,16 @@ def _err(a, b):
     return relerr(np.nan_to_num(a), np.nan_to_num(b))
 
 
-def _with_env(name, value, fn):
-    old = os.environ.get(name)
-    os.environ[name] = value
-    try:
-        return fn()
-    finally:
-        if old is None:
-            os.environ.pop(name, None)
-        else:
-            os.environ[name] = old
-
-
 def _v2(fn):
-    return _with_env("PSMF_IMPUTE_V3", "0", fn)
+    with netlib.env({"PSMF_IMPUTE_V3": "0"}):
+        return fn()
 
 
 def _sequential(fn):
     """PSMF_IMPUTE_PAR=0: the two r x r inversions of a column one after the other on one wave (the Q = q I case takes them side by
     side on two by default)"""
-    return _with_env("PSMF_IMPUTE_PAR", "0", fn)
+    with netlib.env({"PSMF_IMPUTE_PAR": "0"}):
+        return fn()
 
 
 SHAPES = [(19, 10), (19, 9), (7, 3), (12, 5), (16, 14), (20, 13), (21, 2), (32, 14), (25, 7), (2, 1),

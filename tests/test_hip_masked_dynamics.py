@@ -10,32 +10,16 @@ theta after an epoch 1e-7, theta stepped inside the loop 1e-6, predict 1e-8 (tes
 those four times 1e3; sharded against unsharded SHARD_BAR = 1e-11 with the replicated quantities bit-identical."""
 
 import os
-import threading
-from contextlib import contextmanager
 
 import numpy as np
 import pytest
 
 import gram_cases as GC
 import masked_dyn_cases as D
-from host_group import HostGroup
+import netlib
 from oracle import psmf_oracle as O
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(120)]
-
-
-@contextmanager
-def _env(vars_):
-    old = {k: os.environ.get(k) for k in vars_}
-    os.environ.update(vars_)
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 def bars(cs):
@@ -171,22 +155,7 @@ def test_two_uneven_shards(robust):
     whole = run_handle(c, cs, pb, parts=parts)
     shards = (187, 113)
     row0 = (0, shards[0])
-    grp = HostGroup(2)
-    out, errs = [None, None], []
-
-    def worker(rank):
-        try:
-            out[rank] = run_handle(c, cs, pb, parts=parts, row0=row0[rank], dl=shards[rank], comm=(2, rank, grp.allreduce(rank)))
-        except BaseException as e:      # noqa: BLE001
-            errs.append((rank, e))
-            grp.barrier.abort()
-
-    th = [threading.Thread(target=worker, args=(k,)) for k in range(2)]
-    for t in th:
-        t.start()
-    for t in th:
-        t.join(100)
-    assert not any(t.is_alive() for t in th) and not errs, errs
+    _, out = netlib.run_ranks(2, lambda rank, comm: run_handle(c, cs, pb, parts=parts, row0=row0[rank], dl=shards[rank], comm=comm), 100)
     for k in ("V", "P", "mu", "theta", "gradsum"):
         assert np.array_equal(out[0]["s"][k], out[1]["s"][k]), k
     assert np.array_equal(out[0]["X"], out[1]["X"]) and np.array_equal(out[0]["cut"][h][0], out[1]["cut"][h][0])
@@ -286,7 +255,7 @@ def test_persistent_against_launched_form(robust, ue):
     pb, ref = D.reference(cs)
     got = {}
     for name, env in (("persistent", {"PSMF_STEP_PERSISTENT": "1"}), ("launched", {"PSMF_STEP_PERSISTENT": "0"})):
-        with _env(env):
+        with netlib.env(env):
             got[name] = run_handle(c, cs, pb)
     assert got["persistent"]["kernel"] == "psmf_pstep_k" and got["launched"]["kernel"] == "psmf_sweep_solve"
     a, b = got["persistent"], got["launched"]
@@ -308,7 +277,7 @@ def test_random_walk_is_the_masked_handle_of_before(robust):
     T = cs["T"]
     for env in ({"PSMF_STEP_PERSISTENT": "1"}, {"PSMF_STEP_PERSISTENT": "0"}):
         out = []
-        with _env(env):
+        with netlib.env(env):
             for masked in (1, c.MASKED_DYNAMICS):
                 f = c.DeviceFilter(cs["d"], cs["r"], robust=robust, storage="f64", masked=masked, engine="step")
                 try:

@@ -16,35 +16,18 @@ exactly (float32: 5e-4); sharded against unsharded 1e-11.  tests/test_gram_cases
 to a last-bit change of the inputs sits 16 x inside them for every case.
 Reference: ExperimentImpute/PSMF.py:40-95, rPSMF.py:40-148, MLESMF.py:40-92, TMF.py:30-73; pypsmf/psmf/psmf.py:140-152."""
 
-import os
-import threading
 import time
-from contextlib import contextmanager
 
 import numpy as np
 import pytest
 
 import gram_cases as GC
+import netlib
 from conftest import relerr
-from host_group import HostGroup
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(120)]
 
 METHOD_CODE = {"psmf": 1, "rpsmf": 1, "mle_smf": 2, "tmf": 3}          # cfg.masked (include/psmf_hip.h)
-
-
-@contextmanager
-def _env(vars_):
-    old = {k: os.environ.get(k) for k in vars_}
-    os.environ.update(vars_)
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 def _gam(ep):
@@ -106,26 +89,6 @@ def _masked_errs(cs, pb, ref, got, tol):
     return errs
 
 
-def _threads(n, fn):
-    grp = HostGroup(n)
-    out, errs = [None] * n, []
-
-    def worker(rank):
-        try:
-            out[rank] = fn(rank, (n, rank, grp.allreduce(rank)))
-        except BaseException as e:      # noqa: BLE001
-            errs.append((rank, e))
-            grp.barrier.abort()
-
-    th = [threading.Thread(target=worker, args=(k,)) for k in range(n)]
-    for t in th:
-        t.start()
-    for t in th:
-        t.join(100)
-    assert not any(t.is_alive() for t in th) and not errs, errs
-    return grp, out
-
-
 def _run_masked(c, cs, pb, ref):
     tol, r, T = GC.bar(cs), cs["r"], cs["T"]
     if cs["route"] == "batch":
@@ -148,7 +111,7 @@ def _run_masked(c, cs, pb, ref):
     errs = _masked_errs(cs, pb, ref, flat(whole), tol)
     if cs["shards"]:
         row0 = np.concatenate([[0], np.cumsum(cs["shards"])]).astype(int)
-        grp, out = _threads(len(cs["shards"]), lambda rank, comm: _masked_handle(c, cs, pb, int(row0[rank]), cs["shards"][rank], comm))
+        grp, out = netlib.run_ranks(len(cs["shards"]), lambda rank, comm: _masked_handle(c, cs, pb, int(row0[rank]), cs["shards"][rank], comm), 100)
         assert all(o["kernel"] == "psmf_sweep_solve" for o in out), [o["kernel"] for o in out]
         for o in out[1:]:                    # replicated state: the same bits on every shard
             for k in {"psmf": ("V", "P", "mu"), "rpsmf": ("V", "P", "mu"), "mle_smf": ("P", "mu"), "tmf": ("mu",)}[cs["method"]]:      # (what the method keeps)
@@ -203,7 +166,7 @@ def _run_weighted(c, cs, pb, ref):
     errs = [(f"{k}@{j}", relerr(g[k], w[k]), tol) for j, (g, w) in enumerate(zip(whole, ref)) for k in GC.WEIGHTED_KEYS]
     if cs["shards"]:
         row0 = np.concatenate([[0], np.cumsum(cs["shards"])]).astype(int)
-        grp, out = _threads(len(cs["shards"]), lambda rank, comm: _weighted_handle(c, cs, pb, ref, int(row0[rank]), cs["shards"][rank], comm)[1])
+        grp, out = netlib.run_ranks(len(cs["shards"]), lambda rank, comm: _weighted_handle(c, cs, pb, ref, int(row0[rank]), cs["shards"][rank], comm)[1], 100)
         for j, w in enumerate(ref):
             for o in out[1:]:
                 for k in ("V", "P", "mu"):
@@ -229,7 +192,7 @@ def test_masked_gram_net(i):
     with np.errstate(all="ignore"):
         ref = GC.reference(cs, pb)
     t1 = time.perf_counter()
-    with _env(cs["env"]):
+    with netlib.env(cs["env"]):
         kernel, errs = (_run_masked if cs["masked"] else _run_weighted)(c, cs, pb, ref)
     p = GC.plan_of(cs)
     worst = max(errs, key=lambda e: (e[1] / e[2]) if np.isfinite(e[1]) else np.inf)
@@ -284,7 +247,7 @@ def test_a_mask_that_arrives_in_pieces():
             try:
                 f.upload_series(Y)
                 f.upload_mask(M[:cut] if pieces else M)
-                f.set_state(C0, GC._spd(np.random.default_rng(r), r, 2.0), np.eye(r), 0.1 * np.eye(r), np.full(r, 0.3), rho=5.0)
+                f.set_state(C0, netlib.spd(np.random.default_rng(r), r, 2.0), np.eye(r), 0.1 * np.eye(r), np.full(r, 0.3), rho=5.0)
                 assert f.geometry()["filter_kernel"] == kernel
                 if pieces:
                     with pytest.raises(ValueError, match="beyond the uploaded mask"):

@@ -8,11 +8,10 @@
 * One diverging replica in a batch no longer voids the batch (rPSMF.py:236-243: NaN for that repeat, carry on).
 """
 
-import threading
-
 import numpy as np
 import pytest
 
+import netlib
 from conftest import relerr
 from oracle.impute_oracle import impute_filter
 from rpsmf_amd import impute
@@ -96,7 +95,6 @@ def test_masked_engine_two_shards_on_one_gpu(robust):
     """cfg.masked on two row shards (uneven), host communicator: gathered C, y_hat, summed metrics = the unsharded handle and the
     oracle; replicated V, P, mu, X bit-identical across the shards; message sizes r^2 + 1 and r + 1 per step (the Gram one step ahead)."""
     from rpsmf_amd import _capi as c
-    from test_hip_multishard import HostGroup
 
     d, n, r, nsh = 2001, 50, 20, 2
     Yorig, M, Mmiss, C0, X0 = _problem(d, n, r, 11)
@@ -117,26 +115,16 @@ def test_masked_engine_two_shards_on_one_gpu(robust):
     f = c.DeviceFilter(d, r, **kw)
     whole = run(f, 0, d)
     f.close()
-    grp = HostGroup(nsh)
-    out, errs = [None] * nsh, []
 
-    def worker(rank):
-        try:
-            row0, dl = shard_rows(d, nsh, rank)
-            g = c.DeviceFilter(d, r, row0=row0, d_local=dl, **kw)
-            g.comm_init_host(nsh, rank, grp.allreduce(rank))
-            out[rank] = run(g, row0, dl)
-            g.close()
-        except BaseException as e:      # noqa: BLE001
-            errs.append((rank, e))
-            grp.barrier.abort()
+    def worker(rank, comm):
+        row0, dl = shard_rows(d, nsh, rank)
+        g = c.DeviceFilter(d, r, row0=row0, d_local=dl, **kw)
+        g.comm_init_host(*comm)
+        out = run(g, row0, dl)
+        g.close()
+        return out
 
-    th = [threading.Thread(target=worker, args=(k,)) for k in range(nsh)]
-    for t in th:
-        t.start()
-    for t in th:
-        t.join(200)
-    assert not any(t.is_alive() for t in th) and not errs, errs
+    grp, out = netlib.run_ranks(nsh, worker, 200)
     for key in ("V", "P", "mu"):
         assert np.array_equal(out[0]["s"][key], out[1]["s"][key]), key          # replicated state: same bits on every shard
     assert np.array_equal(out[0]["X"], out[1]["X"])

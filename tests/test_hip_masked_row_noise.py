@@ -12,34 +12,18 @@ coverage exactly, float32 storage 1e-5 and the coverage within 5e-4, sharded aga
 Reference: ExperimentImpute/PSMF.py:40-95 (70-72), rPSMF.py:40-148 (91-98), MLESMF.py:40-92 (70-76)."""
 
 import os
-import threading
-from contextlib import contextmanager
 
 import numpy as np
 import pytest
 
 import gram_cases as GC
 import masked_noise_cases as MC
+import netlib
 from conftest import relerr
-from host_group import HostGroup
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(120)]
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "masked_uniform_parent.npz")
-
-
-@contextmanager
-def _env(vars_):
-    old = {k: os.environ.get(k) for k in vars_}
-    os.environ.update(vars_)
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 def _gam(ep):
@@ -124,22 +108,7 @@ def test_two_uneven_shards(method):
     whole = run_handle(c, cs, pb)
     shards = (1207, 794)
     row0 = (0, shards[0])
-    grp = HostGroup(2)
-    out, errs = [None, None], []
-
-    def worker(rank):
-        try:
-            out[rank] = run_handle(c, cs, pb, row0[rank], shards[rank], (2, rank, grp.allreduce(rank)))
-        except BaseException as e:      # noqa: BLE001
-            errs.append((rank, e))
-            grp.barrier.abort()
-
-    th = [threading.Thread(target=worker, args=(k,)) for k in range(2)]
-    for t in th:
-        t.start()
-    for t in th:
-        t.join(100)
-    assert not any(t.is_alive() for t in th) and not errs, errs
+    grp, out = netlib.run_ranks(2, lambda rank, comm: run_handle(c, cs, pb, row0[rank], shards[rank], comm), 100)
     for k in ("V", "P", "mu"):
         assert np.array_equal(out[0]["s"][k], out[1]["s"][k]), k
     assert np.array_equal(out[0]["X"], out[1]["X"]) and np.array_equal(out[0]["sc"], out[1]["sc"])
@@ -203,7 +172,7 @@ def test_equal_entries_agree_with_the_uniform_handle(method):
 
     cs = MC.find(700, 3, method)
     pb, _ = MC.reference(cs)
-    with _env({"PSMF_STEP_PERSISTENT": "0"}):          # the uniform handle on the launched form too: the same sweep and serial stage
+    with netlib.env({"PSMF_STEP_PERSISTENT": "0"}):          # the uniform handle on the launched form too: the same sweep and serial stage
         uni = run_handle(c, cs, pb, rho_rows=None, rho=10.0)
     row = run_handle(c, cs, pb, rho_rows=np.full(cs["d"], 10.0), rho=1.0)
     errs = [(k, relerr(row["s"][k], uni["s"][k]), GC.SHARD_BAR) for k in ("C", "P")] + [(k, relerr(row[k], uni[k]), GC.SHARD_BAR) for k in ("X", "yp", "sc")]
@@ -243,7 +212,7 @@ def test_graph_capture_and_tail_reduce_variants():
     pb, ref = MC.reference(cs)
     got = []
     for v in ("0", "1"):
-        with _env({"PSMF_TAIL_REDUCE": v}):
+        with netlib.env({"PSMF_TAIL_REDUCE": v}):
             got.append(run_handle(c, cs, pb))
     errs = [(k, relerr(got[1]["s"][k], got[0]["s"][k]), GC.SHARD_BAR) for k in ("C", "V", "P")] + [(k, relerr(got[1][k], got[0][k]), GC.SHARD_BAR) for k in ("X", "yp", "sc")]
     for v, g in zip("01", got):
@@ -260,7 +229,7 @@ def test_refusals_by_message():
     rng = np.random.default_rng(4)
     with pytest.raises(ValueError, match=r"TMF\) ignores R"):
         c.DeviceFilter(d, r, storage="f64", masked=3, nonuniform_R=True, engine="step")
-    with _env({"PSMF_WGRAM_MFMA": "0"}):
+    with netlib.env({"PSMF_WGRAM_MFMA": "0"}):
         with pytest.raises(ValueError, match="PSMF_WGRAM_MFMA=0.*no masked form"):
             c.DeviceFilter(d, r, storage="f64", masked=1, nonuniform_R=True, engine="step")
         c.DeviceFilter(d, r, storage="f64", nonuniform_R=True, engine="step").close()          # the unmasked twin exists
@@ -288,7 +257,7 @@ def uniform_parent_runs(c):
     pb = MC.problem(cs)
     out = {}
     for name, env in (("default", {}), ("launched", {"PSMF_STEP_PERSISTENT": "0"})):
-        with _env(env):
+        with netlib.env(env):
             d, n, r = cs["d"], cs["n"], cs["r"]
             f = c.DeviceFilter(d, r, storage="f64", masked=True, engine="step")
             try:

@@ -9,32 +9,21 @@ within 1e-5 of the oracle and within 2e-6 of each other -- the shard boundaries 
 the replicated V, P, mu, rho, lambda are BIT-IDENTICAL across shards; everything agrees with the CPU oracle.
 """
 
-import os
-import threading
-
 import numpy as np
 import pytest
 
+import netlib
 from conftest import relerr
-from host_group import HostGroup
 from oracle import psmf_oracle as O
 from rpsmf_amd.sharding import shard_rows
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(240)]
 
 
-def _capi():
-    from rpsmf_amd import _capi
-
-    return _capi
-
-
 def _run(c, nshards, d, r, Y, C0, st0, T, *, engine, storage, robust, env=None, extra=None, theta=None, want_kernel=None):
     """nshards = 0: plain unsharded handle.  Returns (per-shard get_state dicts, per-shard y_pred, group).
     `extra`: further DeviceFilter keywords (dynamics kind, hook configuration), `theta` its parameters."""
-    old = {k: os.environ.get(k) for k in (env or {})}
-    os.environ.update(env or {})
-    try:
+    with netlib.env(env or {}):
         kw = dict(storage=storage, engine=engine, robust=robust, **(extra or {}))
         skw = dict(rho=1.0, lambda0=1.8) if theta is None else dict(rho=1.0, lambda0=1.8, theta=theta)
         if nshards == 0:
@@ -48,41 +37,23 @@ def _run(c, nshards, d, r, Y, C0, st0, T, *, engine, storage, robust, env=None, 
             out = [f.get_state()], [f.y_pred(0, T)], None
             f.close()
             return out
-        grp = HostGroup(nshards)
-        states, yps, errs = [None] * nshards, [None] * nshards, []
 
-        def worker(rank):
-            try:
-                row0, dl = shard_rows(d, nshards, rank)
-                f = c.DeviceFilter(d, r, row0=row0, d_local=dl, **kw)
-                f.comm_init_host(nshards, rank, grp.allreduce(rank))
-                f.upload_series(np.ascontiguousarray(Y[:, row0:row0 + dl]))
-                f.set_state(C0[row0:row0 + dl], *st0, **skw)
-                if want_kernel:
-                    assert f.geometry()["filter_kernel"] == want_kernel, f.geometry()
-                f.run(0, T // 2)                # two runs: the state carried between runs is sharded state too
-                f.run(T // 2, T)
-                states[rank] = f.get_state()
-                yps[rank] = f.y_pred(0, T)
-                f.close()
-            except BaseException as e:          # noqa: BLE001 -- reported by the main thread
-                errs.append((rank, e))
-                grp.barrier.abort()
+        def worker(rank, comm):
+            row0, dl = shard_rows(d, nshards, rank)
+            f = c.DeviceFilter(d, r, row0=row0, d_local=dl, **kw)
+            f.comm_init_host(*comm)
+            f.upload_series(np.ascontiguousarray(Y[:, row0:row0 + dl]))
+            f.set_state(C0[row0:row0 + dl], *st0, **skw)
+            if want_kernel:
+                assert f.geometry()["filter_kernel"] == want_kernel, f.geometry()
+            f.run(0, T // 2)                # two runs: the state carried between runs is sharded state too
+            f.run(T // 2, T)
+            out = f.get_state(), f.y_pred(0, T)
+            f.close()
+            return out
 
-        threads = [threading.Thread(target=worker, args=(k,)) for k in range(nshards)]
-        for t in threads:
-            t.start()
-        for t in threads:
-            t.join(150)
-        assert not any(t.is_alive() for t in threads), "a shard thread is stuck"
-        assert not errs, errs
-        return states, yps, grp
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
+        grp, out = netlib.run_ranks(nshards, worker, 150)
+        return [s for s, _ in out], [y for _, y in out], grp
 
 
 CASES = [
@@ -112,7 +83,7 @@ CASES = [
 @pytest.mark.parametrize("robust", [False, True], ids=["PSMF", "rPSMF"])
 @pytest.mark.parametrize("engine,storage,d,r,T,nshards,env", CASES)
 def test_shards_on_one_gpu_equal_unsharded(engine, storage, d, r, T, nshards, env, robust):
-    c = _capi()
+    c = netlib.capi()
     Y = O.synthetic_series(d, r, T, 900 + d + r, noise="t" if robust else "normal", dtype=np.float64)
     rng = np.random.default_rng(d + r)
     C0 = 0.1 * rng.standard_normal((d, r))
@@ -164,7 +135,7 @@ DYN_CASES = [
 def test_shards_of_the_diagonal_dynamics_kernels_equal_unsharded(name, extra, kernel, r, T, tol, robust):
     """psmf_blk_filter4 / psmf_blk_filter5 / psmf_blk_filter6 under a host communicator: the cross-Gram K of every block is summed over the
     shards, theta and the gradient sum are replicated (bit-identical), the gathered C and y_hat equal the unsharded run."""
-    c = _capi()
+    c = netlib.capi()
     d = 3001
     kind = c.DYN_FOURIER if extra.get("dyn_kind") == "fourier" else c.DYN_COS_PHASE
     extra = dict(extra, dyn_kind=kind)
@@ -190,7 +161,7 @@ def test_shards_of_the_diagonal_dynamics_kernels_equal_unsharded(name, extra, ke
 def test_missing_reduction_would_be_caught():
     """The test above is only worth something if a shard that skips the exchange gives a different answer: run the
     shards with an identity 'all-reduce' and check that the result is wrong."""
-    c = _capi()
+    c = netlib.capi()
     d, r, T = 2000, 32, 100
     Y = O.synthetic_series(d, r, T, 31, dtype=np.float64)
     C0 = 0.1 * np.random.default_rng(1).standard_normal((d, r))

@@ -14,27 +14,19 @@ the error figures (each prints before it asserts).
 8. A launched per-step handle with chunks above 256 steps: the captured graph is rebuilt with every chunk's window.
 Reference: pypsmf/psmf/psmf.py:85-102 (step consumes one observation after the other and never looks back)."""
 
-import threading
-
 import numpy as np
 import pytest
 
 import blocked_cases as BC
+import netlib
 import ring_cases as RC
 from conftest import relerr
-from host_group import HostGroup
 from rpsmf_amd.sharding import shard_rows
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(240)]
 
 STATE_KEYS = ("C", "V", "P", "Q", "mu", "theta", "gradsum")
 SCALARS = ("rho", "lam", "s", "eta", "N", "phi", "omega", "k")
-
-
-def _capi():
-    from rpsmf_amd import _capi
-
-    return _capi
 
 
 def _handle(c, cs, pb, ring, row0=0, dl=None, comm=None, storage=None):
@@ -132,7 +124,7 @@ def _runs(i):
         cs = RC.CASES[i]
         try:
             pb = RC.problem(cs)
-            _RUNS[i] = (_run_resident(_capi(), cs, pb), _run_ring(_capi(), cs, pb), RC.reference(cs, pb))
+            _RUNS[i] = (_run_resident(netlib.capi(), cs, pb), _run_ring(netlib.capi(), cs, pb), RC.reference(cs, pb))
         except BaseException as e:      # noqa: BLE001
             _RUNS[i] = e
     if isinstance(_RUNS[i], BaseException):
@@ -171,7 +163,7 @@ def test_ring_run_against_the_oracle(i):
 
 def test_residency_is_enforced_on_the_host():
     """Nothing here reaches the device with an index outside a slot: every case is refused by the library's host code."""
-    c = _capi()
+    c = netlib.capi()
     cs = RC.CASES[0]
     pb = RC.problem(cs)
     ch, n, d = cs["chunk"], cs["n_slots"], cs["d"]
@@ -250,7 +242,7 @@ def test_a_stream_of_the_other_dtype_is_converted_as_numpy_does(storage, d, chun
     beforehand; and the y_hat downloads in the other type (float32 storage read as float64 -- run_stream asked for float64 -- and float64
     storage read as float32) are numpy's cast of the stored rows.  37 x 257 rows start at odd elements (scalar head, vector body,
     scalar tail of psmf_cast_rows); d = 1 leaves chunks without a vector body; d = 4 is all body."""
-    c = _capi()
+    c = netlib.capi()
     cs = dict(RC.CASES[0], d=d, chunk=chunk, T=(RC.N_CHUNKS - 1) * chunk + chunk // 2 + 2, storage=storage)
     pb = RC.problem(dict(cs, storage="f64"))          # float64 values that float32 has to round
     if storage == "f64":
@@ -269,28 +261,17 @@ def test_a_stream_of_the_other_dtype_is_converted_as_numpy_does(storage, d, chun
 
 
 def test_two_row_shards_each_with_its_ring():
-    c = _capi()
+    c = netlib.capi()
     cs = dict(RC.CASES[0], name="two shards", r=12, storage="f64", kernel="psmf_blk_filter6d")
     pb = RC.problem(cs)
     whole = _run_ring(c, cs, pb)
     nsh = 2
-    grp = HostGroup(nsh)
-    out, errs = [None] * nsh, []
 
-    def worker(rank):
-        try:
-            row0, dl = shard_rows(cs["d"], nsh, rank)
-            out[rank] = _run_ring(c, cs, pb, row0=row0, dl=dl, comm=(nsh, rank, grp.allreduce(rank)))
-        except BaseException as e:      # noqa: BLE001 -- reported by the main thread
-            errs.append((rank, e))
-            grp.barrier.abort()
+    def worker(rank, comm):
+        row0, dl = shard_rows(cs["d"], nsh, rank)
+        return _run_ring(c, cs, pb, row0=row0, dl=dl, comm=comm)
 
-    th = [threading.Thread(target=worker, args=(k,)) for k in range(nsh)]
-    for t in th:
-        t.start()
-    for t in th:
-        t.join(150)
-    assert not any(t.is_alive() for t in th) and not errs, errs
+    _, out = netlib.run_ranks(nsh, worker, 150)
     for k in ("V", "P", "mu", "Q", "rho", "lam"):
         assert np.array_equal(np.asarray(out[0]["state"][k]), np.asarray(out[1]["state"][k])), k
     for a, b in zip(out[0]["recs"], out[1]["recs"]):
@@ -361,7 +342,7 @@ def test_masked_metrics_of_resident_chunks_while_later_runs_are_queued():
     """psmf_masked_metrics reads the live C for its second sum, so on a ring handle it waits for the compute stream: taken right
     after runs were queued without a sync, the four sums are those of a resident handle run to the same step and asked for the
     same chunks -- bit for bit (the same kernel over the same rows, partial sums added in a fixed order)."""
-    c = _capi()
+    c = netlib.capi()
     cs = next(x for x in RC.CASES if x["name"] == "masked persistent")
     pb = RC.problem(cs)
     ch, Y, M, sig = cs["chunk"], pb["Y"], pb["M"], 2.0
@@ -407,7 +388,7 @@ def test_launched_handle_with_chunks_above_the_graph_threshold():
     """The launched per-step engine captures its launches into a graph for runs of 256 steps and more, and the captured nodes
     carry the parameter block: with chunks of 260 steps every chunk rebuilds the graph with its own series_t0.  The bits of the
     resident handle cut at the same steps, and the oracle at the float64 bar."""
-    c = _capi()
+    c = netlib.capi()
     cs = RC.GRAPH_CASE
     pb = RC.problem(cs)
     res, ring, ref = _run_resident(c, cs, pb), _run_ring(c, cs, pb), RC.reference(cs, pb)

@@ -24,8 +24,9 @@ import numpy as np
 import pytest
 
 import ring_cases as RC
+import netlib
 from conftest import relerr
-from test_hip_series_ring import STATE_KEYS, _capi, _handle
+from test_hip_series_ring import STATE_KEYS, _handle
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(120)]
 
@@ -62,7 +63,7 @@ _RUNS = {}
 def _runs(name):
     """what the resident handle and the ring answer, asked once for the tests that share it"""
     if name not in _RUNS:
-        c, cs = _capi(), CASES[name]
+        c, cs = netlib.capi(), CASES[name]
         pb = RC.problem(cs)
         held = ((np.random.default_rng(5).random((T, cs["d"])) < 0.3) & (pb["M"] == 0)).astype(np.uint8) if cs["masked"] else None
         res, ring = _handle(c, cs, pb, ring=False), _handle(c, cs, pb, ring=True)
@@ -114,7 +115,7 @@ def test_y_pred_in_the_other_dtype_is_numpys_cast(name):
 
 
 def test_a_resident_upload_of_the_other_dtype_in_two_blocks():
-    c, cs = _capi(), CASES["block f32"]
+    c, cs = netlib.capi(), CASES["block f32"]
     pb = RC.problem(cs)
     Y = pb["Y"]
     assert Y.dtype == np.float64 and Y.shape == (T, cs["d"])

@@ -8,17 +8,12 @@ import os
 import numpy as np
 import pytest
 
+import netlib
 from conftest import relerr
 from oracle import psmf_oracle as O
 from rpsmf_amd import nonlinearities as NL
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(300)]
-
-
-def _capi():
-    from rpsmf_amd import _capi
-
-    return _capi
 
 
 def _theta_for(nl, rng, r):
@@ -70,7 +65,7 @@ MODES = {"full": FULL, "no_update": dict(coef_update=False, eta_full=True, pbar_
 @pytest.mark.parametrize("r", [1, 2, 5, 10, 13, 14, 15, 16])
 @pytest.mark.parametrize("name,make", KINDS, ids=[k[0] for k in KINDS])
 def test_small_rank_kinds_vs_oracle(name, make, r, robust):
-    c = _capi()
+    c = netlib.capi()
     d, T = 260, 70            # two blocks of 48: the second one ragged; and two runs (the state carried between launches)
     nl = make(r)
     rng = np.random.default_rng(100 * r + len(name))
@@ -99,7 +94,7 @@ def test_small_rank_kinds_vs_oracle(name, make, r, robust):
 @pytest.mark.parametrize("name,make", [KINDS[1], KINDS[7], KINDS[5]], ids=["scaled_walk_bias", "fourier2", "cos_phase"])
 def test_small_rank_hook_configurations(name, make, mode):
     """The reference's hook overrides one at a time (no coefficient update / eta = tr R / d / P_bar = P), r = 9 (odd)."""
-    c = _capi()
+    c = netlib.capi()
     d, r, T = 260, 9, 60
     nl = make(r)
     rng = np.random.default_rng(3)
@@ -120,7 +115,7 @@ def test_small_rank_hook_configurations(name, make, mode):
 def test_small_rank_schedules_with_a_dense_jacobian_and_vs_general_kernel():
     """R_k, Q_k schedules (psmf.py:115,123,141) with FourierBasis dynamics, against the oracle; and the same run on the general
     one-group kernel (PSMF_FILTER6=0): the two kernels agree to round-off."""
-    c = _capi()
+    c = netlib.capi()
     d, r, T = 300, 10, 96
     nl = NL.FourierBasis(r, N=2)
     rng = np.random.default_rng(5)
@@ -153,7 +148,7 @@ def test_small_rank_random_walk_inversions_side_by_side(r, robust):
     """The default model (random walk, Q = q I) at r <= 14 on psmf_blk_filter6d with W_k = (M_k / beta + I / q_k)^-1 formed beside
     P+_k = M_k^-1 (one sweep on the path of a step instead of two); rPSMF: q, rho, lambda run with omega.  And the same run with
     PSMF_FILTER6_DUAL=0 (filter3s): the two kernels agree."""
-    c = _capi()
+    c = netlib.capi()
     d, T = 260, 130           # three blocks, the last one ragged; two runs
     nl = NL.RandomWalk()
     rng = np.random.default_rng(40 + r)

@@ -5,30 +5,14 @@ test_hip_small_rank.py, PSMF_IMPUTE_V3 in test_hip_impute_small.py, PSMF_NS_PRED
 test_hip_filter.py, PSMF_BLOCK_PIPE / PSMF_FILTER3 with several shards in test_hip_multishard.py.)  GPU only: `pytest -m gpu`.
 Reference: pypsmf/psmf/psmf.py:85-165, rpsmf.py:116-171 (one code path; every variant here must reproduce it)."""
 
-import os
-from contextlib import contextmanager
-
 import numpy as np
 import pytest
 
+import netlib
 from conftest import relerr
 from oracle import psmf_oracle as O
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(600)]
-
-
-@contextmanager
-def _env(vars_):
-    old = {k: os.environ.get(k) for k in vars_}
-    os.environ.update(vars_)
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 def _problem(d, r, T, robust, seed, f32):
@@ -89,7 +73,7 @@ def test_switch_reproduces_the_oracle(case):
     V0, P0, Q = 0.1 * np.eye(r), np.eye(r), 0.1 * np.eye(r)
     st = O.State(C=C0, V=V0, mu=np.zeros(r), P=P0, Q=Q, rho=1.0, lam=1.8)
     cut = T // 3
-    with _env(env):
+    with netlib.env(env):
         f = c.DeviceFilter(d, r, storage=storage, robust=robust, engine=engine)
         if sched:          # constant schedules: the oracle's arithmetic is the unscheduled one, the device takes the scheduled kernels
             f.set_schedules(np.ones(T + 1), np.ones(T + 1))
@@ -115,7 +99,7 @@ def test_two_launch_engine_graph_and_eager_agree_bitwise():
     d, r, T = 3000, 16, 300
     Y, C0 = _problem(d, r, T, False, 77, False)
     outs = []
-    with _env({"PSMF_STEP_PERSISTENT": "0"}):
+    with netlib.env({"PSMF_STEP_PERSISTENT": "0"}):
         for graph in (True, False):
             f = c.DeviceFilter(d, r, storage="f64", engine="step", use_graph=graph)
             f.upload_series(Y)
@@ -174,7 +158,7 @@ def test_weighted_gram_of_a_nonuniform_R_both_kernels(wgram, r):
         V0, P0, Q = 0.1 * np.eye(r), np.eye(r), 0.1 * np.eye(r)
         st = O.State(C=C0, V=V0, mu=np.zeros(r), P=P0, Q=Q, rho=rho, lam=1.8)
         st, Yp, _ = O.run_epoch(st, Y, O.Mode(robust=True), O.RandomWalkDyn(), want_grad=False)
-        with _env({"PSMF_WGRAM_MFMA": wgram}):
+        with netlib.env({"PSMF_WGRAM_MFMA": wgram}):
             f = c.DeviceFilter(d, r, storage=storage, robust=True, engine="step", nonuniform_R=True)
             f.set_row_noise(rho)
             f.upload_series(Y)

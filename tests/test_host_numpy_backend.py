@@ -5,12 +5,9 @@ experiment scripts: same constructors, same run/step/predict/adam calls."""
 import numpy as np
 import pytest
 
+import netlib
 from conftest import load_golden, relerr
 import rpsmf_amd as psmf
-
-
-def ydict(Y):
-    return {k + 1: Y[k][:, None].copy() for k in range(Y.shape[0])}
 
 
 @pytest.mark.parametrize("name,robust", [("psmf_full_rw", False), ("rpsmf_full_rw", True)])
@@ -28,9 +25,9 @@ def test_full_filter_classes(name, robust):
         f = psmf.PSMFIter(theta0, g["C0"], g["V0"], mu0, g["P0"], {k: g["Q"] for k in range(T + 1)},
                           {k: np.eye(d) for k in range(T + 1)}, psmf.RandomWalk(), backend="numpy")
     f.optim_init()
-    f.step(ydict(Y), 1, T)
+    f.step(netlib.ydict(Y), 1, T)
     f.optim_update(1)
-    f.step(ydict(Y), 2, T)
+    f.step(netlib.ydict(Y), 2, T)
     assert relerr(f._C[T], g["s_e2_k200_C"]) < 1e-10
     assert relerr(f._V[T], g["s_e2_k200_V"]) < 1e-10
     assert relerr(f._mu[T], g["s_e2_k200_mu"]) < 1e-10
@@ -92,7 +89,7 @@ def test_experiment_synthetic_subclass_with_plain_callable(name, robust):
     g = load_golden(name)
     T, n_pred, n_iter = int(g["T"]), int(g["n_pred"]), int(g["n_iter"])
     d, r = g["C0"].shape
-    y_obs = ydict(g["Y_obs"])
+    y_obs = netlib.ydict(g["Y_obs"])
     y_train = {k: y_obs[k] for k in range(1, T + 1)}
     theta0, mu0 = g["theta0"].reshape(-1, 1), g["mu0"].reshape(-1, 1)
     if robust:
@@ -127,7 +124,7 @@ def test_fourier_basis_beijing_configuration():
                       {k: g["Q"] for k in range(T + 1)}, {k: np.eye(d) for k in range(T + 1)}, nl, backend="numpy")
     f.adam_init(gam=1e-3)
     for i in range(1, n_iter + 1):
-        f.step(ydict(Y[:T]), i, T)
+        f.step(netlib.ydict(Y[:T]), i, T)
         f.predict(i, T, n_pred)
         f.adam_update(i, project=True)
     theta = np.array([f._theta[i].reshape(-1) for i in range(n_iter + 1)])
@@ -147,7 +144,7 @@ def test_recursive_classes(name, robust):
     else:
         f = psmf.PSMFRecursive(theta0, g["C0"], g["V0"], mu0, g["P0"], {k: g["Q"] for k in range(T + 1)},
                                {k: np.eye(d) for k in range(T + 1)}, cos_nl, backend="numpy")
-    f.run(ydict(g["Y"]), T, n_pred, update_every=ue)
+    f.run(netlib.ydict(g["Y"]), T, n_pred, update_every=ue)
     theta = np.array([f._theta[k].reshape(-1) for k in range(T + 1)])
     assert relerr(theta, g["theta"]) < 1e-6
     assert relerr(f._C[T], g["C_T"]) < 1e-7
@@ -167,7 +164,7 @@ def test_scalar_and_vector_R_equal_dense_R():
                           {k: 0.1 * np.eye(r) for k in range(T + 1)}, {k: R for k in range(T + 1)},
                           psmf.RandomWalk(), backend="numpy")
         f.optim_init()
-        f.step(ydict(Y), 1, T)
+        f.step(netlib.ydict(Y), 1, T)
         outs.append((f._C[T], f._P[T], f._mu[T]))
     for a, b in zip(*outs):
         assert relerr(a, b) < 1e-12
@@ -187,7 +184,7 @@ def test_compute_scaling_factor_matches_reference():
     f = mk(1.8, use_scaling=True)
     assert abs(f._alpha - float(g["alpha"])) < 1e-12 and abs(f._beta - float(g["beta"])) < 1e-12
     f.optim_init()
-    f.step(ydict(Y), 1, T)
+    f.step(netlib.ydict(Y), 1, T)
     assert relerr(f._C[T], g["C_T"]) < 1e-10 and relerr(f._V[T], g["V_T"]) < 1e-10
     assert relerr(f._mu[T], g["mu_T"].reshape(-1, 1)) < 1e-10 and relerr(f._P[T], g["P_T"]) < 1e-10
 
@@ -204,7 +201,7 @@ def test_rpsmf_vector_R0_equals_dense_R0():
         f = psmf.rPSMFIter(np.zeros((0, 1)), C0, 0.2 * np.eye(r), np.zeros((r, 1)), np.eye(r), 0.1 * np.eye(r), R0, 1.8,
                            psmf.RandomWalk(), backend="numpy")
         f.optim_init()
-        f.step(ydict(Y), 1, T)
+        f.step(netlib.ydict(Y), 1, T)
         outs.append((f._C[T], f._P[T], f._V[T], f._mu[T]))
         assert np.shape(f._R[T]) == np.shape(R0)
     for o in outs[1:]:
@@ -214,7 +211,7 @@ def test_rpsmf_vector_R0_equals_dense_R0():
         f = psmf.rPSMFIter(np.zeros((0, 1)), C0, 0.2 * np.eye(r), np.zeros((r, 1)), np.eye(r), 0.1 * np.eye(r), np.ones(d + 1), 1.8,
                            psmf.RandomWalk(), backend="numpy")
         f.optim_init()
-        f.step(ydict(Y), 1, T)
+        f.step(netlib.ydict(Y), 1, T)
 
 
 def test_array_series_is_indexed_like_the_dict():
@@ -224,7 +221,7 @@ def test_array_series_is_indexed_like_the_dict():
     Y = rng.standard_normal((T, d))
     C0 = rng.standard_normal((d, r))
     outs = []
-    for y in (ydict(Y), np.vstack([np.full((1, d), np.nan), Y])):
+    for y in (netlib.ydict(Y), np.vstack([np.full((1, d), np.nan), Y])):
         f = psmf.PSMFIter(np.zeros((0, 1)), C0, 0.2 * np.eye(r), np.zeros((r, 1)), np.eye(r),
                           {k: 0.1 * np.eye(r) for k in range(T + 1)}, {k: 1.0 for k in range(T + 1)}, psmf.RandomWalk(), backend="numpy")
         f.optim_init()
@@ -282,7 +279,7 @@ def test_builtin_nonlinearities_numpy_backend_gradients():
             f = psmf.PSMFIter(theta0, C0, 0.2 * np.eye(r), np.zeros((r, 1)), np.eye(r), {k: 0.1 * np.eye(r) for k in range(T + 1)},
                               {k: 1.0 for k in range(T + 1)}, fn, backend="numpy")
             f.optim_init()
-            f.step(ydict(Y), 1, T)
+            f.step(netlib.ydict(Y), 1, T)
             outs.append((f._C[T], f._P[T], f._gradsum))
         for a, b in zip(*outs):
             assert relerr(a, b) < 1e-10
@@ -296,7 +293,7 @@ def test_tracking_mixin_host_path():
     rng = np.random.default_rng(8)
     d, r, T, n_pred = 9, 2, 12, 4
     Y = rng.standard_normal((T + n_pred, d))
-    y = ydict(Y)
+    y = netlib.ydict(Y)
     f = Tracked(np.zeros((0, 1)), rng.standard_normal((d, r)), 0.2 * np.eye(r), np.zeros((r, 1)), np.eye(r),
                 {k: 0.1 * np.eye(r) for k in range(T + 1)}, {k: 1.0 for k in range(T + 1)}, psmf.RandomWalk(), backend="numpy")
     f.optim_init()
