@@ -544,6 +544,57 @@ typedef struct {
 int psmf_bocpd_run(const psmf_bocpd_config* cfg, const double* X, int32_t* map_run, int32_t* changepoints, int32_t* n_changepoints,
                    double* R_last, double* R, double* logpred, int32_t* status, float* elapsed_ms);
 
+/* Batched probabilistic matrix factorisation: the PMF baseline of the imputation experiment (ExperimentImpute/PMF.py:43-159, mini-batch
+ * gradient descent with momentum on the observed entries), float64 throughout, for a batch of independent replicas. */
+typedef struct {
+  int32_t abi_version;
+  int32_t d, n, r;         /* Y is d x n, the factors have r features: 1 <= d <= 512, 1 <= r <= 16, n unlimited     */
+  int32_t batch;           /* independent replicas                                                               */
+  int32_t epochs;          /* passes over the training set, >= 1 (the reference: 2)                              */
+  int32_t num_batches;     /* mini-batches of an epoch, 1 .. 254 (the reference: 9)                              */
+  int32_t device;
+  int32_t want_rec;        /* also return the reconstruction at the probe entries after the last epoch           */
+  double epsilon;          /* learning rate (the reference: 50)                                                  */
+  double lambda;           /* weight of the quadratic penalty (the reference: 0.01)                              */
+  double momentum;         /* (the reference: 0.8)                                                               */
+} psmf_pmf_config;
+
+/* Per replica, with T = {(i, j): M_ij = 1} the training entries and N = |T|:
+ *   mu = mean over T of y_ij,  v_ij = (y_ij - mu) / mu  (the reference divides by the mean),  mbar = mean over T of v_ij
+ *   P = 0.1 C0 (d x r),  W = 0.1 X0^T (n x r),  incP = incW = 0                      -- formed by the caller
+ *   per epoch the entries of T are dealt to num_batches batches (a random permutation cut as numpy.array_split cuts it); per batch b
+ *   with N_b entries, everything from the W, P at the start of the batch:
+ *     g_ij = 2 (w_j . p_i - (v_ij - mbar))                               for (i, j) in the batch
+ *     dW_j = sum_i g_ij p_i + lambda c_j w_j,   dP_i = sum_j g_ij w_j + lambda c_i p_i,   c_j, c_i = batch entries of column j / row i
+ *     incW = momentum incW + epsilon dW / N_b,  W -= incW;   incP = momentum incP + epsilon dP / N_b,  P -= incP
+ *   (a column or row without an entry in the batch still moves by its momentum), and at the end of epoch e over the probe entries
+ *   (Mmiss_ij = 1):   yhat_ij = (w_j . p_i + mbar) mu + mu,   Efull[e] = sqrt(sum (yhat_ij - y_ij)^2 / sum Mmiss)
+ * The caller states the dealing as a BATCH MAP per replica and epoch: n x d bytes, time-major, the batch index of a training entry
+ * and 255 elsewhere -- the order inside a batch only orders sums -- and hands over mu and mbar, so that they carry the bits of the
+ * host's summation.  The three products of a batch (W P^T, G P, G^T W) run on the float64 matrix cores, a workgroup per range of
+ * columns with P in LDS; W and incW are updated in place, the d x r sum dP crosses workgroups through partial sums that a second
+ * kernel adds in a fixed order.  No atomics: the same call twice gives the same bits.  A batch whose maps and factors exceed what is
+ * free on the device is processed in chunks of replicas.
+ *   Y             n x d, time-major: the data, read at the training and the probe entries (shared by the replicas)
+ *   maps          batch x epochs x n x d bytes
+ *   Mmiss         batch x n x d bytes, nonzero = probe entry
+ *   batch_sizes   batch x num_batches: N_b, every one >= 1
+ *   row_counts    batch x epochs x num_batches x d: c_i of every batch
+ *   mean, mean_rating   batch: mu (not 0) and mbar
+ *   P             batch x d x r, in: 0.1 C0, out: the final P
+ *   W             batch x n x r, in: 0.1 X0^T, out: the final W
+ *   Efull         batch x epochs
+ *   Yrec          batch x n x d, time-major, yhat at the probe entries after the last epoch and 0 elsewhere; want_rec = 1, else NULL
+ *   status        batch int32 or NULL, as in psmf_ssm_run: PSMF_OK, or PSMF_ERR_NUMERIC for a replica whose factors or errors are
+ *                 not finite (the steps diverged); the other replicas are untouched by it.  With status = NULL such a replica
+ *                 fails the call (PSMF_ERR_NUMERIC)
+ *   elapsed_ms    the kernels alone (HIP events, summed over the chunks), or NULL
+ * PSMF_ERR_ARG, by message: d > 512, r > 16, num_batches outside 1 .. 254, an empty batch, a zero mean.  PSMF_PMF_COLS=n sets the
+ * columns per workgroup, PSMF_PMF_CHUNK=n caps the replicas per chunk (both read at every call). */
+int psmf_pmf_run(const psmf_pmf_config* cfg, const double* Y, const uint8_t* maps, const uint8_t* Mmiss, const int32_t* batch_sizes,
+                 const int32_t* row_counts, const double* mean, const double* mean_rating, double* P, double* W, double* Efull,
+                 double* Yrec, int32_t* status, float* elapsed_ms);
+
 #ifdef __cplusplus
 }
 #endif

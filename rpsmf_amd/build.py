@@ -6,9 +6,10 @@
 The library is a handful of translation units, compiled side by side (at most 16 at a time) and linked: the C ABI with the launched
 per-step engine (psmf_capi.hip), the series buffers -- resident or a ring: uploads, downloads, reductions over stored rows --
 (psmf_series.hip), the blocked engine's host driver and kernels (psmf_blocked.hip), the filter3 family of block filters
-(psmf_filter34.hip), the persistent per-step engine (psmf_pstep.hip), the three units of the entry points without a handle, host side on
+(psmf_filter34.hip), the persistent per-step engine (psmf_pstep.hip), the four units of the entry points without a handle, host side on
 psmf_batch.h -- the masked small-shape engine with its route to the large-d handle (psmf_impute.hip), the batched filter with linear-Gaussian
-dynamics and an observation map (psmf_ssm.hip), the batched Bayesian online change-point detection (psmf_bocpd.hip) --
+dynamics and an observation map (psmf_ssm.hip), the batched Bayesian online change-point detection (psmf_bocpd.hip), the batched
+probabilistic matrix factorisation (psmf_pmf.hip) --
 and the build identity (psmf_buildid.cpp: `psmf_build_id()` returns the SHA-256 of every source file and of the compiler flags the library was built
 from).  An object is stale when the hash of what its source reaches through `#include "..."`, followed transitively, differs from the one
 it was compiled from -- no list of dependencies is kept by hand.  `build_library` rebuilds whenever the whole-library hash differs from
@@ -40,7 +41,7 @@ FLAGS += os.environ.get("PSMF_CXXFLAGS", "").split()      # diagnostic builds (e
 LINK = ["-L/opt/rocm/lib", "-lrccl", "-Wl,-rpath,/opt/rocm/lib"]
 
 UNITS = ("psmf_capi.hip", "psmf_series.hip", "psmf_blocked.hip", "psmf_filter34.hip", "psmf_impute.hip", "psmf_pstep.hip", "psmf_ssm.hip",
-         "psmf_bocpd.hip")
+         "psmf_bocpd.hip", "psmf_pmf.hip")
 MAX_JOBS = 16
 
 
