@@ -595,6 +595,61 @@ int psmf_pmf_run(const psmf_pmf_config* cfg, const double* Y, const uint8_t* map
                  const int32_t* row_counts, const double* mean, const double* mean_rating, double* P, double* W, double* Efull,
                  double* Yrec, int32_t* status, float* elapsed_ms);
 
+/* Batched Bayesian probabilistic matrix factorisation: the BPMF baseline of the imputation experiment (ExperimentImpute/BPMF.py:121-302,
+ * a Gibbs sampler over the factors and their Gaussian-Wishart hyper-parameters), float64 throughout, for a batch of independent
+ * replicas.  Every random number is drawn by the caller, up front: no draw of the sampler depends on the data. */
+typedef struct {
+  int32_t abi_version;
+  int32_t d, n, r;         /* Y is d x n, the factors have r features: 2 <= d <= 512, 2 <= r <= 16, n >= 2            */
+  int32_t batch;           /* independent replicas                                                               */
+  int32_t epochs;          /* Gibbs epochs, >= 1 (the reference: 2): a hyper-parameter step and two sweeps each  */
+  int32_t device;
+  int32_t want_rec;        /* also return the reconstruction at the probe entries after the last epoch           */
+  double beta;             /* observation precision (the reference: 2)                                           */
+} psmf_bpmf_config;
+
+/* Per replica, with T = {(i, j): M_ij != 0} the training entries, mu their mean, v_ij = (y_ij - mu) / mu (the reference divides by the
+ * mean), mbar the mean of v over T, and W (n x r), P (d x r) the factors of the warm start (psmf_pmf_run's recursion, BPMF.py:43-105):
+ *   avg_ij = w_j . p_i + mbar over the probe entries (Mmiss_ij != 0), c = 1
+ *   epoch e = 1 .. epochs:
+ *     for (F, N, A, z) = (W, n, A_m, z_m) and then (P, d, A_u, z_u), with b0 = 2:
+ *       xbar = column mean of F,   S = sum_k (f_k - xbar)(f_k - xbar)^T / (N - 1)                    (numpy.cov, two passes)
+ *       T = I + N S + N b0 / (b0 + N) xbar xbar^T = U U^T, U upper triangular, factored from the last row upwards
+ *       alpha = X X^T with U^T X = A       (U^-T is the lower Cholesky factor of T^-1: alpha is the reference's wishart.rvs(r + N,
+ *                                           sym(inv T)) where A is the standard Bartlett factor scipy draws for it)
+ *       (b0 + N) alpha = V V^T the same way,   mu_h = V^-1 z + N xbar / (b0 + N)                     (cholesky(inv(.)).T z + ...)
+ *     twice (the two Gibbs sweeps):
+ *       every column j:  Lambda = alpha_m + beta sum_i m_ij p_i p_i^T = U U^T,  b = beta sum_i m_ij (v_ij - mbar) p_i + alpha_m mu_m,
+ *                        w_j = U^-1 z_j + U^-T U^-1 b                            (cholesky(inv Lambda).T z_j + inv(Lambda) b)
+ *       every row i, likewise over its training entries with the new W, alpha_u, mu_u and its own z_i
+ *       (a column or row without a training entry has Lambda = alpha)
+ *     avg = (c avg + w_j . p_i + mbar) / (c + 1),  c += 1,   yhat_ij = avg_ij mu + mu,
+ *     Efull[e] = sqrt(sum over the probe entries of (yhat_ij - y_ij)^2 / their number)
+ * The reference's "simple fit" (BPMF.py:197-201) is overwritten before it is used and is not computed.  The two Grams of a sweep and
+ * the covariance of W run on the float64 matrix cores; the sums that cross workgroups are partial sums added in a fixed order.  No
+ * atomics: the same call twice gives the same bits, a replica the same bits alone as inside a batch.  A batch that exceeds what is
+ * free on the device is processed in chunks of replicas.
+ *   Y             n x d, time-major: the data, read at the training and the probe entries (shared by the replicas)
+ *   M, Mmiss      batch x n x d bytes each, nonzero = training entry / probe entry
+ *   mean, mean_rating   batch: mu (not 0) and mbar
+ *   bartlett      batch x epochs x 2 x r x r: A_m then A_u of every epoch, lower triangular (the diagonal: roots of chi-squares with
+ *                 r + N - i degrees of freedom, i = 0 .. r - 1; below it standard normals)
+ *   hyper_normals batch x epochs x 2 x r: z_m then z_u
+ *   normals       batch x epochs x 2 x (n + d) x r: per sweep the z_j of the columns (n x r), then the z_i of the rows (d x r)
+ *   P             batch x d x r, in: the warm start, out: the final P
+ *   W             batch x n x r, likewise
+ *   Efull         batch x epochs
+ *   Yrec          batch x n x d, time-major, yhat at the probe entries after the last epoch and 0 elsewhere; want_rec = 1, else NULL
+ *   status        batch int32 or NULL, as in psmf_pmf_run: PSMF_OK, or PSMF_ERR_NUMERIC for a replica in which a pivot of a factorisation
+ *                 was not positive (numpy.linalg.LinAlgError upstream) or whose factors or errors are not finite; the other replicas
+ *                 are untouched by it.  With status = NULL such a replica fails the call (PSMF_ERR_NUMERIC)
+ *   elapsed_ms    the kernels alone (HIP events, summed over the chunks), or NULL
+ * PSMF_ERR_ARG, by message: d outside 2 .. 512, r outside 2 .. 16, n < 2, a zero mean.  PSMF_BPMF_COLS=n sets the columns per
+ * workgroup, PSMF_BPMF_CHUNK=n caps the replicas per chunk (both read at every call). */
+int psmf_bpmf_run(const psmf_bpmf_config* cfg, const double* Y, const uint8_t* M, const uint8_t* Mmiss, const double* mean,
+                  const double* mean_rating, const double* bartlett, const double* hyper_normals, const double* normals, double* P,
+                  double* W, double* Efull, double* Yrec, int32_t* status, float* elapsed_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,6 +5,7 @@
     from rpsmf_amd.ssm import PSMF, rPSMF, linear_psmf_batch, matern32_state_space
     from rpsmf_amd.changepoint import MVBOCPD, mvbocpd_batch, find_changepoint
     from rpsmf_amd.pmf import pmf, pmf_batch
+    from rpsmf_amd.bpmf import bpmf, bpmf_batch, draw_bpmf
 
 The device path (backend="hip", default) needs rpsmf_amd/lib/libpsmf_hip.so
 (`python -m rpsmf_amd.build`) and a gfx950 GPU; it never falls back to the CPU.

@@ -9,7 +9,7 @@ per-step engine (psmf_capi.hip), the series buffers -- resident or a ring: uploa
 (psmf_filter34.hip), the persistent per-step engine (psmf_pstep.hip), the four units of the entry points without a handle, host side on
 psmf_batch.h -- the masked small-shape engine with its route to the large-d handle (psmf_impute.hip), the batched filter with linear-Gaussian
 dynamics and an observation map (psmf_ssm.hip), the batched Bayesian online change-point detection (psmf_bocpd.hip), the batched
-probabilistic matrix factorisation (psmf_pmf.hip) --
+probabilistic matrix factorisation (psmf_pmf.hip) and its Bayesian form, the Gibbs sampler (psmf_bpmf.hip) --
 and the build identity (psmf_buildid.cpp: `psmf_build_id()` returns the SHA-256 of every source file and of the compiler flags the library was built
 from).  An object is stale when the hash of what its source reaches through `#include "..."`, followed transitively, differs from the one
 it was compiled from -- no list of dependencies is kept by hand.  `build_library` rebuilds whenever the whole-library hash differs from
@@ -41,7 +41,7 @@ FLAGS += os.environ.get("PSMF_CXXFLAGS", "").split()      # diagnostic builds (e
 LINK = ["-L/opt/rocm/lib", "-lrccl", "-Wl,-rpath,/opt/rocm/lib"]
 
 UNITS = ("psmf_capi.hip", "psmf_series.hip", "psmf_blocked.hip", "psmf_filter34.hip", "psmf_impute.hip", "psmf_pstep.hip", "psmf_ssm.hip",
-         "psmf_bocpd.hip", "psmf_pmf.hip")
+         "psmf_bocpd.hip", "psmf_pmf.hip", "psmf_bpmf.hip")
 MAX_JOBS = 16
 
 

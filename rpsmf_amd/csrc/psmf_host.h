@@ -1,7 +1,7 @@
 // Host side of libpsmf_hip.so, shared by its translation units (psmf_capi.hip, psmf_series.hip, psmf_blocked.hip, psmf_filter34.hip,
-// psmf_impute.hip, psmf_ssm.hip, psmf_bocpd.hip, psmf_pmf.hip): the handle, the switch table, the error helpers and the few host functions that cross
+// psmf_impute.hip, psmf_ssm.hip, psmf_bocpd.hip, psmf_pmf.hip, psmf_bpmf.hip): the handle, the switch table, the error helpers and the few host functions that cross
 // unit boundaries.  A kernel is launched -- and its LDS opt-in is made -- only in the unit that defines it (the rule of psmf_pstep.h);
-// across units only these functions are called; the entry points without a handle (the last four units) stand on psmf_batch.h.
+// across units only these functions are called; the entry points without a handle (the last five units) stand on psmf_batch.h.
 #pragma once
 #include "../../include/psmf_hip.h"
 #include "psmf_block.h"       // BlockParams
@@ -30,7 +30,7 @@ struct Geometry {
 // Environment switches: one row each, and this struct is the library's only reader of the environment.  The rows
 // are read when a Switches is constructed: ONCE per handle, with the handle at psmf_create -- tests flip them between handles of one
 // process, and nothing on the per-block host path looks at the environment; the entry points without a handle (psmf_impute_*,
-// psmf_measure_copy_bandwidth, psmf_bocpd_run, psmf_pmf_run) construct one at entry, on every call.
+// psmf_measure_copy_bandwidth, psmf_bocpd_run, psmf_pmf_run, psmf_bpmf_run) construct one at entry, on every call.
 struct Switches {
   static bool set(const char* name) { return getenv(name) != nullptr; }                                  // present at all
   static bool on(const char* name) { const char* e = getenv(name); return e && atoi(e) != 0; }           // set and non-zero
@@ -74,6 +74,9 @@ struct Switches {
   // probabilistic matrix factorisation (psmf_pmf.hip)
   int pmf_cols = as_int("PSMF_PMF_COLS", 0);             // n > 0: columns per workgroup, rounded up to a multiple of 16 (0, unset: from n, at most 64 workgroups a replica)
   int pmf_chunk = as_int("PSMF_PMF_CHUNK", 0);           // n > 0: at most n replicas per chunk, still capped by free memory (0, unset: sized from free memory alone)
+  // Bayesian probabilistic matrix factorisation (psmf_bpmf.hip)
+  int bpmf_cols = as_int("PSMF_BPMF_COLS", 0);           // n > 0: columns per workgroup, rounded up to a multiple of 4 (0, unset: from n, at most 64 workgroups a replica)
+  int bpmf_chunk = as_int("PSMF_BPMF_CHUNK", 0);         // n > 0: at most n replicas per chunk, still capped by free memory (0, unset: sized from free memory alone)
   // diagnostics
   bool dbg_breakdown = set("PSMF_DBG_BREAKDOWN");        // psmf_counters prints the in-situ breakdown of a filter3 launch
   bool host_timing = on("PSMF_HOST_TIMING");             // report slow host-side enqueues and waits

@@ -18,8 +18,8 @@ The only random input is the permutation of every epoch, which the host draws (o
 they carry the reference's bits.  What the device is handed per replica and epoch is a batch map -- n x d bytes, the batch index of a
 training entry and 255 elsewhere: the order inside a batch only orders sums.  There is no CPU fallback.
 
-`pmf` keeps the reference function's signature and consumes the global numpy RNG as the reference does.  BPMF (BPMF.py) is not
-here: it is a Gibbs sampler that draws inside its loops; its pmf() warm start is this recursion, and `pmf_batch` returns the factors.
+`pmf` keeps the reference function's signature and consumes the global numpy RNG as the reference does.  BPMF (BPMF.py) is
+rpsmf_amd.bpmf: its pmf() warm start is this recursion, and `pmf_batch` returns the factors.
 """
 
 import ctypes as C
@@ -48,9 +48,8 @@ def _batch_sizes(N, nb):
     return np.full(nb, N // nb, dtype=np.int64) + (np.arange(nb) < N % nb)
 
 
-def _prepare(YorgInt, M, Mmiss, C0, X0, perms, epochs, num_batches):
-    """The host work in front of the launch: every refusal, mu and mbar with numpy, the batch maps, the sizes of the batches and their
-    entries by row, and the arrays in the device's layouts.  Returns the dict `_launch` takes."""
+def _shapes(YorgInt, M, Mmiss, C0, X0):
+    """The arrays with the batch dimension in front, and (d, n, r, B); ValueError where the shapes do not fit each other."""
     YorgInt = np.asarray(YorgInt, dtype=np.float64)
     M, Mmiss = np.asarray(M), np.asarray(Mmiss)
     C0, X0 = np.asarray(C0, dtype=np.float64), np.asarray(X0, dtype=np.float64)
@@ -64,6 +63,13 @@ def _prepare(YorgInt, M, Mmiss, C0, X0, perms, epochs, num_batches):
     B, r = M.shape[0], C0.shape[2]
     if B < 1 or d < 1 or n < 1 or M.shape != (B, d, n) or Mmiss.shape != (B, d, n) or C0.shape != (B, d, r) or X0.shape != (B, r, n):
         raise ValueError("inconsistent shapes: YorgInt (d, n); M, Mmiss (batch, d, n); C0 (batch, d, r); X0 (batch, r, n)")
+    return YorgInt, M, Mmiss, C0, X0, (d, n, r, B)
+
+
+def _prepare(YorgInt, M, Mmiss, C0, X0, perms, epochs, num_batches):
+    """The host work in front of the launch: every refusal, mu and mbar with numpy, the batch maps, the sizes of the batches and their
+    entries by row, and the arrays in the device's layouts.  Returns the dict `_launch` takes."""
+    YorgInt, M, Mmiss, C0, X0, (d, n, r, B) = _shapes(YorgInt, M, Mmiss, C0, X0)
     epochs, nb = int(epochs), int(num_batches)
     if not 1 <= nb <= MAX_BATCHES:
         raise ValueError(f"num_batches must be 1 .. {MAX_BATCHES} (the batch map is bytes, {NO_ENTRY} = no training entry); got {nb}")
