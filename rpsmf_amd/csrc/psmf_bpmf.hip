@@ -461,7 +461,7 @@ int bpmf_run(const psmf_bpmf_config* cfg, const double* Y, const uint8_t* M, con
   if (cfg->want_rec && !Yrec) return fail(PSMF_ERR_ARG, "want_rec needs Yrec");
   if (sw.bpmf_cols < 0 || sw.bpmf_chunk < 0) return fail(PSMF_ERR_ARG, "PSMF_BPMF_COLS and PSMF_BPMF_CHUNK must be >= 0 (0 = chosen by the library)");
   for (int b = 0; b < B; ++b)
-    if (!(mean[b] != 0.0)) return fail(PSMF_ERR_ARG, "the mean of the training entries is 0 or NaN in replica " + std::to_string(b) + " (the data is divided by it)");
+    if (mean[b] == 0.0 || !std::isfinite(mean[b])) return fail(PSMF_ERR_ARG, "the mean of the training entries is 0 or not finite in replica " + std::to_string(b) + " (the data is divided by it)");
   const bool wantRec = cfg->want_rec != 0;
   PSMF_TRY(open_device(fail, cfg->device));
 

@@ -303,7 +303,7 @@ int pmf_run(const psmf_pmf_config* cfg, const double* Y, const uint8_t* maps, co
   for (size_t i = 0; i < (size_t)B * nb; ++i)
     if (batch_sizes[i] < 1) return fail(PSMF_ERR_ARG, "an empty batch (the reference divides by its size): replica " + std::to_string(i / nb));
   for (int b = 0; b < B; ++b)
-    if (!(mean[b] != 0.0)) return fail(PSMF_ERR_ARG, "the mean of the training entries is 0 or NaN in replica " + std::to_string(b) + " (the data is divided by it)");
+    if (mean[b] == 0.0 || !std::isfinite(mean[b])) return fail(PSMF_ERR_ARG, "the mean of the training entries is 0 or not finite in replica " + std::to_string(b) + " (the data is divided by it)");
   const bool wantRec = cfg->want_rec != 0;
   PSMF_TRY(open_device(fail, cfg->device));
 

@@ -1,4 +1,4 @@
-"""Records tests/golden/net_cases_parent.json: per net (blocked, step, impute, gram, ssm_net) and per case index, the SHA-256 of
+"""Records tests/golden/net_cases_parent.json: per net (blocked, step, impute, gram, ssm_net, pmf_net, bpmf_net) and per case index, the SHA-256 of
 the case dict and of the arrays of problem(device_case(i)) (tests/test_net_cases_unchanged_cpu.py, which holds the digests' definition).
 Run once, without a GPU, at the commit whose cases are to be kept:
 

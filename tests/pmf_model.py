@@ -22,15 +22,20 @@ def draw_perms(N, epochs):
     return [np.random.permutation(N) for _ in range(epochs)]
 
 
-def pmf_model(YorigInt, M, Mmiss, C, X, perms, epochs=2, epsilon=50, lmd=0.01, momentum=0.8, num_batches=9, order="reference"):
-    """Returns dict(Efull (epochs,), P (d, r), W (n, r), Yrec (d, n) of the last epoch, mean, mean_rating)."""
-    YorigInt = np.asarray(YorigInt, dtype=float)
+def pmf_model(YorigInt, M, Mmiss, C, X, perms, epochs=2, epsilon=50, lmd=0.01, momentum=0.8, num_batches=9, order="reference", dtype=float):
+    """Returns dict(Efull (epochs,), P (d, r), W (n, r), Yrec (d, n) of the last epoch, mean, mean_rating).  dtype=np.longdouble is
+    the extended-precision model: the same expressions on the same (float64) inputs, with every array, constant and accumulator a
+    long double -- the data, the 0.1 of the scaling, lmd, momentum, epsilon, the means, the scatter and the error.  dtype=float
+    moves no bit of what the function gave before it had the argument."""
+    YorigInt = np.asarray(YorigInt, dtype=dtype)
     M, Mmiss = np.asarray(M), np.asarray(Mmiss)
+    C, X = np.asarray(C, dtype=dtype), np.asarray(X, dtype=dtype)
+    epsilon, lmd, momentum = dtype(epsilon), dtype(lmd), dtype(momentum)
     Y = YorigInt * M
     num_p, num_m = Y.shape
     num_feat = C.shape[1]
-    w1_M1 = 0.1 * X.T
-    w1_P1 = 0.1 * C
+    w1_M1 = dtype(0.1) * X.T
+    w1_P1 = dtype(0.1) * C
     w1_M1_inc = np.zeros_like(w1_M1)
     w1_P1_inc = np.zeros_like(w1_P1)
     tr_p, tr_m = training_set(M)
@@ -42,7 +47,7 @@ def pmf_model(YorigInt, M, Mmiss, C, X, perms, epochs=2, epsilon=50, lmd=0.01, m
     rating_all = (rating_all - old_mean) / old_std
     mean_rating = rating_all.mean()
 
-    Efull = np.zeros(epochs)
+    Efull = np.zeros(epochs, dtype=dtype)
     Yrec2 = np.zeros_like(Y)
     order_idx = np.arange(rating_all.size)
     with np.errstate(all="ignore"):
@@ -57,8 +62,8 @@ def pmf_model(YorigInt, M, Mmiss, C, X, perms, epochs=2, epsilon=50, lmd=0.01, m
                 rating = rating_all[batch_idx] - mean_rating
                 pred_out = np.sum(w1_M1[aa_m, :] * w1_P1[aa_p, :], axis=1)
                 IO = np.tile(2 * (pred_out - rating).reshape(N, 1), (1, num_feat))
-                dw1_M1 = np.zeros((num_m, num_feat))
-                dw1_P1 = np.zeros((num_p, num_feat))
+                dw1_M1 = np.zeros((num_m, num_feat), dtype=dtype)
+                dw1_P1 = np.zeros((num_p, num_feat), dtype=dtype)
                 if order == "sorted":
                     np.add.at(dw1_M1, aa_m, IO * w1_P1[aa_p, :])
                     np.add.at(dw1_P1, aa_p, IO * w1_M1[aa_m, :])
@@ -79,6 +84,6 @@ def pmf_model(YorigInt, M, Mmiss, C, X, perms, epochs=2, epsilon=50, lmd=0.01, m
             Yrec2[pr_p, pr_m] = pred_out
             # RMSEM(Yrec2, YorigInt, Mmiss), common.py:79-84
             nMissing = np.sum(Mmiss)
-            R2 = (1 / nMissing) * np.sum(np.power(np.multiply(Yrec2, Mmiss) - np.multiply(YorigInt, Mmiss), 2))
+            R2 = (dtype(1) / nMissing) * np.sum(np.power(np.multiply(Yrec2, Mmiss) - np.multiply(YorigInt, Mmiss), 2))
             Efull[epoch] = np.sqrt(R2)
     return dict(Efull=Efull, P=w1_P1, W=w1_M1, Yrec=Yrec2, mean=old_mean, mean_rating=mean_rating)

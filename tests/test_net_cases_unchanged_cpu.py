@@ -1,6 +1,6 @@
 """The cases of the random-configuration nets are what they were: tests/golden/net_cases_parent.json holds, per net and per case
 index, one SHA-256 over the case dict (canonical JSON) and every array of problem(device_case(i)) in sorted key order, recorded
-by tests/golden/make_golden_net_cases.py before the nets were moved onto tests/netlib.py.  A change to a draw, to a table
+by tests/golden/make_golden_net_cases.py before the nets were moved onto tests/netlib.py (pmf_net and bpmf_net: when they were added).  A change to a draw, to a table
 (RESOLUTION, REPLACED, TARGETS, ...) or to the order of the random draws inside a `problem` shows here, without a GPU.
 Wall time: about 15 s, most of it the step net's big-d series."""
 
@@ -13,7 +13,8 @@ import numpy as np
 import pytest
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "net_cases_parent.json")
-NETS = {"blocked": "blocked_cases", "step": "step_cases", "impute": "impute_cases", "gram": "gram_cases", "ssm_net": "ssm_net_cases"}
+NETS = {"blocked": "blocked_cases", "step": "step_cases", "impute": "impute_cases", "gram": "gram_cases", "ssm_net": "ssm_net_cases",
+        "pmf_net": "pmf_net_cases", "bpmf_net": "bpmf_net_cases"}
 
 
 def _plain(o):
