@@ -37,8 +37,6 @@ overwritten before it is used -- and is not computed.  The reference could in pr
 `bpmf` keeps the reference function's signature and consumes the global numpy RNG as the reference does.
 """
 
-import ctypes as C
-
 import numpy as np
 
 from . import _capi
@@ -144,29 +142,13 @@ def bpmf_batch(YorgInt, M, Mmiss, C0, X0, draws=None, *, epochs=2, beta=2, devic
 def _sweeps(h, warm, draws, beta, device, want_rec):
     """psmf_bpmf_run on what pmf's `_prepare` made (with the training mask, time-major, under "Mt"), the warm start `warm` that
     pmf's `_launch` returned for it, and the draws"""
-    d, n, r, B, epochs = (h[k] for k in ("d", "n", "r", "B", "epochs"))
-    bart = np.ascontiguousarray(np.stack([np.asarray(dr["bartlett"], dtype=np.float64) for dr in draws]))
-    hz = np.ascontiguousarray(np.stack([np.asarray(dr["hyper_normals"], dtype=np.float64) for dr in draws]))
-    Z = np.ascontiguousarray(np.stack([np.asarray(dr["normals"], dtype=np.float64) for dr in draws]))
+    bart, hz, Z = (np.ascontiguousarray(np.stack([np.asarray(dr[k], dtype=np.float64) for dr in draws])) for k in ("bartlett", "hyper_normals", "normals"))
     Pb = warm["C"]                                                              # (batch, d, r): h's own buffer, overwritten below
     Wb = np.ascontiguousarray(np.transpose(warm["X"], (0, 2, 1)))               # (batch, n, r)
     mean, mbar = warm["mean"], warm["mean_rating"]
-    Efull = np.zeros((B, epochs))
-    rec = np.zeros((B, n, d)) if want_rec else None
-    status = np.zeros(B, dtype=np.int32)
-    cfg = _capi.PsmfBpmfConfig(abi_version=_capi.ABI_VERSION, d=d, n=n, r=r, batch=B, epochs=epochs, device=int(device), want_rec=int(bool(want_rec)),
-                               beta=float(beta))
-    ms = C.c_float()
-    ptr = _capi._ptr
-    lib = _capi.load_library()
-    rc = lib.psmf_bpmf_run(C.byref(cfg), ptr(h["Yt"]), ptr(h["Mt"]), ptr(h["Mmt"]), ptr(mean), ptr(mbar), ptr(bart), ptr(hz), ptr(Z), ptr(Pb), ptr(Wb),
-                           ptr(Efull), ptr(rec), ptr(status), C.byref(ms))
-    _capi.raise_for(lib, rc, f"psmf_bpmf_run failed ({rc})")
-    out = dict(Efull=Efull, C=Pb, X=np.ascontiguousarray(np.transpose(Wb, (0, 2, 1))), mean=mean, mean_rating=mbar, status=status,
-               elapsed_ms=warm["elapsed_ms"] + ms.value)
-    if want_rec:
-        out["Yrec"] = np.ascontiguousarray(np.transpose(rec, (0, 2, 1)))
-    return out
+    cfg = _capi.PsmfBpmfConfig(abi_version=_capi.ABI_VERSION, d=h["d"], n=h["n"], r=h["r"], batch=h["B"], epochs=h["epochs"], device=int(device),
+                               want_rec=int(bool(want_rec)), beta=float(beta))
+    return _pmf._native_run("psmf_bpmf_run", cfg, [h["Yt"], h["Mt"], h["Mmt"], mean, mbar, bart, hz, Z], Pb, Wb, mean, mbar, warm["elapsed_ms"])
 
 
 def bpmf(Y, C, X, num_p, num_m, num_feat, M, Mmiss, YorigInt, Einit, epochs=50, beta=2):
@@ -175,20 +157,8 @@ def bpmf(Y, C, X, num_p, num_m, num_feat, M, Mmiss, YorigInt, Einit, epochs=50, 
     epochs.  Every draw comes from the global numpy RNG in the reference's order (`draw_bpmf`): a script that saves and restores
     the RNG state around the call (BPMF.py:361-375) gets the same repeats.  Raises numpy.linalg.LinAlgError where the reference
     would (a precision matrix that is not positive definite), which is what that script catches.  Requires Y == YorigInt * M."""
-    Y = np.asarray(Y, dtype=float)
-    YorigInt = np.asarray(YorigInt, dtype=float)
-    C, X = np.asarray(C), np.asarray(X)
-    if Y.shape != (num_p, num_m) or C.shape != (num_p, num_feat) or X.shape != (num_feat, num_m):
-        raise ValueError("shape mismatch with num_p, num_m, num_feat")
-    if np.shape(M) != Y.shape or not np.array_equal(Y, YorigInt * (np.asarray(M) != 0)):
-        raise ValueError("the device path requires Y == YorigInt * M (as the experiment constructs it)")
+    YorigInt = _pmf._reference_args(Y, C, X, num_p, num_m, num_feat, M, YorigInt)
     res = bpmf_batch(YorigInt, M, Mmiss, C, X, None, epochs=epochs, beta=beta)
     if res["status"][0] != 0:
         raise np.linalg.LinAlgError("a precision matrix of the sampler is not positive definite, or the factors left the finite range")
-    Epred = np.full((1, epochs + 1), np.nan)
-    Efull = np.zeros((1, epochs + 1))
-    Epred[0, 0] = Efull[0, 0] = Einit
-    Efull[0, 1:] = res["Efull"][0]
-    RunTime = np.zeros((1, epochs + 1))
-    RunTime[0, 1:] = 1e-3 * res["elapsed_ms"] * np.arange(1, epochs + 1) / epochs      # epochs are not timed separately
-    return Epred, Efull, RunTime
+    return _pmf._reference_result(res, Einit, epochs)

@@ -40,7 +40,7 @@
 // Limits: dim <= 32, T <= 4096.  Scratch (the table: T * T doubles per series) is allocated per call; a batch whose scratch does not fit
 // what is free on the device is processed in chunks of series.
 #include "psmf_host.h"        // Switches
-#include "psmf_batch.h"       // EntryFail, open_device, typed transfers, TimedLaunch, replica_status
+#include "psmf_batch.h"       // EntryFail, open_device, plan_chunk, per-item slots, TimedLaunch, all_finite, replica_status
 
 #include <algorithm>
 #include <cmath>
@@ -295,39 +295,30 @@ int bocpd_run(const psmf_bocpd_config* cfg, const double* X, int32_t* map_run, i
     cst[a] = std::lgamma(0.5 * (nu + dim)) - std::lgamma(0.5 * nu) + 0.5 * dim * (std::log(sc) - std::log(nu * M_PI));
   }
   std::vector<int> herr(B, 0);
-  for (int b = 0; b < B; ++b) {
-    const double* x = X + (size_t)b * T * dim;
-    for (size_t i = 0; i < (size_t)T * dim; ++i)
-      if (!std::isfinite(x[i])) { herr[b] = 1; break; }
-  }
+  for (int b = 0; b < B; ++b)
+    if (!all_finite(X + (size_t)b * T * dim, (size_t)T * dim)) herr[b] = 1;
   PSMF_TRY(open_device(fail, cfg->device));
 
-  // series per chunk: the scratch and the outputs of a chunk take at most half of what is free, and at most 16 GiB
+  // series per chunk (PSMF_BOCPD_CHUNK: smaller chunks than memory asks for)
   const size_t per_series = ((size_t)T * T + (size_t)T * dim + (wantR ? (size_t)(T + 1) * (T + 1) : 0) + (wantLp ? (size_t)T * T : 0) + (T + 1)) * sizeof(double) +
                             ((size_t)T + maxcp + 2) * sizeof(int);
-  size_t free_b = 0, total_b = 0;
-  PSMF_TRY(HIP_OK(fail, hipMemGetInfo(&free_b, &total_b)));
-  size_t budget = free_b / 2;
-  if (budget > ((size_t)16 << 30)) budget = (size_t)16 << 30;
-  if (per_series > budget) return fail(PSMF_ERR_HIP, "one series needs " + std::to_string(per_series) + " bytes of device scratch, more than is free");
-  int chunk = (int)std::min<size_t>((size_t)B, budget / per_series);
-  if (sw.bocpd_chunk > 0) chunk = std::min(chunk, sw.bocpd_chunk);      // PSMF_BOCPD_CHUNK: smaller chunks than memory asks for
+  int chunk = 0;
+  PSMF_TRY(plan_chunk(fail, B, 0, per_series, kNoItemCap, sw.bocpd_chunk, "series", &chunk));
 
   Dev<double> dX, dCst, dTab, dRl, dR, dLp;
   Dev<int> dMap, dCp, dNcp, dErr;
   TimedLaunch timed;
-  const size_t nX = (size_t)T * dim, nTab = (size_t)T * T, nR = (size_t)(T + 1) * (T + 1), nRl = (size_t)T + 1;
-  PSMF_TRY(alloc_n(fail, dX, chunk * nX));
-  PSMF_TRY(alloc_n(fail, dCst, T));
-  PSMF_TRY(alloc_n(fail, dTab, chunk * nTab));
-  PSMF_TRY(alloc_n(fail, dMap, (size_t)chunk * T));
-  PSMF_TRY(alloc_n(fail, dCp, (size_t)chunk * maxcp + 1));
-  PSMF_TRY(alloc_n(fail, dNcp, chunk));
-  PSMF_TRY(alloc_n(fail, dErr, chunk));
-  if (R_last) PSMF_TRY(alloc_n(fail, dRl, chunk * nRl));
-  if (wantR) PSMF_TRY(alloc_n(fail, dR, chunk * nR));
-  if (wantLp) PSMF_TRY(alloc_n(fail, dLp, chunk * nTab));
-  PSMF_TRY(copy_in(fail, dCst, cst.data(), T));
+  const size_t nX = (size_t)T * dim, nTab = (size_t)T * T, nR = (size_t)(T + 1) * (T + 1), nRl = (size_t)T + 1, nT = T, nCp = maxcp;
+  const auto items = std::make_tuple(      // buffer, filled from, read back to, elements per series, cleared for every chunk
+      item_slot(dX, X, nullptr, nX), item_slot(dTab, nullptr, nullptr, nTab), item_slot(dMap, nullptr, map_run, nT, true),
+      item_slot(dCp, nullptr, changepoints, nCp, true, 1),      // (one element more: max_changepoints may be 0)
+      item_slot(dNcp, nullptr, n_changepoints, 1, true), item_slot(dErr, herr.data(), herr.data(), 1),
+      item_slot(dRl, nullptr, R_last, R_last ? nRl : 0, true), item_slot(dR, nullptr, R, wantR ? nR : 0, true),
+      item_slot(dLp, nullptr, logpred, wantLp ? nTab : 0, true));
+  const auto shared = std::make_tuple(slot(dCst, cst.data(), nullptr, nT));      // what every chunk shares, filled once
+  PSMF_TRY(alloc_all(fail, shared));
+  PSMF_TRY(alloc_items(fail, items, chunk));
+  PSMF_TRY(copy_in_all(fail, shared));
   PSMF_TRY(timed.create(fail));
 
   BocpdParams bp;
@@ -341,27 +332,14 @@ int bocpd_run(const psmf_bocpd_config* cfg, const double* X, int32_t* map_run, i
   float total_ms = 0.0f;
   for (int s0 = 0; s0 < B; s0 += chunk) {      // s0: the chunk's first series = its element offset in the host arrays, per series
     const size_t ns = std::min(chunk, B - s0);
-    PSMF_TRY(copy_in(fail, dX, X, ns * nX, s0 * nX));
-    PSMF_TRY(copy_in(fail, dErr, herr.data(), ns, s0));
-    PSMF_TRY(zero_n(fail, dMap, ns * T));
-    PSMF_TRY(zero_n(fail, dCp, ns * maxcp + 1));
-    PSMF_TRY(zero_n(fail, dNcp, ns));
-    if (R_last) PSMF_TRY(zero_n(fail, dRl, ns * nRl));
-    if (wantR) PSMF_TRY(zero_n(fail, dR, ns * nR));
-    if (wantLp) PSMF_TRY(zero_n(fail, dLp, ns * nTab));
+    PSMF_TRY(fill_items(fail, items, s0, ns));
     PSMF_TRY(timed.start(fail));
     PSMF_TRY(bocpd_launch_chain<1>(fail, bp, (int)ns));      // the instance of this dim
     PSMF_TRY(launch(fail, (const void*)psmf_bocpd_post_kernel, dim3((unsigned)ns), dim3(BOCPD_POST_WG), &bp, 0));
     float ms = 0.0f;
     PSMF_TRY(timed.finish(fail, &ms));
     total_ms += ms;
-    PSMF_TRY(copy_out(fail, map_run, dMap, ns * T, (size_t)s0 * T));
-    if (maxcp > 0) PSMF_TRY(copy_out(fail, changepoints, dCp, ns * maxcp, (size_t)s0 * maxcp));
-    PSMF_TRY(copy_out(fail, n_changepoints, dNcp, ns, s0));
-    PSMF_TRY(copy_out(fail, herr.data(), dErr, ns, s0));
-    if (R_last) PSMF_TRY(copy_out(fail, R_last, dRl, ns * nRl, s0 * nRl));
-    if (wantR) PSMF_TRY(copy_out(fail, R, dR, ns * nR, s0 * nR));
-    if (wantLp) PSMF_TRY(copy_out(fail, logpred, dLp, ns * nTab, s0 * nTab));
+    PSMF_TRY(read_items(fail, items, s0, ns));
   }
   if (elapsed_ms) *elapsed_ms = total_ms;
   // Per-replica outcome, as psmf_ssm_run; the other replicas are untouched by a bad one.

@@ -37,7 +37,7 @@
 // sets the replica's flag (a plain store of 1) and the replica goes on in NaNs; nothing of its neighbours reads it.
 // Limits: 2 <= d <= 512, 2 <= r <= 16, n >= 2.
 #include "psmf_host.h"        // Switches
-#include "psmf_batch.h"       // EntryFail, open_device, typed transfers, TimedLaunch, replica_status
+#include "psmf_batch.h"       // EntryFail, open_device, plan_chunk, per-item slots, TimedLaunch, cols_per_workgroup, all_finite, replica_status
 #include "psmf_wave.h"        // f64x4, row_sum_f64_dpp
 
 #include <algorithm>
@@ -465,38 +465,32 @@ int bpmf_run(const psmf_bpmf_config* cfg, const double* Y, const uint8_t* M, con
   const bool wantRec = cfg->want_rec != 0;
   PSMF_TRY(open_device(fail, cfg->device));
 
-  // columns per workgroup: a multiple of the four columns a wave takes at a time; by default at most 64 workgroups a replica
-  int cols = sw.bpmf_cols > 0 ? sw.bpmf_cols : std::max(64, (n + 63) / 64);      // PSMF_BPMF_COLS
-  cols = (int)std::min<long long>(((long long)cols + 3) & ~3LL, ((long long)n + 3) & ~3LL);
-  const int nwg = (n + cols - 1) / cols;
+  // columns per workgroup: a multiple of the four columns a wave takes at a time (PSMF_BPMF_COLS)
+  const auto [cols, nwg] = cols_per_workgroup(n, sw.bpmf_cols, 64, 4);
 
   const size_t nYd = (size_t)n * d, nW = (size_t)n * r, nP = (size_t)d * r, nZ = (size_t)epochs * 2 * (nW + nP), nBart = (size_t)epochs * 2 * r * r,
                nHz = (size_t)epochs * 2 * r, nPart = (size_t)nwg * d * BPMF_IMG, nSum = (size_t)nwg * 16, nCov = (size_t)nwg * 256;
   const size_t per_rep = 2 * nYd * sizeof(uint8_t) + sizeof(int) +
                          (nZ + nBart + nHz + nW + nP + nPart + nSum + nCov + 2 * BPMF_IMG + nYd + (wantRec ? nYd : 0) + epochs + 2) * sizeof(double);
-  size_t free_b = 0, total_b = 0;
-  PSMF_TRY(HIP_OK(fail, hipMemGetInfo(&free_b, &total_b)));
-  const size_t shared_b = nYd * sizeof(double);
-  size_t budget = free_b / 2;
-  if (budget > ((size_t)16 << 30)) budget = (size_t)16 << 30;
-  if (shared_b + per_rep > budget) return fail(PSMF_ERR_HIP, "one replica needs " + std::to_string(shared_b + per_rep) + " bytes of device memory, more than is free");
-  int chunk = (int)std::min<size_t>(std::min(B, BPMF_MAX_REPLICAS), (budget - shared_b) / per_rep);
-  if (sw.bpmf_chunk > 0) chunk = std::min(chunk, sw.bpmf_chunk);      // PSMF_BPMF_CHUNK: smaller chunks than memory asks for
+  int chunk = 0;      // replicas per chunk (PSMF_BPMF_CHUNK: smaller chunks than memory asks for)
+  PSMF_TRY(plan_chunk(fail, B, nYd * sizeof(double), per_rep, BPMF_MAX_REPLICAS, sw.bpmf_chunk, "replica", &chunk));
 
   Dev<double> dY, dMu, dMbar, dBart, dHz, dZ, dW, dP, dSum, dCov, dHyp, dPart, dAvg, dE, dRec;
   Dev<uint8_t> dM, dMiss;
   Dev<int> dBad;
   TimedLaunch timed;
-  const size_t nc = chunk;
-  const auto bufs = std::make_tuple(slot(dY, Y, nullptr, nYd), slot(dM, nullptr, nullptr, nc * nYd), slot(dMiss, nullptr, nullptr, nc * nYd),
-                                    slot(dMu, nullptr, nullptr, nc), slot(dMbar, nullptr, nullptr, nc), slot(dBart, nullptr, nullptr, nc * nBart),
-                                    slot(dHz, nullptr, nullptr, nc * nHz), slot(dZ, nullptr, nullptr, nc * nZ), slot(dW, nullptr, nullptr, nc * nW),
-                                    slot(dP, nullptr, nullptr, nc * nP), slot(dSum, nullptr, nullptr, nc * nSum), slot(dCov, nullptr, nullptr, nc * nCov),
-                                    slot(dHyp, nullptr, nullptr, nc * 2 * BPMF_IMG), slot(dPart, nullptr, nullptr, nc * nPart),
-                                    slot(dAvg, nullptr, nullptr, nc * nYd), slot(dE, nullptr, nullptr, nc * epochs),
-                                    slot(dRec, nullptr, nullptr, wantRec ? nc * nYd : 0), slot(dBad, nullptr, nullptr, nc));
-  PSMF_TRY(alloc_all(fail, bufs));
-  PSMF_TRY(copy_in_all(fail, bufs));      // (Y: the one buffer every chunk shares)
+  std::vector<int> bad((size_t)B, 0);
+  const size_t nE = epochs, nHyp = 2 * BPMF_IMG;
+  const auto items = std::make_tuple(      // buffer, filled from, read back to, elements per replica, cleared for every chunk
+      item_slot(dM, M, nullptr, nYd), item_slot(dMiss, Mmiss, nullptr, nYd), item_slot(dMu, mean, nullptr, 1), item_slot(dMbar, mean_rating, nullptr, 1),
+      item_slot(dBart, bartlett, nullptr, nBart), item_slot(dHz, hyper_normals, nullptr, nHz), item_slot(dZ, normals, nullptr, nZ),
+      item_slot(dW, W, W, nW), item_slot(dP, P, P, nP), item_slot(dSum, nullptr, nullptr, nSum), item_slot(dCov, nullptr, nullptr, nCov),
+      item_slot(dHyp, nullptr, nullptr, nHyp), item_slot(dPart, nullptr, nullptr, nPart), item_slot(dAvg, nullptr, nullptr, nYd),
+      item_slot(dE, nullptr, Efull, nE), item_slot(dRec, nullptr, Yrec, wantRec ? nYd : 0, true), item_slot(dBad, nullptr, bad.data(), 1, true));
+  const auto shared = std::make_tuple(slot(dY, Y, nullptr, nYd));      // what every chunk shares, filled once
+  PSMF_TRY(alloc_all(fail, shared));
+  PSMF_TRY(alloc_items(fail, items, chunk));
+  PSMF_TRY(copy_in_all(fail, shared));
   PSMF_TRY(timed.create(fail));
   const size_t col_lds = bpmf_col_lds_doubles(d) * sizeof(double);
   PSMF_TRY(lds_opt_in(fail, (const void*)psmf_bpmf_col_kernel, col_lds));
@@ -508,22 +502,11 @@ int bpmf_run(const psmf_bpmf_config* cfg, const double* Y, const uint8_t* M, con
   pp.psum = dSum; pp.pcov = dCov; pp.hyp = dHyp; pp.part = dPart; pp.avg = dAvg; pp.efull = dE; pp.yrec = wantRec ? dRec.get() : nullptr;
   pp.bad = dBad;
 
-  std::vector<int> bad((size_t)B, 0);
   float total_ms = 0.0f;
   for (int s0 = 0; s0 < B; s0 += chunk) {      // s0: the chunk's first replica = its element offset in the host arrays, per replica
     const size_t ns = std::min(chunk, B - s0);
     const dim3 wide((unsigned)nwg, (unsigned)ns), one((unsigned)ns), block(BPMF_WG);
-    PSMF_TRY(copy_in(fail, dM, M, ns * nYd, s0 * nYd));
-    PSMF_TRY(copy_in(fail, dMiss, Mmiss, ns * nYd, s0 * nYd));
-    PSMF_TRY(copy_in(fail, dMu, mean, ns, s0));
-    PSMF_TRY(copy_in(fail, dMbar, mean_rating, ns, s0));
-    PSMF_TRY(copy_in(fail, dBart, bartlett, ns * nBart, s0 * nBart));
-    PSMF_TRY(copy_in(fail, dHz, hyper_normals, ns * nHz, s0 * nHz));
-    PSMF_TRY(copy_in(fail, dZ, normals, ns * nZ, s0 * nZ));
-    PSMF_TRY(copy_in(fail, dW, W, ns * nW, s0 * nW));
-    PSMF_TRY(copy_in(fail, dP, P, ns * nP, s0 * nP));
-    PSMF_TRY(zero_n(fail, dBad, ns));
-    if (wantRec) PSMF_TRY(zero_n(fail, dRec, ns * nYd));
+    PSMF_TRY(fill_items(fail, items, s0, ns));
     PSMF_TRY(timed.start(fail));
     pp.count = 0; pp.last = 0; pp.epoch = 0;
     PSMF_TRY(launch(fail, (const void*)psmf_bpmf_metric_kernel, one, block, &pp, 0));
@@ -545,22 +528,13 @@ int bpmf_run(const psmf_bpmf_config* cfg, const double* Y, const uint8_t* M, con
     float ms = 0.0f;
     PSMF_TRY(timed.finish(fail, &ms));
     total_ms += ms;
-    PSMF_TRY(copy_out(fail, W, dW, ns * nW, s0 * nW));
-    PSMF_TRY(copy_out(fail, P, dP, ns * nP, s0 * nP));
-    PSMF_TRY(copy_out(fail, Efull, dE, ns * epochs, (size_t)s0 * epochs));
-    PSMF_TRY(copy_out(fail, bad.data(), dBad, ns, (size_t)s0));
-    if (wantRec) PSMF_TRY(copy_out(fail, Yrec, dRec, ns * nYd, s0 * nYd));
+    PSMF_TRY(read_items(fail, items, s0, ns));
   }
   if (elapsed_ms) *elapsed_ms = total_ms;
   // Per-replica outcome, as psmf_pmf_run: a replica with a pivot that was not positive, or whose factors or errors left the finite
   // range; the others are untouched by it.
-  auto finite = [](const double* v, size_t count) {
-    for (size_t i = 0; i < count; ++i)
-      if (!std::isfinite(v[i])) return false;
-    return true;
-  };
   return replica_status(fail, B, status,
-                        [&](int b) { return bad[b] != 0 || !(finite(W + b * nW, nW) && finite(P + b * nP, nP) && finite(Efull + (size_t)b * epochs, epochs)); },
+                        [&](int b) { return bad[b] != 0 || !(all_finite(W + b * nW, nW) && all_finite(P + b * nP, nP) && all_finite(Efull + b * nE, nE)); },
                         [](int b) { return "a precision matrix of replica " + std::to_string(b) + " is not positive definite (numpy.linalg.LinAlgError upstream)"; });
 }
 

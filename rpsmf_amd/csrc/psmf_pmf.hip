@@ -27,10 +27,10 @@
 //
 // No atomics and no flags: the dependency between the batches is a whole-grid one, and launches express it.  Every sum has a fixed
 // order, so a call gives the same bits twice, and a replica the same bits alone as inside a batch (the workgroups of a replica depend
-// on n and PSMF_PMF_COLS alone).  Limits: d <= 512, r <= 16, num_batches <= 254; n is unlimited.  A batch whose maps, W and incW do
-// not fit half of the free device memory is processed in chunks of replicas.
+// on n and PSMF_PMF_COLS alone).  Limits: d <= 512, r <= 16, num_batches <= 254; n is unlimited.  A batch whose buffers do not fit
+// the device is processed in chunks of replicas (plan_chunk in psmf_batch.h).
 #include "psmf_host.h"        // Switches
-#include "psmf_batch.h"       // EntryFail, open_device, typed transfers, TimedLaunch, replica_status
+#include "psmf_batch.h"       // EntryFail, open_device, plan_chunk, per-item slots, TimedLaunch, cols_per_workgroup, all_finite, replica_status
 #include "psmf_wave.h"        // f64x4
 
 #include <algorithm>
@@ -307,36 +307,29 @@ int pmf_run(const psmf_pmf_config* cfg, const double* Y, const uint8_t* maps, co
   const bool wantRec = cfg->want_rec != 0;
   PSMF_TRY(open_device(fail, cfg->device));
 
-  // columns per workgroup: a multiple of the 16-column tile; by default at most 64 workgroups a replica and at least 16 tiles each
-  const int waves = pmf_waves(pmf_row_tiles(d));
-  int cols = sw.pmf_cols > 0 ? sw.pmf_cols : std::max(64 * waves, (n + 63) / 64);      // PSMF_PMF_COLS
-  cols = (int)std::min<long long>(((long long)cols + 15) / 16 * 16, ((long long)n + 15) / 16 * 16);
-  const int nwg = (n + cols - 1) / cols;
+  // columns per workgroup: a multiple of the 16-column tile; by default at least 16 tiles a wave (PSMF_PMF_COLS)
+  const auto [cols, nwg] = cols_per_workgroup(n, sw.pmf_cols, 64 * pmf_waves(pmf_row_tiles(d)), 16);
 
   const size_t nYd = (size_t)n * d, nW = (size_t)n * r, nP = (size_t)d * r, nPart = (size_t)nwg * nP, nCnt = (size_t)epochs * nb * d;
   const size_t per_rep = (epochs * nYd + nYd) * sizeof(uint8_t) + (2 * nW + 2 * nP + nPart + (wantRec ? nYd : 0) + epochs + 2) * sizeof(double) +
                          (nCnt + nb) * sizeof(int);
-  size_t free_b = 0, total_b = 0;
-  PSMF_TRY(HIP_OK(fail, hipMemGetInfo(&free_b, &total_b)));
-  const size_t shared_b = nYd * sizeof(double);
-  size_t budget = free_b / 2;
-  if (budget > ((size_t)16 << 30)) budget = (size_t)16 << 30;
-  if (shared_b + per_rep > budget) return fail(PSMF_ERR_HIP, "one replica needs " + std::to_string(shared_b + per_rep) + " bytes of device memory, more than is free");
-  int chunk = (int)std::min<size_t>(std::min(B, PMF_MAX_REPLICAS), (budget - shared_b) / per_rep);
-  if (sw.pmf_chunk > 0) chunk = std::min(chunk, sw.pmf_chunk);      // PSMF_PMF_CHUNK: smaller chunks than memory asks for
+  int chunk = 0;      // replicas per chunk (PSMF_PMF_CHUNK: smaller chunks than memory asks for)
+  PSMF_TRY(plan_chunk(fail, B, nYd * sizeof(double), per_rep, PMF_MAX_REPLICAS, sw.pmf_chunk, "replica", &chunk));
 
   Dev<double> dY, dMu, dMbar, dW, dIncW, dP, dIncP, dPart, dE, dRec;
   Dev<uint8_t> dMap, dMiss;
   Dev<int> dNb, dCnt;
   TimedLaunch timed;
-  const size_t nc = chunk;
-  const auto bufs = std::make_tuple(slot(dY, Y, nullptr, nYd), slot(dMap, nullptr, nullptr, nc * epochs * nYd), slot(dMiss, nullptr, nullptr, nc * nYd),
-                                    slot(dNb, nullptr, nullptr, nc * nb), slot(dCnt, nullptr, nullptr, nc * nCnt), slot(dMu, nullptr, nullptr, nc),
-                                    slot(dMbar, nullptr, nullptr, nc), slot(dW, nullptr, nullptr, nc * nW), slot(dIncW, nullptr, nullptr, nc * nW),
-                                    slot(dP, nullptr, nullptr, nc * nP), slot(dIncP, nullptr, nullptr, nc * nP), slot(dPart, nullptr, nullptr, nc * nPart),
-                                    slot(dE, nullptr, nullptr, nc * epochs), slot(dRec, nullptr, nullptr, wantRec ? nc * nYd : 0));
-  PSMF_TRY(alloc_all(fail, bufs));
-  PSMF_TRY(copy_in_all(fail, bufs));      // (Y: the one buffer every chunk shares)
+  const size_t nE = epochs, nNb = nb;
+  const auto items = std::make_tuple(      // buffer, filled from, read back to, elements per replica, cleared for every chunk
+      item_slot(dMap, maps, nullptr, nE * nYd), item_slot(dMiss, Mmiss, nullptr, nYd), item_slot(dNb, batch_sizes, nullptr, nNb),
+      item_slot(dCnt, row_counts, nullptr, nCnt), item_slot(dMu, mean, nullptr, 1), item_slot(dMbar, mean_rating, nullptr, 1),
+      item_slot(dW, W, W, nW), item_slot(dIncW, nullptr, nullptr, nW, true), item_slot(dP, P, P, nP), item_slot(dIncP, nullptr, nullptr, nP, true),
+      item_slot(dPart, nullptr, nullptr, nPart), item_slot(dE, nullptr, Efull, nE), item_slot(dRec, nullptr, Yrec, wantRec ? nYd : 0, true));
+  const auto shared = std::make_tuple(slot(dY, Y, nullptr, nYd));      // what every chunk shares, filled once
+  PSMF_TRY(alloc_all(fail, shared));
+  PSMF_TRY(alloc_items(fail, items, chunk));
+  PSMF_TRY(copy_in_all(fail, shared));
   PSMF_TRY(timed.create(fail));
 
   PmfParams pp;
@@ -348,17 +341,7 @@ int pmf_run(const psmf_pmf_config* cfg, const double* Y, const uint8_t* maps, co
   float total_ms = 0.0f;
   for (int s0 = 0; s0 < B; s0 += chunk) {      // s0: the chunk's first replica = its element offset in the host arrays, per replica
     const size_t ns = std::min(chunk, B - s0);
-    PSMF_TRY(copy_in(fail, dMap, maps, ns * epochs * nYd, s0 * epochs * nYd));
-    PSMF_TRY(copy_in(fail, dMiss, Mmiss, ns * nYd, s0 * nYd));
-    PSMF_TRY(copy_in(fail, dNb, batch_sizes, ns * nb, (size_t)s0 * nb));
-    PSMF_TRY(copy_in(fail, dCnt, row_counts, ns * nCnt, s0 * nCnt));
-    PSMF_TRY(copy_in(fail, dMu, mean, ns, s0));
-    PSMF_TRY(copy_in(fail, dMbar, mean_rating, ns, s0));
-    PSMF_TRY(copy_in(fail, dW, W, ns * nW, s0 * nW));
-    PSMF_TRY(copy_in(fail, dP, P, ns * nP, s0 * nP));
-    PSMF_TRY(zero_n(fail, dIncW, ns * nW));
-    PSMF_TRY(zero_n(fail, dIncP, ns * nP));
-    if (wantRec) PSMF_TRY(zero_n(fail, dRec, ns * nYd));
+    PSMF_TRY(fill_items(fail, items, s0, ns));
     PSMF_TRY(timed.start(fail));
     for (int e = 0; e < epochs; ++e) {
       pp.epoch = e;
@@ -373,19 +356,11 @@ int pmf_run(const psmf_pmf_config* cfg, const double* Y, const uint8_t* maps, co
     float ms = 0.0f;
     PSMF_TRY(timed.finish(fail, &ms));
     total_ms += ms;
-    PSMF_TRY(copy_out(fail, W, dW, ns * nW, s0 * nW));
-    PSMF_TRY(copy_out(fail, P, dP, ns * nP, s0 * nP));
-    PSMF_TRY(copy_out(fail, Efull, dE, ns * epochs, (size_t)s0 * epochs));
-    if (wantRec) PSMF_TRY(copy_out(fail, Yrec, dRec, ns * nYd, s0 * nYd));
+    PSMF_TRY(read_items(fail, items, s0, ns));
   }
   if (elapsed_ms) *elapsed_ms = total_ms;
   // Per-replica outcome, as psmf_ssm_run: a replica whose factors or errors left the finite range; the others are untouched by it.
-  auto finite = [](const double* v, size_t count) {
-    for (size_t i = 0; i < count; ++i)
-      if (!std::isfinite(v[i])) return false;
-    return true;
-  };
-  return replica_status(fail, B, status, [&](int b) { return !(finite(W + b * nW, nW) && finite(P + b * nP, nP) && finite(Efull + (size_t)b * epochs, epochs)); },
+  return replica_status(fail, B, status, [&](int b) { return !(all_finite(W + b * nW, nW) && all_finite(P + b * nP, nP) && all_finite(Efull + b * nE, nE)); },
                         [](int b) { return "the factors or the error of replica " + std::to_string(b) + " are not finite (the gradient steps diverged)"; });
 }
 

@@ -20,7 +20,7 @@
 // psmf_impute2.hip; the p x p and p x r products of the step (A P_prev, its product with A^T, Pbar H^T, its product with W, the update
 // of P) run there too, one 16 x 16 output tile per wave.  Limits: d <= 512, r <= 16, r <= p <= 32.
 #include "psmf_host.h"        // WG and the device headers
-#include "psmf_batch.h"       // EntryFail, open_device, typed transfers, TimedLaunch, replica_status
+#include "psmf_batch.h"       // EntryFail, open_device, typed transfers, TimedLaunch, all_finite, replica_status
 #include "psmf_sweep.h"       // solve_barrier
 #include "psmf_wave16.hip"    // wave_sweep16m, Sw16K
 
@@ -616,12 +616,7 @@ int ssm_run(const EntryFail& fail, bool ex, const psmf_ssm_config_ex* cfg, const
   if (robust) PSMF_TRY(copy_out(fail, robust_state, dRs, (size_t)B * 2));
   PSMF_TRY(copy_out(fail, herr.data(), dErr, B));
   // Per-replica outcome, as psmf_impute_run; the other replicas are untouched by a bad one (one workgroup each).
-  const auto bad = [&](int b) {
-    bool nf = herr[b] != 0;
-    for (int i = 0; i < np && !nf; ++i) nf = !std::isfinite(x[(size_t)b * np + i]);
-    for (size_t i = 0; i < (size_t)d * r && !nf; ++i) nf = !std::isfinite(C[(size_t)b * d * r + i]);
-    return nf;
-  };
+  const auto bad = [&](int b) { return herr[b] != 0 || !all_finite(x + (size_t)b * np, np) || !all_finite(C + (size_t)b * d * r, (size_t)d * r); };
   return replica_status(fail, B, status, bad, [](int b) {
     return "the r x r system lost positive definiteness, or the state is not finite, in replica " + std::to_string(b);
   });

@@ -139,25 +139,29 @@ def _prepare(YorgInt, M, Mmiss, C0, X0, perms, epochs, num_batches):
     return dict(d=d, n=n, r=r, B=B, epochs=epochs, nb=nb, Yt=Yt, maps=maps, Mmt=Mmt, sizes=sizes, counts=counts, mean=mean, mbar=mbar, Pb=Pb, Wb=Wb)
 
 
-def _launch(h, epsilon, lmd, momentum, device, want_rec):
-    """psmf_pmf_run on what `_prepare` made (P and W of `h` are overwritten with the final factors)"""
-    d, n, r, B, epochs, nb = (h[k] for k in ("d", "n", "r", "B", "epochs", "nb"))
-    Yt, maps, Mmt, sizes, counts, mean, mbar, Pb, Wb = (h[k] for k in ("Yt", "maps", "Mmt", "sizes", "counts", "mean", "mbar", "Pb", "Wb"))
-    Efull = np.zeros((B, epochs))
-    rec = np.zeros((B, n, d)) if want_rec else None
-    status = np.zeros(B, dtype=np.int32)
-    cfg = _capi.PsmfPmfConfig(abi_version=_capi.ABI_VERSION, d=d, n=n, r=r, batch=B, epochs=epochs, num_batches=nb, device=int(device),
-                              want_rec=int(bool(want_rec)), epsilon=float(epsilon), lmd=float(lmd), momentum=float(momentum))
+def _native_run(entry, cfg, inputs, Pb, Wb, mean, mbar, elapsed_before=0.0):
+    """The native call `entry` (psmf_pmf_run or psmf_bpmf_run: the configuration, `inputs`, then P, W, Efull, Yrec, status, elapsed_ms)
+    and the dict a batch function returns.  Pb (batch, d, r) and Wb (batch, n, r) are overwritten with the final factors."""
+    Efull = np.zeros((cfg.batch, cfg.epochs))
+    rec = np.zeros((cfg.batch, cfg.n, cfg.d)) if cfg.want_rec else None
+    status = np.zeros(cfg.batch, dtype=np.int32)
     ms = C.c_float()
     ptr = _capi._ptr
     lib = _capi.load_library()
-    rc = lib.psmf_pmf_run(C.byref(cfg), ptr(Yt), ptr(maps), ptr(Mmt), ptr(sizes), ptr(counts), ptr(mean), ptr(mbar), ptr(Pb), ptr(Wb), ptr(Efull),
-                          ptr(rec), ptr(status), C.byref(ms))
-    _capi.raise_for(lib, rc, f"psmf_pmf_run failed ({rc})")
-    out = dict(Efull=Efull, C=Pb, X=np.ascontiguousarray(np.transpose(Wb, (0, 2, 1))), mean=mean, mean_rating=mbar, status=status, elapsed_ms=ms.value)
-    if want_rec:
+    rc = getattr(lib, entry)(C.byref(cfg), *(ptr(a) for a in inputs), ptr(Pb), ptr(Wb), ptr(Efull), ptr(rec), ptr(status), C.byref(ms))
+    _capi.raise_for(lib, rc, f"{entry} failed ({rc})")
+    out = dict(Efull=Efull, C=Pb, X=np.ascontiguousarray(np.transpose(Wb, (0, 2, 1))), mean=mean, mean_rating=mbar, status=status,
+               elapsed_ms=elapsed_before + ms.value)
+    if cfg.want_rec:
         out["Yrec"] = np.ascontiguousarray(np.transpose(rec, (0, 2, 1)))
     return out
+
+
+def _launch(h, epsilon, lmd, momentum, device, want_rec):
+    """psmf_pmf_run on what `_prepare` made (P and W of `h` are overwritten with the final factors)"""
+    cfg = _capi.PsmfPmfConfig(abi_version=_capi.ABI_VERSION, d=h["d"], n=h["n"], r=h["r"], batch=h["B"], epochs=h["epochs"], num_batches=h["nb"],
+                              device=int(device), want_rec=int(bool(want_rec)), epsilon=float(epsilon), lmd=float(lmd), momentum=float(momentum))
+    return _native_run("psmf_pmf_run", cfg, [h[k] for k in ("Yt", "maps", "Mmt", "sizes", "counts", "mean", "mbar")], h["Pb"], h["Wb"], h["mean"], h["mbar"])
 
 
 def pmf_batch(YorgInt, M, Mmiss, C0, X0, perms=None, *, epochs=2, epsilon=50, lmd=0.01, momentum=0.8, num_batches=9, device=0,
@@ -181,11 +185,8 @@ def pmf_batch(YorgInt, M, Mmiss, C0, X0, perms=None, *, epochs=2, epsilon=50, lm
     return _launch(h, epsilon, lmd, momentum, device, want_rec)
 
 
-def pmf(Y, C, X, num_p, num_m, num_feat, M, Mmiss, YorigInt, Einit, epochs=50, epsilon=50, lmd=0.01, momentum=0.8, num_batches=9):
-    """ExperimentImpute/PMF.py:43-159 on the device.  Returns (Epred, Efull, RunTime) like the reference, each (1, epochs + 1): column
-    0 is Einit, Epred is NaN beyond it (PMF predicts nothing online), RunTime spreads the kernels' time evenly over the epochs.  The
-    permutations come from the global numpy RNG, one numpy.random.permutation per epoch, as in the reference: a script that saves
-    and restores the RNG state around the call (PMF.py:218-224) gets the same repeats.  Requires Y == YorigInt * M."""
+def _reference_args(Y, C, X, num_p, num_m, num_feat, M, YorigInt):
+    """the checks of a function with the reference's signature; returns YorigInt as an array"""
     Y = np.asarray(Y, dtype=float)
     YorigInt = np.asarray(YorigInt, dtype=float)
     C, X = np.asarray(C), np.asarray(X)
@@ -193,7 +194,11 @@ def pmf(Y, C, X, num_p, num_m, num_feat, M, Mmiss, YorigInt, Einit, epochs=50, e
         raise ValueError("shape mismatch with num_p, num_m, num_feat")
     if np.shape(M) != Y.shape or not np.array_equal(Y, YorigInt * (np.asarray(M) != 0)):
         raise ValueError("the device path requires Y == YorigInt * M (as the experiment constructs it)")
-    res = pmf_batch(YorigInt, M, Mmiss, C, X, None, epochs=epochs, epsilon=epsilon, lmd=lmd, momentum=momentum, num_batches=num_batches)
+    return YorigInt
+
+
+def _reference_result(res, Einit, epochs):
+    """(Epred, Efull, RunTime), each (1, epochs + 1), of the first replica of a batch function's result"""
     Epred = np.full((1, epochs + 1), np.nan)
     Efull = np.zeros((1, epochs + 1))
     Epred[0, 0] = Efull[0, 0] = Einit
@@ -201,3 +206,13 @@ def pmf(Y, C, X, num_p, num_m, num_feat, M, Mmiss, YorigInt, Einit, epochs=50, e
     RunTime = np.zeros((1, epochs + 1))
     RunTime[0, 1:] = 1e-3 * res["elapsed_ms"] * np.arange(1, epochs + 1) / epochs      # epochs are not timed separately
     return Epred, Efull, RunTime
+
+
+def pmf(Y, C, X, num_p, num_m, num_feat, M, Mmiss, YorigInt, Einit, epochs=50, epsilon=50, lmd=0.01, momentum=0.8, num_batches=9):
+    """ExperimentImpute/PMF.py:43-159 on the device.  Returns (Epred, Efull, RunTime) like the reference, each (1, epochs + 1): column
+    0 is Einit, Epred is NaN beyond it (PMF predicts nothing online), RunTime spreads the kernels' time evenly over the epochs.  The
+    permutations come from the global numpy RNG, one numpy.random.permutation per epoch, as in the reference: a script that saves
+    and restores the RNG state around the call (PMF.py:218-224) gets the same repeats.  Requires Y == YorigInt * M."""
+    YorigInt = _reference_args(Y, C, X, num_p, num_m, num_feat, M, YorigInt)
+    res = pmf_batch(YorigInt, M, Mmiss, C, X, None, epochs=epochs, epsilon=epsilon, lmd=lmd, momentum=momentum, num_batches=num_batches)
+    return _reference_result(res, Einit, epochs)

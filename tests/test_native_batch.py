@@ -1,8 +1,9 @@
-"""The entry points without a handle (psmf_impute_run, psmf_impute_run_rows, psmf_ssm_run, psmf_ssm_run_ex, psmf_bocpd_run) share one host
-scaffold, rpsmf_amd/csrc/psmf_batch.h: the failure functor, the device check, typed transfers, the timed launch and the closing status
-loop are written there and nowhere else.  CPU only: the first tests read sources, in the manner of tests/test_native_ownership.py; the
-last compiles tests/native/batch_check.cpp -- the transfer helpers over memcpy and counting host allocators -- with the address and
-undefined-behaviour sanitizers and runs it as a child process (no device, and the test preloads nothing)."""
+"""The entry points without a handle (psmf_impute_run, psmf_impute_run_rows, psmf_ssm_run, psmf_ssm_run_ex, psmf_bocpd_run, psmf_pmf_run,
+psmf_bpmf_run) share one host scaffold, rpsmf_amd/csrc/psmf_batch.h: the failure functor, the device check, typed transfers, the chunk
+plan with its memory query, the per-item slots, the timed launch and the closing status loop are written there and nowhere else.  CPU
+only: the first tests read sources, in the manner of tests/test_native_ownership.py; the last compiles tests/native/batch_check.cpp --
+the transfer helpers, the per-item slots and the chunk plan over memcpy, counting host allocators and a made-up memory query -- with the
+address and undefined-behaviour sanitizers and runs it as a child process (no device, and the test preloads nothing)."""
 
 import os
 import re
@@ -11,11 +12,12 @@ import subprocess
 from conftest import ROOT
 from test_native_ownership import _body, _read, _strip_comments
 
-UNITS = ("psmf_impute.hip", "psmf_ssm.hip", "psmf_bocpd.hip")
+UNITS = ("psmf_impute.hip", "psmf_ssm.hip", "psmf_bocpd.hip", "psmf_pmf.hip", "psmf_bpmf.hip")
+CHUNKED = ("psmf_bocpd.hip", "psmf_pmf.hip", "psmf_bpmf.hip")       # the batch goes through the device in chunks
 BATCH = "psmf_batch.h"
-# what the scaffold does for its users: transfers, event timing, the device check
+# what the scaffold does for its users: transfers, event timing, the device check, the memory query of the chunk plan
 SCAFFOLD_CALLS = ("hipMemcpy(", "hipMemcpyAsync(", "hipMemset(", "hipEventRecord(", "hipEventSynchronize(", "hipEventElapsedTime(", "hipGetDeviceCount(",
-                  "hipSetDevice(", "hipLaunchKernel(", "hipFuncSetAttribute(")
+                  "hipSetDevice(", "hipLaunchKernel(", "hipFuncSetAttribute(", "hipMemGetInfo(")
 
 
 def _host_part(name):
@@ -37,7 +39,7 @@ def test_the_host_part_starts_behind_the_last_kernel():
 def test_the_units_leave_transfers_timing_and_the_device_check_to_the_scaffold():
     batch = _read(BATCH)
     for call in ("hipMemcpy", "hipMemset(", "hipEventRecord(", "hipEventSynchronize(", "hipEventElapsedTime(", "hipGetDeviceCount(", "hipSetDevice(",
-                 "hipLaunchKernel(", "hipFuncSetAttribute("):
+                 "hipLaunchKernel(", "hipFuncSetAttribute(", "hipMemGetInfo("):
         assert call in batch, f"{BATCH} is where {call} is written"
     for unit in UNITS:
         host = _host_part(unit)
@@ -49,6 +51,26 @@ def test_the_units_leave_transfers_timing_and_the_device_check_to_the_scaffold()
         for m in re.finditer(r"\bstruct\s+(\w*)\s*\{[^}]*operator\(\)", host):
             raise AssertionError(f"{unit}: a functor of its own (struct {m.group(1)}): the failure functor is EntryFail")
         assert "g_create_error" not in host or unit == "psmf_impute.hip", f"{unit}: g_create_error is written by EntryFail"
+
+
+def test_the_chunk_plan_and_the_per_item_transfers_are_the_scaffolds():
+    batch = _strip_comments(_read(BATCH))
+    assert "16 << 30" in batch and "budget" in batch and "int plan_chunk(" in batch
+    for name in sorted(n for n in os.listdir(os.path.join(ROOT, "rpsmf_amd", "csrc")) if n.endswith(".hip")):
+        text = _read(name)      # (comments included; psmf_capi.hip speaks of a kernel's "register budget", which is no memory budget)
+        assert "hipMemGetInfo" not in text and "16 << 30" not in text and "budget" not in text.replace("register budget", ""), \
+            f"{name}: the chunk plan is plan_chunk in {BATCH}"
+    for unit in CHUNKED:
+        host = _host_part(unit)
+        assert "plan_chunk(fail, B, " in host and "alloc_items(fail, items, chunk)" in host, unit
+        assert "fill_items(fail, items, s0, ns)" in host and "read_items(fail, items, s0, ns)" in host, unit
+        # a per-item buffer is stated once, in its slot: the chunk loop moves and clears nothing by name
+        loop = _body(host[host.index("for (int s0 = 0;"):], "for (int s0 = 0;")
+        for call in ("copy_in(", "copy_out(", "zero_n(", "alloc_n("):
+            assert call not in loop, f"{unit}: {call} inside the chunk loop"
+    for unit in ("psmf_pmf.hip", "psmf_bpmf.hip"):
+        host = _host_part(unit)
+        assert "cols_per_workgroup(n, sw." in host and "isfinite(v[i])" not in host and "all_finite(" in host, unit
 
 
 def test_g_create_error_is_written_by_the_failure_functor_alone():
