@@ -657,6 +657,58 @@ __device__ __forceinline__ void f3_ns_program(const BlockParams& b, const F3Blk&
     }                                                                                                      \
   } while (0)
 
+  // psmf_blk_filter3 (WIDE): the same fill and the same traces, straight-line.  Above, the source of every tile -- own column,
+  // sweep image, dump -- is chosen tile by tile: sixteen scalar branches in phase 0, the flags they test reloaded from spilled
+  // SGPRs, the image's addresses from scratch.  Here W always comes from the dump: a step that sweeps has its Y waves publish
+  // their columns of the image there, in the layout an iteration leaves (F3_W_PUBLISH in the sweep's exit, ordered by BF like the
+  // iterations' own stores), so the refill from the image is a cold block of that exit and phase 0 never asks where W is.  The one
+  // run-time choice left, X or Y wave, is made once for the own column and the trace together.  Same words, same values, same
+  // order of summation.
+#define F3_W_TILE(ti_, tj_)                                                                                \
+  do {                                                                                                     \
+    const f64x2* d2_ = reinterpret_cast<const f64x2*>(L.dump) + (size_t)((w_par * 4 + 2 + (tj_)) * 4) * 64 + lane; \
+    const f64x2 v0_ = d2_[((ti_) * 2) * 64], v1_ = d2_[((ti_) * 2 + 1) * 64];                              \
+    const double wv_[4] = {v0_[0], v0_[1], v1_[0], v1_[1]};                                                \
+    _Pragma("unroll") for (int q_ = 0; q_ < 4; ++q_)                                                       \
+      Wf[((ti_) * 2 + (tj_)) * 4 + q_] = F3_VALID(mk, ti_, tj_, q_) ? wv_[q_] : 0.0;                       \
+  } while (0)
+#define F3_W_AND_TRACES_WIDE()                                                                             \
+  do {                                                                                                     \
+    if (!(F3_KNOCK & 4))                                                                                   \
+    _Pragma("unroll") for (int ti_ = 0; ti_ < 2; ++ti_) F3_W_TILE(ti_, 1 - C);                             \
+    if (isX) {                                                                                             \
+      if (!(F3_KNOCK & 4))                                                                                 \
+      _Pragma("unroll") for (int ti_ = 0; ti_ < 2; ++ti_) F3_W_TILE(ti_, C);                               \
+      BLK_T(6);                                                                                            \
+      if (!(F3_KNOCK & 2)) {                                                                               \
+        double g1_ = 0.0;                                                                                  \
+        _Pragma("unroll") for (int ti_ = 0; ti_ < 2; ++ti_)                                                \
+          _Pragma("unroll") for (int q_ = 0; q_ < 4; ++q_)                                                 \
+            g1_ += G[(ti_ * 2 + C) * 4 + q_] * Xc[ti_ * 4 + q_];     /* G is zero outside r x r */         \
+        g1_ = wave_sum_f64_dpp(g1_);                                                                       \
+        if (lane == 0) L.gp[C] = g1_;                                                                      \
+      }                                                                                                    \
+    } else {                                                                                               \
+      if (!(F3_KNOCK & 4))                                                                                 \
+      _Pragma("unroll") for (int ti_ = 0; ti_ < 2; ++ti_)                                                  \
+        _Pragma("unroll") for (int q_ = 0; q_ < 4; ++q_)                                                   \
+          Wf[(ti_ * 2 + C) * 4 + q_] = F3_VALID(mk, ti_, C, q_) ? Xc[ti_ * 4 + q_] : 0.0;                  \
+      BLK_T(6);                                                                                            \
+      if (!(F3_KNOCK & 2)) {                                                                               \
+        double t1_ = 0.0;                                                                                  \
+        _Pragma("unroll") for (int q_ = 0; q_ < 4; ++q_) t1_ += F3_DIAG(mk, C, C, q_) ? G[(C * 2 + C) * 4 + q_] : 0.0; \
+        t1_ = wave_sum_f64_dpp(t1_);                                                                       \
+        if (lane == 0) L.tr[C] = t1_;                                                                      \
+      }                                                                                                    \
+    }                                                                                                      \
+  } while (0)
+  // the sweep's exit: a Y wave's column of W (just read from the image into Xc) into its slot of dump parity `par`
+#define F3_W_PUBLISH(parity_out)                                                                           \
+  do {                                                                                                     \
+    f64x2* dp_ = reinterpret_cast<f64x2*>(L.dump) + (size_t)(((parity_out) * 4 + role) * 4) * 64 + lane;   \
+    _Pragma("unroll") for (int e_ = 0; e_ < 4; ++e_) dp_[e_ * 64] = f64x2{Xc[2 * e_], Xc[2 * e_ + 1]};    \
+  } while (0)
+
 #define F3_ITERATE(parity_out)                                                                             \
   do {                                                                                                     \
     const double nr_ = f3_ns_iter<C, FULL>(Mf, Xc, Xa, Xn, mk);                                               \
@@ -694,7 +746,9 @@ __device__ __forceinline__ void f3_ns_program(const BlockParams& b, const F3Blk&
   for (int jb = 0; jb < k.nb; ++jb) {
     // phase 0 (wave 4 forms w, s, kappa meanwhile): what the step that just ended left to do off the critical path
     if (fetch_late) F3_FETCH_PARTNER(w_par);     // (after BF: the partner published it in the last phase it ran)
-    if (jb > 0) F3_W_AND_TRACES();
+    if (WIDE) {
+      if (jb > 0) F3_W_AND_TRACES_WIDE();
+    } else if (jb > 0) F3_W_AND_TRACES();
     BLK_T(7);
     f3_barrier();                                                     // ---- B1
     BLK_T(1);
@@ -873,6 +927,7 @@ __device__ __forceinline__ void f3_ns_program(const BlockParams& b, const F3Blk&
 #pragma unroll
           for (int to = 0; to < 2; ++to) Xa[to * 8 + ti * 4 + qq] = (float)im[row * F3_S + 16 * to + pcol];
         }
+      if (WIDE && isY) F3_W_PUBLISH(par);        // (the next phase 0 finds W where an iteration would have left it)
     } else {
       ++ctl.c_ns;
     }
@@ -921,7 +976,9 @@ __device__ __forceinline__ void f3_ns_program(const BlockParams& b, const F3Blk&
   BLK_TOUT();
   // ---- block end ----
   if (fetch_late) F3_FETCH_PARTNER(w_par);
-  if (k.nb > 0) F3_W_AND_TRACES();
+  if (WIDE) {
+    if (k.nb > 0) F3_W_AND_TRACES_WIDE();
+  } else if (k.nb > 0) F3_W_AND_TRACES();
   f3_barrier();                       // wave 4 has published pscale and 1 / omega of the last step
   const double ps = L.sc[F3_PSCALE], iom = L.sc[F3_IOM];
   if (k.to_lds) {
@@ -986,6 +1043,9 @@ __device__ __forceinline__ void f3_ns_program(const BlockParams& b, const F3Blk&
 #undef F3_ITERATE
 #undef F3_FETCH_PARTNER
 #undef F3_W_AND_TRACES
+#undef F3_W_AND_TRACES_WIDE
+#undef F3_W_TILE
+#undef F3_W_PUBLISH
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1097,12 +1157,34 @@ __device__ __forceinline__ void f3_v_program(const BlockParams& b, const F3Blk& 
       wj = part;                                                        // this half's share of w_j; completed in phase 1
     } else if ((isV1 || isV2) && !(F3_KNOCK & 32)) {
       double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+      // psmf_blk_filter3 (WIDE): the compiler already reads mu_bar sixteen bytes at a time, but three or four reads per group into
+      // the same registers, each group waited for before the next is issued: five LDS round trips in a row in the phase these two
+      // waves arrive last in.  All sixteen reads as ONE group, pinned in front of the products (64 more live registers, which
+      // the vector waves have).  Same words, same products, same four sums.
+      if (WIDE) {
+        double mb[32];
+        const f64x2* m2 = reinterpret_cast<const f64x2*>(L.mub);        // (16-byte aligned: blk_filter3_body's carve)
+#pragma unroll
+        for (int c = 0; c < 32; c += 2) { const f64x2 v = m2[c >> 1]; mb[c] = v[0]; mb[c + 1] = v[1]; }
+#pragma unroll
+        for (int c = 0; c < 32; c += 16)
+          asm volatile("" : "+v"(mb[c]), "+v"(mb[c + 1]), "+v"(mb[c + 2]), "+v"(mb[c + 3]), "+v"(mb[c + 4]), "+v"(mb[c + 5]), "+v"(mb[c + 6]), "+v"(mb[c + 7]),
+                            "+v"(mb[c + 8]), "+v"(mb[c + 9]), "+v"(mb[c + 10]), "+v"(mb[c + 11]), "+v"(mb[c + 12]), "+v"(mb[c + 13]), "+v"(mb[c + 14]), "+v"(mb[c + 15]));
+#pragma unroll
+        for (int c = 0; c < 32; c += 4) {
+          a0 += pr[c] * mb[c];
+          a1 += pr[c + 1] * mb[c + 1];
+          a2 += pr[c + 2] * mb[c + 2];
+          a3 += pr[c + 3] * mb[c + 3];
+        }
+      } else {
 #pragma unroll
       for (int c = 0; c < 32; c += 4) {
         a0 += pr[c] * L.mub[c];
         a1 += pr[c + 1] * L.mub[c + 1];
         a2 += pr[c + 2] * L.mub[c + 2];
         a3 += pr[c + 3] * L.mub[c + 3];
+      }
       }
       const double dot = (a0 + a1) + (a2 + a3);
       if (isV1) {

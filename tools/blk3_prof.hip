@@ -25,7 +25,7 @@ int main() {
   for (int a = 0; a < RB; ++a) for (int c = 0; c < RB; ++c) { double acc = 0; for (int i = 0; i < dd; ++i) acc += Z[(size_t)i * RB + a] * Z[(size_t)i * RB + c]; K[a * RB + c] = acc; }
   double *dK, *dA, *dB, *dKp; hipMalloc((void**)&dK, RB * RB * 8); hipMalloc((void**)&dA, RB * RM * 8); hipMalloc((void**)&dB, RB * RB * 8); hipMalloc((void**)&dKp, 1 << 20);
   hipMemcpy(dK, K.data(), RB * RB * 8, hipMemcpyHostToDevice);
-  BlockParams b{}; b.sp.st = st; b.sp.r = r; b.sp.d = 4096; b.sp.d_local = 4096; b.sp.use_ns = 1; b.sp.coef_update = 1; b.sp.eta_full = 1; b.sp.pbar_predict = 1;
+  BlockParams b{}; b.sp.st = st; b.sp.r = r; b.sp.d = getenv("D") ? atoi(getenv("D")) : 4096; b.sp.d_local = b.sp.d; b.sp.use_ns = 1; b.sp.coef_update = 1; b.sp.eta_full = 1; b.sp.pbar_predict = 1;
   b.sp.alpha = b.sp.beta = 1.0; b.sp.ns_predict = getenv("PRED") ? atoi(getenv("PRED")) : 7; b.sp.ns_far2 = 0.09; b.sp.ns_tol2 = getenv("TOL") ? atof(getenv("TOL")) * atof(getenv("TOL")) : 9e-14; b.K = dK; b.Acoef = dA; b.Bcoef = dB; b.Kpart = dKp; b.k0 = 0; b.nb = nb;
   const size_t lds = blk_filter3_lds_bytes();
   hipFuncSetAttribute((const void*)psmf_blk_filter3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -42,5 +42,14 @@ int main() {
   const char* nm[10] = {"phase 0 (idle)", "barrier waits", "phase 1 (M, it 0)", "phase 2 (it 1, G)", "further iterations", "phase F", "phase 0: W fill", "phase 0: traces", "-", "-"};
   printf("block of %d steps: %.1f us = %.2f us/step; err flag field k=%d\n", nb, ms * 1e3, ms * 1e3 / nb, 0);
   for (int w : {0, 2, 4, 5, 7}) { printf("wave %d (%s):\n", w, w < 2 ? "X" : (w < 4 ? "Y" : "V: phase 0 | barrier waits | phase 1 | phase 2 | to BF")); for (int q = 0; q < 10; ++q) printf("   %-22s %7.0f cycles/step\n", nm[q], (double)h[w * 12 + q] / nb); }
+  // arrival profile: cycles per step from the release of a barrier to the wave's arrival at the next one (its own work in that
+  // phase; the wave with the largest figure is the one the barrier waits for).  Inversion waves: B1 <- phase 0 (stamps 6 + 7),
+  // B2 <- phase 1 (2), BF <- phase 2, further iterations, phase F (3 + 4 + 5); vector waves: 0 | 2 | 3 + 4.  Stamp 1 = all waits.
+  printf("arrival (cycles per step)   BF->B1   B1->B2   B2->BF     waits\n");
+  for (int w = 0; w < 8; ++w) {
+    const unsigned long long* t = h + w * 12;
+    const double p0 = w < 4 ? t[6] + t[7] : t[0], p1 = t[2], p2 = w < 4 ? t[3] + t[4] + t[5] : t[3] + t[4];
+    printf("  wave %d (%s)            %8.0f %8.0f %8.0f  %8.0f\n", w, w < 2 ? "X" : (w < 4 ? "Y" : "V"), p0 / nb, p1 / nb, p2 / nb, (double)t[1] / nb);
+  }
   return 0;
 }
