@@ -650,6 +650,69 @@ int psmf_bpmf_run(const psmf_bpmf_config* cfg, const double* Y, const uint8_t* M
                   const double* mean_rating, const double* bartlett, const double* hyper_normals, const double* normals, double* P,
                   double* W, double* Efull, double* Yrec, int32_t* status, float* elapsed_ms);
 
+/* The convergence experiment (Convergence/main.m, the paper's Figure 1): n_iter sweeps of the PSMF filter over one series of n steps,
+ * each restarted from the first filtered state of the sweep before, every filtered posterior compared in Wasserstein-2 distance with
+ * that of the Kalman filter that knows the true C.  Float64 throughout, R diagonal, for a batch of independent replicas; one lane per
+ * replica with the whole state in registers. */
+typedef struct {
+  int32_t abi_version;
+  int32_t d, n, r;         /* Y is d x n, the state has r components: 1 <= r <= 4, r <= d <= 16, n >= 2                 */
+  int32_t batch;           /* independent replicas, >= 1                                                              */
+  int32_t n_iter;          /* sweeps of this call, >= 1 (the reference: 10000)                                         */
+  int32_t own_data;        /* 0: one Y, Ctrue and Kalman path for all replicas; 1: every replica has its own           */
+  int32_t want_moments;    /* also return C, Sxy and Sxx of every iteration (what ErM = ||Y - C Xps||_2 is formed from) */
+  int32_t device;
+} psmf_conv_config;
+
+/* The Kalman pass (main.m:15-34), once per call and series, from x = x0k, P = P0k, for t = 1 .. n:
+ *   Pp = P + Q,  S = (R + Ctrue Pp Ctrue^T)^-1,  x <- x + Pp Ctrue^T S (y_t - Ctrue x),  P <- Pp - Pp Ctrue^T S Ctrue Pp;  Xk(:,t) = x, Pk(:,:,t) = P
+ * One iteration (main.m:49-108), per replica, with V = v I at its top and (xp, Pprev) = (X0, P0) at t = 1, (Xps(:,t-1), Pps(:,:,t-1)) after:
+ *   1. Pp = Pprev + q_scale Q                         (q_scale, r_scale: main.m:44-45's knobs; the Kalman pass uses Q and R as given)
+ *   2. s = xp^T V xp
+ *   3. eta = trace(r_scale R + C Pp C^T) / d
+ *   4. S = (r_scale R + s I + C Pp C^T)^-1
+ *   5. Xps(:,t) = xp + Pp C^T S (y_t - C xp)
+ *   6. Pps(:,:,t) = Pp - Pp C^T S C Pp
+ *   7. C <- C + (y_t - C xp) xp^T V / (s + eta)
+ *   8. V <- V - V xp xp^T V / (s + eta)
+ *   9. Cerr(t) = ||C - Ctrue||_2
+ *  10. W(t) = W2(N(Xps_t, Pps_t), N(Xk_t, Pk_t)) for t >= 2, W(1) = 0
+ *   then avW = mean of W over all n entries, CerrI = ||C - Ctrue||_2 (the largest singular value), and the next iteration starts from
+ *   X0 = Xps(:,1), P0 = Pps(:,:,1) with the same C.  (main.m:54 writes P0ps = Pps(:,1), which is Pps(:,:,1) at r = 1, the reference's
+ *   only shape, and no covariance at r > 1.)
+ * S is applied through the r x r system (two Cholesky factorisations in registers per step; no d x d inverse is formed), and W2 through
+ * the eigenvalues of an r x r product (closed form at r <= 2, cyclic Jacobi above; no matrix square root).  A W2^2 that cancellation
+ * makes negative is returned as 0, where Matlab returns a complex number.  A launch covers at most K iterations, K the largest with
+ * n K <= 2^20 steps (PSMF_CONV_ITERS=k: at most k); the state crosses launches in device memory as float64: the same bits at every K.
+ * A batch that exceeds what is free on the device is processed in chunks of replicas (PSMF_CONV_CHUNK=n caps a chunk); both switches
+ * are read at every call and change no output bit.  Symmetric r x r matrices are PACKED where noted: the lower triangle by rows,
+ * nt = r (r + 1) / 2 elements, (i, j) at i (i + 1) / 2 + j.
+ *   Y          n x d, time-major (own_data: batch x n x d)
+ *   Ctrue      d x r (own_data: batch x d x r)
+ *   Q          r x r, symmetric positive definite;  Rdiag: d, the diagonal of R, > 0 (both shared by the replicas)
+ *   x0k, P0k   r and r x r, the start of the Kalman pass (own_data: batch x r, batch x r x r)
+ *   v, q_scale, r_scale   batch each: v > 0, q_scale >= 0, r_scale > 0
+ *   C, x0, P0  batch x d x r, batch x r, batch x r x r; in: the start, out: the final C, Xps(:,1) and Pps(:,:,1) of the last
+ *              iteration -- what a continuing call takes: two calls of k iterations give the bits of one call of 2 k
+ *   Xk, Pk     n x r and n x nt (packed), the Kalman path (own_data: batch x n x r, batch x n x nt)
+ *   avW, CerrI batch x n_iter
+ *   C_iter, Sxy, Sxx   batch x n_iter x (d x r | r x d | nt): the C at the end of every iteration, Sxy = sum_t Xps_t y_t^T and
+ *              Sxx = sum_t Xps_t Xps_t^T (packed); want_moments = 1, else NULL.  (E E^T = Y Y^T - C Sxy - (C Sxy)^T + C Sxx C^T for
+ *              E = Y - C Xps: the caller takes the d x d spectral norm.)
+ *   Xps, Pps, W, Cerr  batch x n x (r | nt packed | 1 | 1): every step of the call's last iteration
+ *   status     batch int32 or NULL, as in psmf_ssm_run: PSMF_OK, or PSMF_ERR_NUMERIC for a replica with a non-finite input, a pivot
+ *              of an r x r factorisation that is not positive or a state that is not finite; it stops there (its outputs are
+ *              unspecified) and the other replicas, those of its wave included, are untouched by it.  With status = NULL such a
+ *              replica fails the call (PSMF_ERR_NUMERIC)
+ *   elapsed_ms the kernels alone (HIP events, summed over the chunks), or NULL
+ * PSMF_ERR_ARG, by message: r outside 1 .. 4, d outside r .. 16 (for d < r the factorisation is not identifiable and the recursion
+ * amplifies rounding without bound), n < 2, n_iter < 1, batch < 1, a diagonal entry of R <= 0, a Q that is not symmetric, non-finite
+ * shared data.  PSMF_ERR_NUMERIC for the call where the shared Kalman pass loses positive definiteness. */
+int psmf_conv_run(const psmf_conv_config* cfg, const double* Y, const double* Ctrue, const double* Q, const double* Rdiag,
+                  const double* x0k, const double* P0k, const double* v, const double* q_scale, const double* r_scale, double* C,
+                  double* x0, double* P0, double* Xk, double* Pk, double* avW, double* CerrI, double* C_iter, double* Sxy, double* Sxx,
+                  double* Xps, double* Pps, double* W, double* Cerr, int32_t* status, float* elapsed_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -58,6 +58,10 @@ class PsmfBpmfConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("abi_version", "d", "n", "r", "batch", "epochs", "device", "want_rec")] + [("beta", C.c_double)]
 
 
+class PsmfConvConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("abi_version", "d", "n", "r", "batch", "n_iter", "own_data", "want_moments", "device")]
+
+
 class PsmfSsmConfigEx(C.Structure):
     _fields_ = PsmfSsmConfig._fields_ + [("robust", C.c_int32), ("fixed_lambda", C.c_int32), ("lambda0", C.c_double), ("alpha", C.c_double),
                                          ("beta", C.c_double)]
@@ -121,6 +125,7 @@ SIGNATURES = {
                                C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
     "psmf_bpmf_run": (C.c_int, [C.POINTER(PsmfBpmfConfig), _dp, _u8p, _u8p, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int32),
                                 C.POINTER(C.c_float)]),
+    "psmf_conv_run": (C.c_int, [C.POINTER(PsmfConvConfig)] + [_dp] * 23 + [C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
     "psmf_comm_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "psmf_device_pci_bus_id": (C.c_int, [C.c_int, C.c_char_p, C.c_int]),
     "psmf_upload_mask": (C.c_int, [C.c_void_p, _u8p, C.c_int64, C.c_int64]),

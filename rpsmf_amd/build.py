@@ -9,7 +9,8 @@ per-step engine (psmf_capi.hip), the series buffers -- resident or a ring: uploa
 (psmf_filter34.hip), the persistent per-step engine (psmf_pstep.hip), the four units of the entry points without a handle, host side on
 psmf_batch.h -- the masked small-shape engine with its route to the large-d handle (psmf_impute.hip), the batched filter with linear-Gaussian
 dynamics and an observation map (psmf_ssm.hip), the batched Bayesian online change-point detection (psmf_bocpd.hip), the batched
-probabilistic matrix factorisation (psmf_pmf.hip) and its Bayesian form, the Gibbs sampler (psmf_bpmf.hip) --
+probabilistic matrix factorisation (psmf_pmf.hip) and its Bayesian form, the Gibbs sampler (psmf_bpmf.hip) -- the convergence
+experiment, one lane per replica (psmf_conv.hip), also on psmf_batch.h,
 and the build identity (psmf_buildid.cpp: `psmf_build_id()` returns the SHA-256 of every source file and of the compiler flags the library was built
 from).  An object is stale when the hash of what its source reaches through `#include "..."`, followed transitively, differs from the one
 it was compiled from -- no list of dependencies is kept by hand.  `build_library` rebuilds whenever the whole-library hash differs from
@@ -41,7 +42,10 @@ FLAGS += os.environ.get("PSMF_CXXFLAGS", "").split()      # diagnostic builds (e
 LINK = ["-L/opt/rocm/lib", "-lrccl", "-Wl,-rpath,/opt/rocm/lib"]
 
 UNITS = ("psmf_capi.hip", "psmf_series.hip", "psmf_blocked.hip", "psmf_filter34.hip", "psmf_impute.hip", "psmf_pstep.hip", "psmf_ssm.hip",
-         "psmf_bocpd.hip", "psmf_pmf.hip", "psmf_bpmf.hip")
+         "psmf_bocpd.hip", "psmf_pmf.hip", "psmf_bpmf.hip", "psmf_conv.hip")
+# psmf_conv.hip: no contraction of a * b + c by the compiler -- the unit writes its fused multiply-adds out, so that the instances of
+# a shape (shared data, own data) are the same arithmetic and give the same bits
+UNIT_FLAGS = {"psmf_conv.hip": ["-ffp-contract=off"]}
 MAX_JOBS = 16
 
 
@@ -83,7 +87,7 @@ def _reached(src):
 
 def _units():
     """(object name, source, files whose content decides whether the object is stale, extra flags)"""
-    return [(u.replace(".hip", ".o"), os.path.join(CSRC, u), _reached(os.path.join(CSRC, u)), []) for u in UNITS]
+    return [(u.replace(".hip", ".o"), os.path.join(CSRC, u), _reached(os.path.join(CSRC, u)), UNIT_FLAGS.get(u, [])) for u in UNITS]
 
 
 def library_build_id():

@@ -30,7 +30,7 @@ struct Geometry {
 // Environment switches: one row each, and this struct is the library's only reader of the environment.  The rows
 // are read when a Switches is constructed: ONCE per handle, with the handle at psmf_create -- tests flip them between handles of one
 // process, and nothing on the per-block host path looks at the environment; the entry points without a handle (psmf_impute_*,
-// psmf_measure_copy_bandwidth, psmf_bocpd_run, psmf_pmf_run, psmf_bpmf_run) construct one at entry, on every call.
+// psmf_measure_copy_bandwidth, psmf_bocpd_run, psmf_pmf_run, psmf_bpmf_run, psmf_conv_run) construct one at entry, on every call.
 struct Switches {
   static bool set(const char* name) { return getenv(name) != nullptr; }                                  // present at all
   static bool on(const char* name) { const char* e = getenv(name); return e && atoi(e) != 0; }           // set and non-zero
@@ -77,6 +77,9 @@ struct Switches {
   // Bayesian probabilistic matrix factorisation (psmf_bpmf.hip)
   int bpmf_cols = as_int("PSMF_BPMF_COLS", 0);           // n > 0: columns per workgroup, rounded up to a multiple of 4 (0, unset: from n, at most 64 workgroups a replica)
   int bpmf_chunk = as_int("PSMF_BPMF_CHUNK", 0);         // n > 0: at most n replicas per chunk, still capped by free memory (0, unset: sized from free memory alone)
+  // convergence experiment (psmf_conv.hip)
+  int conv_chunk = as_int("PSMF_CONV_CHUNK", 0);         // n > 0: at most n replicas per chunk, still capped by free memory (0, unset: sized from free memory alone)
+  int conv_iters = as_int("PSMF_CONV_ITERS", 0);         // k > 0: at most k iterations per launch (0, unset: the most with n k <= 2^20 steps)
   // diagnostics
   bool dbg_breakdown = set("PSMF_DBG_BREAKDOWN");        // psmf_counters prints the in-situ breakdown of a filter3 launch
   bool host_timing = on("PSMF_HOST_TIMING");             // report slow host-side enqueues and waits
