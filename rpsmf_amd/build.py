@@ -3,8 +3,9 @@
     python -m rpsmf_amd.build            # libpsmf_hip.so  (only what is stale)
     python -m rpsmf_amd.build --force    # everything from source
 
-The library is a handful of translation units, compiled side by side (at most 16 at a time) and linked: the C ABI with the launched
-per-step engine (psmf_capi.hip), the series buffers -- resident or a ring: uploads, downloads, reductions over stored rows --
+The library is a handful of translation units, compiled side by side (at most 16 at a time) and linked: the C ABI (psmf_capi.hip), the launched
+per-step engine with the host driver of the persistent one (psmf_step.hip), the communicator (psmf_comm.hip), the noise rotation
+(psmf_rotation.hip), the series buffers -- resident or a ring: uploads, downloads, reductions over stored rows --
 (psmf_series.hip), the blocked engine's host driver and kernels (psmf_blocked.hip), the filter3 family of block filters
 (psmf_filter34.hip), the persistent per-step engine (psmf_pstep.hip), the four units of the entry points without a handle, host side on
 psmf_batch.h -- the masked small-shape engine with its route to the large-d handle (psmf_impute.hip), the batched filter with linear-Gaussian
@@ -42,7 +43,7 @@ FLAGS += os.environ.get("PSMF_CXXFLAGS", "").split()      # diagnostic builds (e
 LINK = ["-L/opt/rocm/lib", "-lrccl", "-Wl,-rpath,/opt/rocm/lib"]
 
 UNITS = ("psmf_capi.hip", "psmf_series.hip", "psmf_blocked.hip", "psmf_filter34.hip", "psmf_impute.hip", "psmf_pstep.hip", "psmf_ssm.hip",
-         "psmf_bocpd.hip", "psmf_pmf.hip", "psmf_bpmf.hip", "psmf_conv.hip")
+         "psmf_bocpd.hip", "psmf_pmf.hip", "psmf_bpmf.hip", "psmf_conv.hip", "psmf_step.hip", "psmf_comm.hip", "psmf_rotation.hip")
 # psmf_conv.hip: no contraction of a * b + c by the compiler -- the unit writes its fused multiply-adds out, so that the instances of
 # a shape (shared data, own data) are the same arithmetic and give the same bits
 UNIT_FLAGS = {"psmf_conv.hip": ["-ffp-contract=off"]}

@@ -49,7 +49,7 @@ struct F4Lds {
   } while (0)
 
 // The direct symmetric sweep of ONE 32 x 32 image (in place, A <- A^-1).  Round 4: by ONE vector wave (wave 4), wave-local on the
-// matrix cores (wave_sweep_tiles, psmf_ns.hip: the image as 2 x 2 tiles of 16 x 16 in its registers, no LDS exchange, no barrier
+// matrix cores (wave_sweep_tiles_m, psmf_ns.hip: the image as 2 x 2 tiles of 16 x 16 in its registers, no LDS exchange, no barrier
 // inside) -- where P ~ q both inversions of every step end up here, and a pivot round of the LDS-and-barrier sweep that the four
 // vector waves ran before cost 1 150 cycles against ~450.  (PSMF_F4_WAVE_SWEEP=0 at build time: that sweep, kept for A/B runs.)
 // Called by all 512 threads at the same point; the image was published before the barrier that precedes it.

@@ -168,8 +168,6 @@ void launch_blk_apply(psmf_filter* h, const psmf::BlockParams& b, hipStream_t st
   by_storage(h, [&](auto t) { hipLaunchKernelGGL(psmf::psmf_blk_apply_mfma<decltype(t)>, dim3(g), dim3(psmf::WG), lds, stream, b); });
 }
 
-}  // namespace
-
 int enqueue_block(psmf_filter* h, int64_t k0, int nb) {
   psmf::BlockParams b;
   fill_block_params(h, b, k0, nb);
@@ -290,6 +288,30 @@ int enqueue_blocks_pipelined(psmf_filter* h, int64_t k_begin, int64_t k_end) {
   // that launch (not the apply alone) is what host reads / the next run's preparation on the main stream have to follow
   if (chain) HIP_TRY(h, hipStreamWaitEvent(h->stream, h->evC, 0));
   HIP_TRY(h, hipGetLastError());
+  return PSMF_OK;
+}
+
+}  // namespace
+
+// the steps k_begin + 1 .. k_end of a prepared run (run_steps, psmf_capi.hip) on the blocked engine
+int run_blocks(psmf_filter* h, int64_t k_begin, int64_t k_end) {
+  int rc = PSMF_OK;
+  const bool pipe_off = !h->sw.block_pipe;
+  if (!pipe_off && k_end - k_begin > h->block_steps) {
+    rc = enqueue_blocks_pipelined(h, k_begin, k_end);
+    if (rc) return rc;
+    h->k_done = k_end;
+    return PSMF_OK;
+  }
+  int64_t k = k_begin;
+  while (k < k_end) {
+    const int nb = (int)((k_end - k) < h->block_steps ? (k_end - k) : h->block_steps);
+    rc = enqueue_block(h, k, nb);
+    if (rc) return rc;
+    k += nb;
+  }
+  HIP_TRY(h, hipGetLastError());
+  h->k_done = k_end;
   return PSMF_OK;
 }
 

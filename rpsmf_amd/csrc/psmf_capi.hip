@@ -1,12 +1,12 @@
-// C ABI of libpsmf_hip.so (include/psmf_hip.h): host-side orchestration of the large-d engine.
-// One handle = one HIP stream, one device-resident filter (or row shard), one hipGraph of
-// per-step launches replayed over the series.  No torch, no hipBLAS: plain HIP + RCCL.
+// C ABI of libpsmf_hip.so (include/psmf_hip.h): the glue of the large-d handle.  One handle = one HIP stream and one device-resident
+// filter (or row shard); this unit creates and destroys it, moves its state, checks and dispatches a run, and waits.  The engines
+// that advance the filter are units of their own -- launched per-step and persistent (psmf_step.hip, psmf_pstep.hip), blocked
+// (psmf_blocked.hip) -- as are the series buffers (psmf_series.hip), the communicator (psmf_comm.hip) and the noise rotation
+// (psmf_rotation.hip); the only kernels launched here are the four of psmf_handle_kernels.hip.  No torch, no hipBLAS: plain HIP + RCCL.
 // The batched entry points without a handle (psmf_impute_*, psmf_ssm_*, psmf_bocpd_run) live in the units of their engines.
 #include "psmf_host.h"
-#include "psmf_kernels.hip"
-#include "psmf_masked.hip"
-#include "psmf_rotate.hip"
-#include "psmf_wave16.hip"     // solve_block_wave: the per-step engine's solve block
+#include "psmf_dyn.hip"        // dyn_n_theta, dyn_term: the term structure of f_theta, for check_config and the host roll-out
+#include "psmf_handle_kernels.hip"
 
 #include <cmath>
 #include <cstddef>
@@ -14,272 +14,24 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
-#include <mutex>
 #include <string>
 #include <vector>
 
 thread_local std::string g_create_error;
-
-namespace {
-
-#ifndef PSMF_SWEEP_UNROLL
-#define PSMF_SWEEP_UNROLL 4
-#endif
-constexpr int kUnroll = PSMF_SWEEP_UNROLL;      // row passes (16-byte loads per lane) in flight in the sweep
-constexpr int kGramWG = 128;
-
-}  // namespace
-
-// The one exchange of the sharded engines: in-place sum of `count` float64 on the device over all ranks.  RCCL on the given
-// stream, or -- host-mediated communicator -- device -> pinned host -> caller's function -> device, synchronously.
-int all_reduce_sum(psmf_filter* h, double* buf, size_t count, hipStream_t s) {
-  if (h->host_fn) {
-    if (count > psmf_filter::kHostBufElems) return fail(h, PSMF_ERR_ARG, "host all-reduce: message larger than the staging buffer");
-    HIP_TRY(h, hipMemcpyAsync(h->host_buf, buf, count * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, spin_stream(s));
-    if (h->host_fn(h->host_ctx, h->host_buf, (int64_t)count) != 0) return fail(h, PSMF_ERR_RCCL, "host all-reduce callback reported a failure");
-    HIP_TRY(h, hipMemcpyAsync(buf, h->host_buf, count * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(h, spin_stream(s));        // the staging buffer is reused by the next call
-    return PSMF_OK;
-  }
-  NCCL_TRY(h, ncclAllReduce(buf, buf, count, ncclDouble, ncclSum, h->comm, s));
-  return PSMF_OK;
-}
-
-namespace {
-
-int next_pow2(int x) { int p = 1; while (p < x) p <<= 1; return p; }
-
-// A kernel whose dynamic LDS may need the opt-in (hipFuncAttributeMaxDynamicSharedMemorySize): psmf_create sets it for the
-// kernels the handle can launch (opt_in_lds), on the handle's device; the launchers only launch.
-template <typename Fn>
-struct LdsKernel { Fn fn; int threads; size_t lds; };
-
-typedef void (*sweep_fn_t)(StepParams);
-typedef void (*serial_fn_t)(StepParams, int);
-
-// loads in flight per lane of the row sweep.  The 256-thread instances of r > 32 (GS lanes x VEC elements > 32 columns) run ONE wave
-// per SIMD -- their solve block keeps 3 x 3 / 4 x 4 tile arrays in a wave's 512 registers, and a kernel has one register allocation --
-// so the row workgroups make up in depth what they lack in occupancy: 16 passes in flight instead of 4 (rows alone at d = 2e4, r = 40:
-// 17.5 us -> see docs/MEASUREMENTS.md).
-template <typename T, int GS, int NT>
-constexpr int sweep_unroll() { return (NT == 256 && GS * (int)(16 / sizeof(T)) > 32) ? 16 : kUnroll; }
-
-template <typename T, int NT>
-sweep_fn_t sweep_for_gs(int gs) {
-  switch (gs) {
-    case 1: return psmf::psmf_sweep_solve<T, 1, kUnroll, NT>;
-    case 2: return psmf::psmf_sweep_solve<T, 2, kUnroll, NT>;
-    case 4: return psmf::psmf_sweep_solve<T, 4, kUnroll, NT>;
-    case 8: return psmf::psmf_sweep_solve<T, 8, kUnroll, NT>;
-    case 16: return psmf::psmf_sweep_solve<T, 16, sweep_unroll<T, 16, NT>(), NT>;
-    case 32: return psmf::psmf_sweep_solve<T, 32, sweep_unroll<T, 32, NT>(), NT>;
-  }
-  return nullptr;
-}
-
-// threads per sweep workgroup (tuning knob PSMF_SWEEP_THREADS=256|512): 512 halves the number of
-// per-workgroup partial rows the serial stage has to read at the same number of waves per CU
-sweep_fn_t sweep_kernel(const psmf_filter* h) {
-  const int gs = h->geo.gs;
-  return by_storage(h, [&](auto t) { return h->geo.nt == 512 ? sweep_for_gs<decltype(t), 512>(gs) : sweep_for_gs<decltype(t), 256>(gs); });
-}
-
-bool serial_wide(const psmf_filter* h) { return h->geo.rpad >= 64 && h->sw.serial_wide; }
-
-serial_fn_t serial_kernel(const psmf_filter* h) {
-  switch (h->geo.rpad) {
-    case 8: return psmf::psmf_serial<8>;
-    case 16: return psmf::psmf_serial<16>;
-    case 32: return psmf::psmf_serial<32>;
-    default: return serial_wide(h) ? psmf::psmf_serial_wide : psmf::psmf_serial<64>;
-  }
-}
-
-void launch_sweep(psmf_filter* h) {
-  const int grid = h->geo.n_sweep_wg + (h->cfg.coef_update ? 1 : 0);
-  hipLaunchKernelGGL(sweep_kernel(h), dim3(grid), dim3(h->geo.nt), h->geo.sweep_lds, h->stream, h->sp);
-}
-
-void launch_serial(psmf_filter* h, int first) {
-  hipLaunchKernelGGL(serial_kernel(h), dim3(1), dim3(serial_wide(h) ? psmf::SERIAL_WIDE_NT : psmf::serial_threads(h->geo.rpad)), 0, h->stream, h->sp, first);
-}
-
-// one filter step on the stream (captured into the graph or launched eagerly)
-int enqueue_weighted_gram(psmf_filter* h);
-
-int enqueue_serial_mgram(psmf_filter* h, int first);
-
-int enqueue_step(psmf_filter* h) {
-  // non-uniform diagonal R: this step's weighted Gram, before the sweep rewrites C.  On a masked handle it is the masked weighted
-  // Gram of step k (mask row st->k, s_k from the serial stage of step k - 1): the sweep's block 0 solves with it, and the serial
-  // stage of step k then runs beside the UNWEIGHTED masked Gram of step k + 1 as on every masked handle
-  if (h->sp.rho_rows && h->cfg.coef_update) {
-    const int rc = enqueue_weighted_gram(h);
-    if (rc) return rc;
-  }
-  launch_sweep(h);
-  if (h->use_coll) {
-    if (!h->sp.tail_reduce) hipLaunchKernelGGL(psmf::psmf_reduce_partials, dim3(1), dim3(psmf::WG), 0, h->stream, h->sp);
-    const int rc = all_reduce_sum(h, h->st->red, h->geo.ps, h->stream);
-    if (rc) return rc;
-  }
-  if (h->cfg.masked) return enqueue_serial_mgram(h, 0);      // serial stage of this step beside the masked Gram of the next (psmf_masked.hip)
-  launch_serial(h, 0);
-  return PSMF_OK;
-}
-
-}  // namespace
-
-// Can the handle's next run go through the persistent per-step kernel?  (one rank, uniform diagonal R, random walk or cos-phase
-// dynamics, r <= 32, rows that fit the row workgroups' registers, unmasked or the masked PSMF / rPSMF filter; everything else keeps
-// the two -- masked: three -- launches per timestep)
-bool pstep_usable(const psmf_filter* h) {
-  return h->engine == 1 && h->ps_ok && h->sw.step_persistent && !h->use_coll && !h->host_fn && !h->sp.rho_rows &&
-         (h->cfg.masked == 0 || (h->cfg.masked == 1 && h->have_mask)) &&        // masked PSMF / rPSMF; MLE-SMF and TMF keep the two launches
-         !h->cfg.nonuniform_R && h->cfg.dyn_kind <= PSMF_DYN_COS_PHASE && !h->sp.solve_lds && !h->sp.q_mat;
-}
-
-namespace {
-
-int enqueue_gram_into(psmf_filter* h, double* Gout, const DevState* wst, const double* rho_rows) {
-  const int r = h->cfg.r;
-  const int rows = (h->cfg.d_local + kGramWG - 1) / kGramWG;
-  by_storage(h, [&](auto t) {
-    hipLaunchKernelGGL(psmf::psmf_gram_partial<decltype(t)>, dim3(kGramWG), dim3(psmf::WG), 0, h->stream,
-                       h->C.as<const decltype(t)>(), h->cfg.d_local, r, h->geo.rp, rows, h->gpart, wst, rho_rows);
-  });
-  hipLaunchKernelGGL(psmf::psmf_gram_reduce, dim3((r * r + 255) / 256), dim3(256), 0, h->stream,
-                     (const double*)h->gpart, kGramWG, r * r, Gout);
-  if (h->use_coll) { const int rc = all_reduce_sum(h, Gout, (size_t)r * r, h->stream); if (rc) return rc; }
-  return PSMF_OK;
-}
-constexpr int kMGramWG = 256;      // workgroups of the masked Gram (one partial each)
-
-// psmf_serial_mgram: block 0 = the serial stage, blocks 1 .. kMGramWG = the masked Gram of the next step (psmf_masked.hip)
-typedef LdsKernel<void (*)(StepParams, int, double*)> serial_mgram_t;
-template <int RPAD, typename T, int NT, int NW>
-serial_mgram_t serial_mgram_inst() { return {psmf::psmf_serial_mgram<RPAD, T, NT, NW>, NW * 64, (size_t)psmf::mgram_lds_doubles(NT, NW) * sizeof(double)}; }
-
-template <typename T>
-serial_mgram_t serial_mgram_for(int rpad, int r) {
-  if (rpad == 8) return serial_mgram_inst<8, T, 1, 16>();
-  if (rpad == 16) return serial_mgram_inst<16, T, 1, 16>();
-  if (rpad == 32) return serial_mgram_inst<32, T, 2, 8>();
-  return r <= 48 ? serial_mgram_inst<64, T, 3, 4>() : serial_mgram_inst<64, T, 4, 4>();
-}
-serial_mgram_t serial_mgram_kernel(const psmf_filter* h) { return by_storage(h, [&](auto t) { return serial_mgram_for<decltype(t)>(h->geo.rpad, h->cfg.r); }); }
-
-// serial stage of the step + masked Gram of the next, then the Gram's fixed-order reduction (and its all-reduce over the shards)
-int enqueue_serial_mgram(psmf_filter* h, int first) {
-  const serial_mgram_t k = serial_mgram_kernel(h);
-  hipLaunchKernelGGL(k.fn, dim3(1 + kMGramWG), dim3(k.threads), k.lds, h->stream, h->sp, first, h->gpart);
-  const int ne = h->cfg.r * h->cfg.r + 1;
-  // the shares of <G_m, Pbar> for the next sweep's eta: by the reduction itself, or -- row shards -- behind the all-reduce of the Gram
-  const int ntr = (ne + 63) / 64;
-  double* tpart = h->mg + ne + 1;
-  hipLaunchKernelGGL(psmf::psmf_mgram_reduce, dim3(ntr), dim3(512), 0, h->stream, (const double*)h->gpart, (int)kMGramWG, ne, h->mg,
-                     h->use_coll ? (const double*)nullptr : (const double*)h->st->Pbar, h->cfg.r, tpart);
-  if (h->use_coll) {
-    const int rc2 = all_reduce_sum(h, h->mg, (size_t)ne, h->stream);
-    if (rc2) return rc2;
-    hipLaunchKernelGGL(psmf::psmf_mgram_trace, dim3(ntr), dim3(64), 0, h->stream, (const double*)h->mg, (const double*)h->st->Pbar, h->cfg.r, tpart);
-  }
-  return PSMF_OK;
-}
-
-int enqueue_gram(psmf_filter* h) { return enqueue_gram_into(h, h->st->G, nullptr, nullptr); }
-
-// the weighted Gram of the current step (non-uniform diagonal R) on the matrix cores: psmf_wgram_mfma -- on a masked handle
-// psmf_mwgram_mfma, the masked weighted Gram -- + the masked Gram's reduction
-typedef LdsKernel<void (*)(StepParams, double*)> wgram_t;
-template <typename T, int NT>
-wgram_t wgram_inst(bool masked) {
-  return {masked ? psmf::psmf_mwgram_mfma<T, NT, 8> : psmf::psmf_wgram_mfma<T, NT, 8>, 8 * 64, (size_t)psmf::mgram_lds_doubles(NT, 8) * sizeof(double)};
-}
-
-template <typename T>
-wgram_t wgram_for(int rpad, int r, bool masked) {
-  if (rpad <= 16) return wgram_inst<T, 1>(masked);
-  if (rpad == 32) return wgram_inst<T, 2>(masked);
-  return r <= 48 ? wgram_inst<T, 3>(masked) : wgram_inst<T, 4>(masked);
-}
-wgram_t wgram_kernel(const psmf_filter* h) { return by_storage(h, [&](auto t) { return wgram_for<decltype(t)>(h->geo.rpad, h->cfg.r, h->cfg.masked != 0); }); }
-
-int enqueue_weighted_gram(psmf_filter* h) {
-  // PSMF_WGRAM_MFMA=0: the vector-unit Gram (it knows no mask: psmf_create refuses the switch on a masked handle)
-  if (!h->sw.wgram_mfma) return enqueue_gram_into(h, h->st->GR, h->st, h->sp.rho_rows);
-  const int r = h->cfg.r;
-  const wgram_t k = wgram_kernel(h);
-  hipLaunchKernelGGL(k.fn, dim3(kMGramWG), dim3(k.threads), k.lds, h->stream, h->sp, h->gpart);
-  hipLaunchKernelGGL(psmf::psmf_mgram_reduce, dim3((r * r + 63) / 64), dim3(512), 0, h->stream, (const double*)h->gpart, (int)kMGramWG, r * r,
-                     h->st->GR, (const double*)nullptr, r, (double*)nullptr);
-  if (h->use_coll) { const int rc2 = all_reduce_sum(h, h->st->GR, (size_t)r * r, h->stream); if (rc2) return rc2; }
-  return PSMF_OK;
-}
-
-int build_graph(psmf_filter* h, int chunk) {
-  destroy_graph(h);
-  HIP_TRY(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-  int rc = PSMF_OK;
-  for (int i = 0; i < chunk && rc == PSMF_OK; ++i) rc = enqueue_step(h);
-  hipGraph_t g = nullptr;
-  hipError_t e = hipStreamEndCapture(h->stream, &g);
-  if (rc != PSMF_OK) { if (g) hipGraphDestroy(g); return rc; }
-  if (e != hipSuccess) return fail(h, PSMF_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-  h->graph = g;
-  HIP_TRY(h, hipGraphInstantiate(&h->gexec, h->graph, nullptr, nullptr, 0));
-  h->chunk = chunk;
-  return PSMF_OK;
-}
-
-// O[M x N] = A[M x K] B[K x N] on the handle's stream (psmf_rotate.hip); the caller synchronises
-template <typename TA, typename TB, typename TO>
-int rot_gemm(psmf_filter* h, const TA* A, long long a_i, long long a_k, const TB* B, long long b_k, long long b_j, TO* O, long long o_i,
-             long long M, long long N, long long K) {
-  if (M <= 0 || N <= 0 || K <= 0) return PSMF_OK;
-  if (!A || !B || !O || (M + psmf::ROT_T - 1) / psmf::ROT_T > 65535) return fail(h, PSMF_ERR_ARG, "rotation: bad operand");
-  dim3 grid((unsigned)((N + psmf::ROT_T - 1) / psmf::ROT_T), (unsigned)((M + psmf::ROT_T - 1) / psmf::ROT_T));
-  hipLaunchKernelGGL((psmf::psmf_rot_gemm<TA, TB, TO>), grid, dim3(256), 0, h->stream, A, a_i, a_k, B, b_k, b_j, O, o_i, (int)M, (int)N, (int)K);
-  HIP_TRY(h, hipGetLastError());
-  return PSMF_OK;
-}
-
-// the dictionary (d x rp, storage type): dst = U^T src (fwd) or U src (back)
-int rot_dict(psmf_filter* h, const void* src, void* dst, bool fwd) {
-  const long long d = h->cfg.d_local, rp = h->geo.rp, r = h->cfg.r;
-  const long long ai = fwd ? 1 : d, ak = fwd ? d : 1;
-  return by_storage(h, [&](auto t) { return rot_gemm(h, (const double*)h->rotU, ai, ak, (const decltype(t)*)src, rp, 1LL, (decltype(t)*)dst, rp, d, r, d); });
-}
-
-}  // namespace
-
-// what the series unit (psmf_series.hip) calls besides run_steps: the captured graph holds buffer addresses, the scratch and
-// rotation buffers belong to the handle, and the rotation kernel is launched here
-void destroy_graph(psmf_filter* h) {
-  if (h->gexec) { hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }
-  if (h->graph) { hipGraphDestroy(h->graph); h->graph = nullptr; }
-  h->chunk = 0;
-}
 
 int ensure_scratch(psmf_filter* h, size_t bytes) {
   ALLOC_TRY(h, h->scratch.reserve(bytes));
   return PSMF_OK;
 }
 
-int ensure_rot_tmp(psmf_filter* h, size_t bytes) {
-  ALLOC_TRY(h, h->rot_tmp.reserve(bytes));
-  return PSMF_OK;
-}
-
-// rows of X (n x d, storage type, row stride d) times U (fwd: into rotated coordinates) or U^T (back), out of place: src -> dst
-int rot_rows(psmf_filter* h, const void* src, void* dst, long long n, bool fwd) {
-  const long long d = h->cfg.d_local;
-  const long long bk = fwd ? d : 1, bj = fwd ? 1 : d;
-  return by_storage(h, [&](auto t) { return rot_gemm(h, (const decltype(t)*)src, d, 1LL, (const double*)h->rotU, bk, bj, (decltype(t)*)dst, d, n, d, d); });
+// start of a run: the step counter, by a one-thread kernel on the handle's stream (psmf_step_host, psmf_step.hip, starts its runs with it too)
+void launch_prepare_k(psmf_filter* h, int64_t k) {
+  hipLaunchKernelGGL(psmf::psmf_prepare_k, dim3(1), dim3(1), 0, h->stream, h->st, (long long)k);
 }
 
 namespace {
+
+int next_pow2(int x) { int p = 1; while (p < x) p <<= 1; return p; }
 
 void compute_geometry(const psmf_config& c, Geometry& g, const int sweep_nt = 512) {
   g.vec = c.storage == PSMF_F64 ? 2 : 4;
@@ -318,54 +70,6 @@ void update_solve_dual(psmf_filter* h) {
   }
 }
 
-// Persistent kernels spin on device flags: two of them resident at once (two handles of one process on one device) could each
-// hold compute units the other needs.  They are serialised per device with an event chain.
-std::mutex g_ps_mutex;
-hipEvent_t g_ps_event[64] = {};      // raw on purpose, never destroyed: an owning static would call into a runtime that is already torn down at exit
-
-int launch_pstep(psmf_filter* h, int64_t k_begin, int64_t n) {
-  while (n > 0) {
-    const int64_t chunk = n > (int64_t)1 << 30 ? (int64_t)1 << 30 : n;
-    psmf::PstepParams q;
-    memset(&q, 0, sizeof(q));
-    q.sp = h->sp;
-    q.k_begin = k_begin;
-    q.n_steps = (int)chunk;
-    q.n_row_wg = h->ps_plan.n_row_wg;
-    q.rows_per_wg = h->ps_plan.rows_per_wg;
-    q.np = h->ps_plan.np;
-    q.ncol2 = h->ps_plan.ncol2;
-    q.flags = h->ps_comm.as<unsigned>();
-    q.pkt = reinterpret_cast<unsigned long long*>(h->ps_comm.as<char>() + h->ps_plan.off_pkt);
-    q.part = reinterpret_cast<double*>(h->ps_comm.as<char>() + h->ps_plan.off_part);
-    if (h->cfg.masked) {
-      char* base = h->ps_comm.as<char>();
-      q.masked = 1;
-      q.nge = h->ps_plan.nge;
-      q.slice_len = h->ps_plan.slice_len;
-      q.gflags = reinterpret_cast<unsigned*>(base + h->ps_plan.off_gflags);
-      q.sflags = reinterpret_cast<unsigned*>(base + h->ps_plan.off_sflags);
-      q.gpart = reinterpret_cast<double*>(base + h->ps_plan.off_gpart);
-      q.gslice = reinterpret_cast<double*>(base + h->ps_plan.off_gslice);
-      q.mg_out = h->mg;
-      q.mg_ntr = h->sp.mg_ntr;
-    }
-    q.prof = h->ps_prof;
-    h->ps_prof_steps = chunk;
-    std::lock_guard<std::mutex> lock(g_ps_mutex);
-    const int dev = h->cfg.device & 63;
-    if (!g_ps_event[dev]) HIP_TRY(h, hipEventCreateWithFlags(&g_ps_event[dev], hipEventDisableTiming));
-    else HIP_TRY(h, hipStreamWaitEvent(h->stream, g_ps_event[dev], 0));
-    HIP_TRY(h, hipMemsetAsync(h->ps_comm, 0, h->ps_plan.zero_bytes, h->stream));      // every polled word, before every launch
-    HIP_TRY(h, psmf::pstep_launch(q, h->cfg.storage == PSMF_F64, h->stream));
-    HIP_TRY(h, hipEventRecord(g_ps_event[dev], h->stream));
-    ++h->ps_launches;
-    k_begin += chunk;
-    n -= chunk;
-  }
-  return PSMF_OK;
-}
-
 // Give-up policy of filter3's Newton-Schulz starts (docs/MEASUREMENTS.md round 5).  A start whose residual exceeds
 // `far` is abandoned for the pivot-exact LDS sweep (15 us) and the next `skip` steps sweep unasked.  Where Lbar' = (I / q - W / q^2) / omega
 // cancels -- eigenvalues of Pbar far above q: the adversarial Q = 1e-8 -- every early step that iterates instead of sweeping costs
@@ -400,20 +104,7 @@ int prepare(psmf_filter* h, int64_t k_begin) {
     h->k_done = k_begin;
     return PSMF_OK;
   }
-  if (h->sp.track_g) {
-    int rc = enqueue_gram(h);
-    if (rc != PSMF_OK) return rc;
-  }
-  if (h->cfg.masked) {      // + the masked Gram of the run's first step (psmf_prepare_k set kq = k_begin)
-    const int rc = enqueue_serial_mgram(h, 1);
-    if (rc) return rc;
-  } else {
-    launch_serial(h, 1);
-  }
-  HIP_TRY(h, hipGetLastError());
-  h->need_prep = false;
-  h->k_done = k_begin;
-  return PSMF_OK;
+  return prepare_step(h, k_begin);
 }
 
 // f(theta, x, t) on the host, for the predict roll-out (psmf.py:182-188); same term structure as psmf_dyn.hip
@@ -510,24 +201,6 @@ int alloc_common(psmf_filter* h) {
   return PSMF_OK;
 }
 
-// persistent per-step engine (psmf_pstep.hip): the plan of a launch and its communication block, where the kernel applies
-int init_pstep(psmf_filter* h) {
-  const psmf_config* cfg = &h->cfg;
-  if (h->engine == 1 && h->sw.step_persistent && (cfg->r <= 32 || (h->sw.pstep_big && cfg->r <= 48 && cfg->masked == 0)) && cfg->masked <= 1 && !cfg->nonuniform_R &&
-      cfg->dyn_kind <= PSMF_DYN_COS_PHASE) {
-    hipDeviceProp_t prop;
-    HIP_TRY(h, hipGetDeviceProperties(&prop, cfg->device));
-    if (psmf::pstep_plan(cfg->d_local, cfg->r, prop.multiProcessorCount, cfg->storage == PSMF_F64, cfg->masked == 1, &h->ps_plan)) {
-      HIP_TRY(h, psmf::pstep_init());
-      ALLOC_TRY(h, h->ps_comm.alloc(h->ps_plan.total_bytes));
-      HIP_TRY(h, hipMemset(h->ps_comm, 0, h->ps_plan.total_bytes));
-      if (h->sw.pstep_prof) { ALLOC_TRY(h, h->ps_prof.alloc(64 * sizeof(long long))); HIP_TRY(h, hipMemset(h->ps_prof, 0, 64 * sizeof(long long))); }
-      h->ps_ok = true;
-    }
-  }
-  return PSMF_OK;
-}
-
 void fill_step_params(psmf_filter* h) {
   const psmf_config* cfg = &h->cfg;
   StepParams& sp = h->sp;
@@ -579,20 +252,6 @@ void fill_step_params(psmf_filter* h) {
   sp.b1 = cfg->adam_b1; sp.b2 = cfg->adam_b2;
 }
 
-// PSMF_PSTEP_PROF=1 with a -DPSTEP_PROF build: the per-phase clock sums of the last launch, at psmf_destroy
-void print_pstep_prof(psmf_filter* h) {
-  long long pf[64];
-  if (!h->ps_prof || hipMemcpy(pf, h->ps_prof, sizeof(pf), hipMemcpyDeviceToHost) != hipSuccess || h->ps_prof_steps <= 0) return;
-  fprintf(stderr, "[pstep prof] cycles per timestep over the last launch (%lld steps), d_local %d r %d:\n", h->ps_prof_steps, h->cfg.d_local, h->cfg.r);
-  const char* grp[3] = {"hub workers", "solve wave ", "row wg 0   "};
-  const int base[3] = {0, 16, 24}, cnt[3] = {11, 3, 8};
-  for (int g = 0; g < 3; ++g) {
-    fprintf(stderr, "  %s:", grp[g]);
-    for (int i = 0; i < cnt[g]; ++i) fprintf(stderr, " %7.0f", (double)pf[base[g] + i] / (double)h->ps_prof_steps);
-    fprintf(stderr, "\n");
-  }
-}
-
 }  // namespace
 
 extern "C" {
@@ -628,11 +287,7 @@ int psmf_create(psmf_handle* out, const psmf_config* cfg_in) {
                                "not on a masked handle with nonuniform_R = 1");
   if (!rc) rc = alloc_common(h);
   if (!rc && h->engine == 2) rc = init_blocked(h);
-  // dynamic LDS beyond the default limit: opted in here, per handle and so on the handle's device, for the kernels it can launch
-  if (!rc && h->geo.sweep_lds > 48 * 1024) rc = opt_in_lds(h, (const void*)sweep_kernel(h), h->geo.sweep_lds);
-  if (!rc && cfg->masked) { const serial_mgram_t k = serial_mgram_kernel(h); rc = opt_in_lds(h, (const void*)k.fn, k.lds); }
-  if (!rc && cfg->nonuniform_R) { const wgram_t k = wgram_kernel(h); rc = opt_in_lds(h, (const void*)k.fn, k.lds); }
-  if (!rc) rc = init_pstep(h);
+  if (!rc) rc = init_step(h);
   if (rc) return bail(rc);
   fill_step_params(h);
   // the zero-fills above ran on the null stream; the handle's own streams are non-blocking
@@ -800,64 +455,7 @@ int run_steps(psmf_filter* h, int64_t k_begin, int64_t k_end) {
     rc = prepare(h, k_begin);
     if (rc) return rc;
   }
-  int64_t n = k_end - k_begin;
-  if (h->engine == 2) {
-    const bool pipe_off = !h->sw.block_pipe;
-    if (!pipe_off && k_end - k_begin > h->block_steps) {
-      rc = enqueue_blocks_pipelined(h, k_begin, k_end);
-      if (rc) return rc;
-      h->k_done = k_end;
-      return PSMF_OK;
-    }
-    int64_t k = k_begin;
-    while (k < k_end) {
-      const int nb = (int)((k_end - k) < h->block_steps ? (k_end - k) : h->block_steps);
-      rc = enqueue_block(h, k, nb);
-      if (rc) return rc;
-      k += nb;
-    }
-    HIP_TRY(h, hipGetLastError());
-    h->k_done = k_end;
-    return PSMF_OK;
-  }
-  const int64_t refresh = h->cfg.gram_refresh > 0 && h->sp.track_g ? h->cfg.gram_refresh : 0;
-  while (n > 0) {
-    int64_t seg = n;
-    if (refresh) {
-      const int64_t to_next = refresh - (h->k_done % refresh);
-      if (to_next < seg) seg = to_next;
-    }
-    int64_t left = seg;
-    if (pstep_usable(h)) {      // the whole segment in ONE launch: C on chip, hand-offs through device flags (psmf_pstep.hip)
-      rc = launch_pstep(h, h->k_done, left);
-      if (rc) return rc;
-      left = 0;
-    }
-    if (h->cfg.use_graph && !h->host_fn) {   // (a host-mediated all-reduce cannot be captured)
-      const int want = 256;
-      if (left >= want && h->chunk != want) {
-        rc = build_graph(h, want);
-        if (rc) return rc;
-      }
-      while (h->chunk > 0 && left >= h->chunk) {
-        HIP_TRY(h, hipGraphLaunch(h->gexec, h->stream));
-        left -= h->chunk;
-      }
-    }
-    for (; left > 0; --left) {
-      rc = enqueue_step(h);
-      if (rc) return rc;
-    }
-    HIP_TRY(h, hipGetLastError());
-    h->k_done += seg;
-    n -= seg;
-    if (refresh && n > 0 && h->k_done % refresh == 0) {
-      rc = enqueue_gram(h);
-      if (rc) return rc;
-      launch_serial(h, 1);   // recompute eta / N / kappa of the next step with the exact Gram
-    }
-  }
-  return PSMF_OK;
+  return h->engine == 2 ? run_blocks(h, k_begin, k_end) : run_step_engine(h, k_begin, k_end);
 }
 
 extern "C" {
@@ -971,24 +569,6 @@ static int restore_after_timing(psmf_filter* h, const TimingSave& s) {
   return restore_step_records(h, s.rec);
 }
 
-static int time_step_kernels(psmf_filter* h, int which, int iters, float* avg_us) {
-  {  // the sweep reads y_k / writes y_hat_k at the step counter: point it at a valid row of the series
-    long long k0 = h->sp.series_t0;
-    HIP_TRY(h, hipMemcpy(&h->st->k, &k0, sizeof(k0), hipMemcpyHostToDevice));
-  }
-  // which = 1 times the full serial stage (first = 0: reduction of the partials left by the last
-  // sweep, updates, next-step preparation); the step counter it increments is reset with the state
-  for (int i = 0; i < 3; ++i) { if (which == 0) launch_sweep(h); else launch_serial(h, 0); }
-  HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
-  for (int i = 0; i < iters; ++i) { if (which == 0) launch_sweep(h); else launch_serial(h, 0); }
-  HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
-  HIP_TRY(h, hipEventSynchronize(h->ev1));
-  float ms = 0.f;
-  HIP_TRY(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-  *avg_us = ms * 1000.f / iters;
-  return PSMF_OK;
-}
-
 int psmf_time_kernel(psmf_handle h, int which, int iters, float* avg_us) {
   if (!h || !avg_us || iters < 1 || which < 0 || which > 2) return PSMF_ERR_ARG;
   if (!h->have_state || !h->Y) return fail(h, PSMF_ERR_STATE, "psmf_time_kernel: needs state and series");
@@ -1021,17 +601,6 @@ int psmf_geometry(psmf_handle h, int32_t* out7) {
   if (!h || !out7) return PSMF_ERR_ARG;
   out7[0] = h->geo.n_sweep_wg; out7[1] = h->geo.rows_per_wg; out7[2] = h->geo.rp; out7[3] = h->geo.gs;
   out7[4] = h->chunk; out7[5] = h->engine; out7[6] = h->block_steps;
-  return PSMF_OK;
-}
-
-int psmf_step_plan(psmf_handle h, int32_t* out5) {
-  if (!h || !out5) return PSMF_ERR_ARG;
-  if (set_device(h) != PSMF_OK) return PSMF_ERR_HIP;
-  int n_cu = 0;
-  HIP_TRY(h, hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, h->cfg.device));
-  out5[0] = pstep_usable(h) ? 1 : 0;
-  out5[1] = h->ps_ok ? h->ps_plan.n_row_wg : 0; out5[2] = h->ps_ok ? h->ps_plan.rows_per_wg : 0; out5[3] = h->ps_ok ? h->ps_plan.np : 0;
-  out5[4] = n_cu;
   return PSMF_OK;
 }
 
@@ -1118,8 +687,7 @@ int psmf_project(psmf_handle h, const double* mu, int64_t n_pred, double* out) {
   if (h->rotU) {                         // non-diagonal R: C here is U^T C -- rotate the projections back
     rc = ensure_rot_tmp(h, obytes);
     if (rc) return rc;
-    rc = rot_gemm(h, (const double*)dout, (long long)dl, 1LL, (const double*)h->rotU, 1LL, (long long)dl, h->rot_tmp.as<double>(), (long long)dl,
-                  (long long)n_pred, (long long)dl, (long long)dl);
+    rc = rot_rows_back_f64(h, dout, h->rot_tmp.as<double>(), n_pred);
     if (rc) return rc;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     HIP_TRY(h, hipMemcpy(out, h->rot_tmp, obytes, hipMemcpyDeviceToHost));
@@ -1148,72 +716,6 @@ int psmf_predict_sq_error(psmf_handle h, int64_t T, int64_t n_pred, const double
   return sq_error_sum(h, h->stream, PSMF_F64, dyp, dyt, n, dyt + n, out);
 }
 
-int psmf_comm_unique_id(void* id_out) {
-  if (!id_out) return PSMF_ERR_ARG;
-  static_assert(sizeof(ncclUniqueId) <= PSMF_UNIQUE_ID_BYTES, "unique id size");
-  ncclUniqueId id;
-  if (ncclGetUniqueId(&id) != ncclSuccess) return fail(nullptr, PSMF_ERR_RCCL, "ncclGetUniqueId failed");
-  memset(id_out, 0, PSMF_UNIQUE_ID_BYTES);
-  memcpy(id_out, &id, sizeof(id));
-  return PSMF_OK;
-}
-
-int psmf_comm_init(psmf_handle h, int nranks, int rank, const void* unique_id) {
-  if (!h || !unique_id || nranks < 1 || rank < 0 || rank >= nranks) return fail(h, PSMF_ERR_ARG, "psmf_comm_init: bad argument");
-  if (h->rotU) return fail(h, PSMF_ERR_STATE, "psmf_comm_init: a handle with a noise rotation (non-diagonal R) is one shard by construction");
-  int rc = set_device(h);
-  if (rc) return rc;
-  ncclUniqueId id;
-  memcpy(&id, unique_id, sizeof(id));
-  NCCL_TRY(h, ncclCommInitRank(&h->comm, nranks, id, rank));
-  h->nranks = nranks;
-  h->rank = rank;
-  {
-    // Connect now: the first collective of each message size sets up its channels (seconds on 8 GPUs), and in the pipelined
-    // block engine a filter kernel would be polling for its result meanwhile.  Same sizes, same streams as the engines use.
-    const size_t xg_elems = (size_t)(psmf::RB + psmf::XGB) * psmf::XGB;
-    Dev<double> tmp;
-    ALLOC_TRY(h, tmp.alloc(xg_elems * sizeof(double)));
-    HIP_TRY(h, hipMemsetAsync(tmp, 0, xg_elems * sizeof(double), h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    const size_t sizes[4] = {(size_t)h->cfg.r + 1, (size_t)h->cfg.r * h->cfg.r, (size_t)psmf::RB * psmf::RB, xg_elems};
-    hipStream_t streams[2] = {h->stream, h->bulk};
-    for (int si = 0; si < 2; ++si) {
-      if (!streams[si]) continue;
-      for (int zi = 0; zi < 4; ++zi) {
-        const ncclResult_t e = ncclAllReduce(tmp, tmp, sizes[zi], ncclDouble, ncclSum, h->comm, streams[si]);
-        if (e != ncclSuccess) return fail(h, PSMF_ERR_RCCL, std::string("warm-up all-reduce: ") + ncclGetErrorString(e));
-      }
-      const hipError_t he = hipStreamSynchronize(streams[si]);
-      if (he != hipSuccess) return fail(h, PSMF_ERR_HIP, std::string("warm-up all-reduce: ") + hipGetErrorString(he));
-    }
-  }
-  h->use_coll = nranks > 1 || h->sw.force_collective;
-  h->sp.external_reduce = (h->use_coll || h->sp.tail_reduce) ? 1 : 0;
-  destroy_graph(h);
-  h->need_prep = true;
-  return PSMF_OK;
-}
-
-int psmf_comm_abort(psmf_handle h) {
-  if (!h) return PSMF_ERR_ARG;
-  int rc = set_device(h);
-  if (rc) return rc;
-  if (h->comm) {
-    // ncclCommAbort, not ncclCommDestroy: destroy waits for outstanding work and for its peers, and the caller is here because
-    // some peer never joined (or stopped answering)
-    const ncclResult_t e = ncclCommAbort(h->comm);
-    h->comm = nullptr;
-    if (e != ncclSuccess) return fail(h, PSMF_ERR_RCCL, std::string("ncclCommAbort: ") + ncclGetErrorString(e));
-  }
-  h->nranks = 1; h->rank = 0;
-  h->use_coll = false;
-  h->sp.external_reduce = h->sp.tail_reduce;
-  destroy_graph(h);
-  h->need_prep = true;
-  return PSMF_OK;
-}
-
 int psmf_set_row_noise(psmf_handle h, const double* rho_rows, double rho_mean) {
   if (!h || !rho_rows || !(rho_mean > 0.0)) return fail(h, PSMF_ERR_ARG, "psmf_set_row_noise: bad argument");
   if (!h->cfg.nonuniform_R) return fail(h, PSMF_ERR_STATE, "psmf_set_row_noise: the handle was created with nonuniform_R = 0");
@@ -1228,48 +730,6 @@ int psmf_set_row_noise(psmf_handle h, const double* rho_rows, double rho_mean) {
   h->sp.rho_mean = rho_mean;
   destroy_graph(h);
   h->need_prep = true;
-  return PSMF_OK;
-}
-
-int psmf_set_noise_rotation(psmf_handle h, const double* U, const double* lam) {
-  if (!h || !U || !lam) return fail(h, PSMF_ERR_ARG, "psmf_set_noise_rotation: bad argument");
-  if (!h->cfg.nonuniform_R) return fail(h, PSMF_ERR_STATE, "psmf_set_noise_rotation: the handle was created with nonuniform_R = 0");
-  if (h->cfg.masked) return fail(h, PSMF_ERR_STATE, "psmf_set_noise_rotation: not on a masked handle (the mask selects rows of the ORIGINAL coordinates: it is not equivariant under a rotation)");
-  if (h->use_coll || h->cfg.d_local != h->cfg.d)
-    return fail(h, PSMF_ERR_STATE, "psmf_set_noise_rotation: a non-diagonal R couples all rows: one shard only (d_local = d, no communicator)");
-  if (h->ring_slots) return fail(h, PSMF_ERR_STATE, std::string("psmf_set_noise_rotation") + kRingRefused + ": the rotation of the rows would have to run on the copy stream");
-  if (h->Y || h->have_state) return fail(h, PSMF_ERR_STATE, "psmf_set_noise_rotation: call it before psmf_set_state / psmf_upload_series");
-  const size_t d = (size_t)h->cfg.d;
-  double tr = 0.0;
-  for (size_t i = 0; i < d; ++i) {
-    if (!(lam[i] >= 0.0)) return fail(h, PSMF_ERR_ARG, "psmf_set_noise_rotation: eigenvalues of R must be non-negative");
-    tr += lam[i];
-  }
-  if (!(tr > 0.0)) return fail(h, PSMF_ERR_ARG, "psmf_set_noise_rotation: tr(R) must be positive");
-  if (d > (size_t)PSMF_ROTATION_DMAX)
-    return fail(h, PSMF_ERR_ARG, "psmf_set_noise_rotation: a non-diagonal R is supported up to d = 32768 (the handle keeps the d x d eigenvector matrix "
-                                 "resident: 8 d^2 bytes); beyond that use a diagonal R or backend=\"numpy\"");
-  // orthonormality over ALL of U in O(d^2): U^T (U z) = z for two probe vectors z (+-1 entries from a fixed generator).  A column
-  // pair that is not orthonormal shows in (U^T U - I) z unless z lies in that matrix's null space -- two independent sign
-  // patterns do not.  (The full check U^T U = I is O(d^3); a C caller with a wrong U used to get a silently wrong filter.)
-  {
-    std::vector<double> z(d), t(d), u(d);
-    unsigned long long lcg = 0x9E3779B97F4A7C15ull;
-    for (int probe = 0; probe < 2; ++probe) {
-      for (size_t i = 0; i < d; ++i) { lcg = lcg * 6364136223846793005ull + 1442695040888963407ull; z[i] = (lcg >> 63) ? 1.0 : -1.0; }
-      for (size_t i = 0; i < d; ++i) { double a = 0.0; const double* row = U + i * d; for (size_t k = 0; k < d; ++k) a += row[k] * z[k]; t[i] = a; }
-      for (size_t k = 0; k < d; ++k) u[k] = 0.0;
-      for (size_t i = 0; i < d; ++i) { const double ti = t[i]; const double* row = U + i * d; for (size_t k = 0; k < d; ++k) u[k] += row[k] * ti; }
-      double worst = 0.0;
-      for (size_t k = 0; k < d; ++k) worst = std::fmax(worst, std::fabs(u[k] - z[k]));
-      if (!(worst <= 1e-8 * std::sqrt((double)d) + 1e-10))
-        return fail(h, PSMF_ERR_ARG, "psmf_set_noise_rotation: the columns of U are not orthonormal (U^T U z != z)");
-    }
-  }
-  int rc = psmf_set_row_noise(h, lam, tr / (double)d);
-  if (rc) return rc;
-  ALLOC_TRY(h, h->rotU.reserve(d * d * sizeof(double)));
-  HIP_TRY(h, hipMemcpy(h->rotU, U, d * d * sizeof(double), hipMemcpyHostToDevice));
   return PSMF_OK;
 }
 
@@ -1334,55 +794,6 @@ int psmf_set_q_matrix_schedule(psmf_handle h, const double* Q_k, int64_t n) {
   return PSMF_OK;
 }
 
-int psmf_step_host(psmf_handle h, int64_t k, const double* mu_bar, const double* P_bar, double* mu_out, double* gf_out,
-                   double* P_out, double* Q_out) {
-  if (!h || !mu_bar || !P_bar) return PSMF_ERR_ARG;
-  if (h->cfg.dyn_kind != PSMF_DYN_HOST) return fail(h, PSMF_ERR_STATE, "psmf_step_host: the handle was not created with dyn_kind = PSMF_DYN_HOST");
-  if (!h->have_state) return fail(h, PSMF_ERR_STATE, "psmf_step_host: set_state (C, V, P, mu) first");
-  if (!h->Y) return fail(h, PSMF_ERR_STATE, "psmf_step_host: upload_series first");
-  if (k < 0 || k >= h->T_cap) return fail(h, PSMF_ERR_ARG, "psmf_step_host: step outside the uploaded series");
-  if (h->sched && k + 1 >= h->sched_n) return fail(h, PSMF_ERR_ARG, "psmf_step_host: step beyond the R / Q schedules");
-  int rc = set_device(h);
-  if (rc) return rc;
-  const int r = h->cfg.r;
-  if (h->need_prep || h->k_done != k) {
-    hipLaunchKernelGGL(psmf::psmf_prepare_k, dim3(1), dim3(1), 0, h->stream, h->st, (long long)k);
-    if (h->mu_hist)
-      HIP_TRY(h, hipMemcpyAsync(h->mu_hist + (size_t)(k - h->sp.series_t0) * r, h->st->mu, r * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    if (h->sp.track_g) { rc = enqueue_gram(h); if (rc) return rc; }
-    h->need_prep = false;
-    h->k_done = k;
-  }
-  HIP_TRY(h, hipMemcpyAsync(h->st->mu_bar, mu_bar, r * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(h->st->Pbar, P_bar, (size_t)r * r * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  launch_serial(h, 1);          // w, s, eta, N, kappa of this step from the uploaded mu_bar, P_bar
-  rc = enqueue_step(h);         // row sweep (+ r x r solve), all-reduce, serial stage (stops before the next prediction)
-  if (rc) return rc;
-  HIP_TRY(h, hipGetLastError());
-  h->k_done = k + 1;
-  rc = psmf_sync(h);
-  if (rc) return rc;
-  if (mu_out) HIP_TRY(h, hipMemcpy(mu_out, h->st->mu, r * sizeof(double), hipMemcpyDeviceToHost));
-  if (gf_out) HIP_TRY(h, hipMemcpy(gf_out, h->st->gf, r * sizeof(double), hipMemcpyDeviceToHost));
-  if (P_out) HIP_TRY(h, hipMemcpy(P_out, h->st->P, (size_t)r * r * sizeof(double), hipMemcpyDeviceToHost));
-  if (Q_out) HIP_TRY(h, hipMemcpy(Q_out, h->st->Q, (size_t)r * r * sizeof(double), hipMemcpyDeviceToHost));
-  return PSMF_OK;
-}
-
-int psmf_comm_info(psmf_handle h, int32_t* out4) {
-  if (!h || !out4) return PSMF_ERR_ARG;
-  out4[0] = h->host_fn ? 2 : (h->comm ? 1 : 0);
-  out4[1] = h->nranks; out4[2] = h->rank; out4[3] = h->cfg.device;
-  if (h->comm) {          // what RCCL itself says about the communicator the exchanges run on
-    int n = -1, rk = -1, dev = -1;
-    NCCL_TRY(h, ncclCommCount(h->comm, &n));
-    NCCL_TRY(h, ncclCommUserRank(h->comm, &rk));
-    NCCL_TRY(h, ncclCommCuDevice(h->comm, &dev));
-    out4[1] = n; out4[2] = rk; out4[3] = dev;
-  }
-  return PSMF_OK;
-}
-
 int psmf_device_pci_bus_id(int device, char* buf, int len) {
   if (!buf || len < 16) return fail(nullptr, PSMF_ERR_ARG, "psmf_device_pci_bus_id: buffer of at least 16 bytes");
   if (hipDeviceGetPCIBusId(buf, len, device) != hipSuccess) { (void)hipGetLastError(); return fail(nullptr, PSMF_ERR_HIP, "hipDeviceGetPCIBusId failed"); }
@@ -1429,24 +840,6 @@ int psmf_measure_copy_bandwidth(int device, size_t bytes, int iters, double* gbp
   float ms = 0.f;
   HIP_TRY(h, hipEventElapsedTime(&ms, e0, e1));
   *gbps = 2.0 * (double)(n16 * 16) * iters / (ms * 1e-3) / 1e9;     // read + write
-  return PSMF_OK;
-}
-
-int psmf_comm_init_host(psmf_handle h, int nranks, int rank, psmf_allreduce_fn fn, void* ctx) {
-  if (!h || !fn || nranks < 1 || rank < 0 || rank >= nranks) return fail(h, PSMF_ERR_ARG, "psmf_comm_init_host: bad argument");
-  if (h->rotU) return fail(h, PSMF_ERR_STATE, "psmf_comm_init_host: a handle with a noise rotation (non-diagonal R) is one shard by construction");
-  if (h->comm) return fail(h, PSMF_ERR_STATE, "psmf_comm_init_host: the handle already has an RCCL communicator");
-  int rc = set_device(h);
-  if (rc) return rc;
-  if (!h->host_buf) HIP_TRY(h, hipHostMalloc(h->host_buf.put(), psmf_filter::kHostBufElems * sizeof(double), hipHostMallocDefault));
-  h->host_fn = fn;
-  h->host_ctx = ctx;
-  h->nranks = nranks;
-  h->rank = rank;
-  h->use_coll = true;               // also with one rank: the exchange path is what this communicator exists to exercise
-  h->sp.external_reduce = 1;
-  destroy_graph(h);
-  h->need_prep = true;
   return PSMF_OK;
 }
 

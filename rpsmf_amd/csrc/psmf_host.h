@@ -1,5 +1,5 @@
-// Host side of libpsmf_hip.so, shared by its translation units (psmf_capi.hip, psmf_series.hip, psmf_blocked.hip, psmf_filter34.hip,
-// psmf_impute.hip, psmf_ssm.hip, psmf_bocpd.hip, psmf_pmf.hip, psmf_bpmf.hip): the handle, the switch table, the error helpers and the few host functions that cross
+// Host side of libpsmf_hip.so, shared by its translation units (psmf_capi.hip, psmf_step.hip, psmf_comm.hip, psmf_rotation.hip, psmf_series.hip,
+// psmf_blocked.hip, psmf_filter34.hip, psmf_impute.hip, psmf_ssm.hip, psmf_bocpd.hip, psmf_pmf.hip, psmf_bpmf.hip): the handle, the switch table, the error helpers and the few host functions that cross
 // unit boundaries.  A kernel is launched -- and its LDS opt-in is made -- only in the unit that defines it (the rule of psmf_pstep.h);
 // across units only these functions are called; the entry points without a handle (the last five units) stand on psmf_batch.h.
 #pragma once
@@ -254,16 +254,28 @@ enum FilterKernel { FK_STEP = 0, FK_GENERAL = 1, FK_FILTER2 = 2, FK_FILTER3 = 3,
 inline constexpr char kRingRefused[] = " is not available on a handle with a series ring (psmf_series_ring)";
 
 constexpr int kSqErrorParts = 1024;      // workgroups of psmf_sq_error_k = partial sums that sq_error_sum reads back
+constexpr int kGramWG = 128;             // workgroups of the exact Gram (psmf_step.hip) = partial Grams that alloc_common sizes gpart for
 
 // ---- host functions that cross unit boundaries ----
-// psmf_capi.hip
-int all_reduce_sum(psmf_filter* h, double* buf, size_t count, hipStream_t s);
-bool pstep_usable(const psmf_filter* h);
+// psmf_capi.hip: the C ABI
 int run_steps(psmf_filter* h, int64_t k_begin, int64_t k_end);      // the steps of a checked psmf_run, read at k - sp.series_t0
-void destroy_graph(psmf_filter* h);
 int ensure_scratch(psmf_filter* h, size_t bytes);
+void launch_prepare_k(psmf_filter* h, int64_t k);      // start of a run: the step counter, on the handle's stream
+// psmf_step.hip: the launched per-step engine and the host driver of the persistent kernel
+int init_step(psmf_filter* h);                          // psmf_create: LDS opt-ins, the persistent kernel's plan
+int prepare_step(psmf_filter* h, int64_t k_begin);      // the per-step engine's part of a run's preparation
+int run_step_engine(psmf_filter* h, int64_t k_begin, int64_t k_end);
+int time_step_kernels(psmf_filter* h, int which, int iters, float* avg_us);
+bool pstep_usable(const psmf_filter* h);
+void destroy_graph(psmf_filter* h);
+void print_pstep_prof(psmf_filter* h);
+// psmf_comm.hip: the communicator
+int all_reduce_sum(psmf_filter* h, double* buf, size_t count, hipStream_t s);
+// psmf_rotation.hip: the noise rotation
 int ensure_rot_tmp(psmf_filter* h, size_t bytes);
 int rot_rows(psmf_filter* h, const void* src, void* dst, long long n, bool fwd);
+int rot_rows_back_f64(psmf_filter* h, const double* src, double* dst, long long n);
+int rot_dict(psmf_filter* h, const void* src, void* dst, bool fwd);
 // psmf_series.hip: the series buffers (resident or a ring), their uploads, downloads and reductions
 int ring_run(psmf_filter* h, int64_t k_begin, int64_t k_end);      // psmf_run on a ring handle
 int sq_error_sum(psmf_filter* h, hipStream_t stream, int storage, const void* yp, const void* y, size_t n, double* part_d, double* acc);
@@ -271,8 +283,7 @@ int sq_error_sum(psmf_filter* h, hipStream_t stream, int storage, const void* yp
 FilterKernel select_filter_kernel(const psmf_filter* h);
 int init_blocked(psmf_filter* h);
 void clear_block_abort_flag(psmf_filter* h);      // start of a run, on the handle's stream
-int enqueue_block(psmf_filter* h, int64_t k0, int nb);
-int enqueue_blocks_pipelined(psmf_filter* h, int64_t k_begin, int64_t k_end);
+int run_blocks(psmf_filter* h, int64_t k_begin, int64_t k_end);
 int time_block_kernels(psmf_filter* h, int which, int iters, int nb, const DevState* saved_st, float* avg_us);
 // psmf_filter34.hip: the filter3 family (FK_FILTER3, 3S, 4, 4S, 5)
 int opt_in_lds_filter34(psmf_filter* h);

@@ -88,58 +88,12 @@ __device__ __forceinline__ double held_out_sse(const double* sC, const int ldc, 
 //       lane) -- <G, P + Q>, eta, N, phi                                                                  | barrier 3
 //   P3b wave 0 alone, NO barrier: the two symmetric sweep inversions of the reference's Woodbury form (PSMF.py:30-36)
 //       with the 16 x 16 matrix in its registers -- the rank-2 update of a pivot round is one float64 MFMA, the pivot
-//       block travels by v_readlane (wave_sweep16; since the end of round 3 its multiplier form, wave_sweep16m of
-//       psmf_wave16.hip) -- then x_t = x_p + kappa P+ C^T e (four MFMAs), omega, P, Q
+//       block travels by v_readlane (wave_sweep16m, psmf_wave16.hip: lane predicates as 0.0 / 1.0 multipliers, which replaced
+//       the select form at the end of round 3) -- then x_t = x_p + kappa P+ C^T e (four MFMAs), omega, P, Q
 //   P4  meanwhile waves 1-3: rank-1 updates of C and V (they need N, phi only); then every row owner: bands, metrics | barrier 4
 // P, Q, rho, lambda live in wave 0's registers for the whole run; x is double-buffered in LDS.
 // Measured on the config-D shape (d = 19, r = 10): tools/impute_prof.hip.
 // ------------------------------------------------------------------------------------------------------------
-// Symmetric sweep of the leading r2 x r2 block (r2 even; identity padding beyond r) of the 16 x 16 matrix held by ONE wave
-// (lane: column lr = l & 15, rows lk + 4 q, lk = l >> 4):  A <- -A^-1, by 2 x 2 SPD block pivots as sweep_all
-// (psmf_kernels.hip) -- half as many dependent rounds as single pivots -- with no LDS memory and no barrier: the rank-2
-// update of a pivot round is ONE v_mfma_f64_16x16x4_f64, the pivot block travels by v_readlane.  (A lone wave issues one
-// instruction per 4+ cycles, so a round costs what it has instructions: the first version moved the pivot rows and columns
-// with 20 lane shuffles and updated with 8 FMAs per lane, 100 instructions per round against 50.)  Symmetric in, symmetric
-// out up to round-off (the two halves of a pair are different FMA chains on the matrix cores).
-// Rows k, k + 1 of the matrix are the register A[k >> 2] of the lanes lk = k & 3, (k + 1) & 3 -- which is exactly where the
-// A operand of the MFMA wants the two columns u, w (by symmetry) in k-slots k & 3, (k + 1) & 3; the B operand is
-// -Ki [u; w]^T in the same lanes (pivot columns: +Ki, their C input zeroed), formed from u_j, w_j that one
-// v_permlane16_swap pair brings into both rows.  D = keep o A - u t1^T - w t2^T, then the pivot rows are overwritten in place.
-__device__ __forceinline__ void wave_sweep16(double (&A)[4], const int r2, const int lk, const int lr, bool& bad) {
-#pragma unroll
-  for (int k = 0; k < 16; k += 2) {
-    if (k < r2) {                                  // uniform
-      const int b0 = (k & 3) << 4, b1 = b0 + 16, kq = k >> 2;
-      const double rk = A[kq];
-      const double ka = readlane_f64(rk, b0 | k), kb = readlane_f64(rk, b0 | (k + 1)), ke = readlane_f64(rk, b1 | (k + 1));
-      const double det = ka * ke - kb * kb;
-      bad |= !(ka > 0.0) | !(det > 0.0);
-      const double dinv = fast_rcp(det);
-      const double kp = ke * dinv, kq2 = -kb * dinv, ks = ka * dinv;       // Ki = [[kp, kq2], [kq2, ks]]
-      // u_j (even row of the pair) and w_j (odd row) in both rows of each pair
-      const unsigned lo = __double2loint(rk), hi = __double2hiint(rk);
-      const auto l2 = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-      const auto h2 = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-      const double uj = __hiloint2double(h2[0], l2[0]), wj = __hiloint2double(h2[1], l2[1]);
-      const bool c0 = (lr == k), c1 = (lr == k + 1), piv = c0 | c1;
-      const bool in_piv = (lk >> 1) == ((k >> 1) & 1);      // the lanes that hold the two pivot rows
-      const bool is_u = (lk & 1) == 0;                      // ... row k (else row k + 1)
-      const double u1 = c0 ? 1.0 : (c1 ? 0.0 : uj), w1 = c0 ? 0.0 : (c1 ? 1.0 : wj);
-      const double cu = is_u ? kp : kq2, cw = is_u ? kq2 : ks;
-      const double sv = cu * u1 + cw * w1;                  // t1_j / t2_j; at the pivot columns the entries of Ki
-      const double aop = in_piv ? rk : 0.0;
-      const double bop = in_piv ? (piv ? sv : -sv) : 0.0;
-      const double keep = piv ? 0.0 : 1.0;
-      f64x4 acc = {keep * A[0], keep * A[1], keep * A[2], keep * A[3]};
-      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(aop, bop, acc, 0, 0, 0);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) A[q] = acc[q];
-      A[kq] = in_piv ? (piv ? -sv : sv) : acc[kq];          // the pivot rows: t1, t2; pivot block: -Ki
-    }
-  }
-}
-
-
 // WV: the wave index as a compile-time constant -- one column loop per wave, each holding only its own role's registers and code
 // (wave 0: the r x r work; wave 1: W beside it, Gram share; waves 2, 3: Gram share, rank-1 updates; wave 3: w = V x).  With the
 // wave index as a run-time value every wave carried the union of the roles through the loop (the same change took 7 % off the

@@ -102,8 +102,8 @@ __device__ __forceinline__ void ns_store_tile(double* sX, const f64x4 acc, const
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// Symmetric sweep of a matrix up to 32 x 32 held by ONE wave as NT x NT tiles of 16 x 16 in the MFMA output layout (the 16 x 16
-// original: wave_sweep16 / wave_sweep16m, psmf_impute.hip / psmf_wave16.hip)
+// wave_sweep_tiles_m (below, behind its per-lane constants): symmetric sweep of a matrix up to 32 x 32 held by ONE wave as NT x NT
+// tiles of 16 x 16 in the MFMA output layout (the 16 x 16 original: wave_sweep16m, psmf_wave16.hip)
 // (tile (ti, tj), lane l: column 16 tj + (l & 15), rows 16 ti + (l >> 4) + 4 q):  A <- -A^-1 of the leading r2 x r2 block (r2 even;
 // identity padding beyond r), 2 x 2 SPD block pivots, no LDS, no barrier.  A round pivots on rows k, k + 1 of tile row tp = k >> 4:
 // they sit in register kq = (k & 15) >> 2 of the lanes lk = k & 3, (k + 1) & 3 of the tiles (tp, 0 .. NT) -- which is where the A
@@ -114,58 +114,6 @@ __device__ __forceinline__ void ns_store_tile(double* sX, const f64x4 acc, const
 // publish / barrier / read exchange per round, ~700 cycles alone and ~1400 on a CU shared with a streaming workgroup) sat on a
 // step's critical path: the solve block of the per-step engine (r <= 32).
 // ------------------------------------------------------------------------------------------------------------
-template <int NT>
-__device__ __forceinline__ void wave_sweep_tiles(double (&A)[NT][NT][4], const int r2, const int lk, const int lr, bool& bad) {
-#pragma unroll
-  for (int k = 0; k < 16 * NT; k += 2) {
-    if (k < r2) {                                  // uniform
-      const int tp = k >> 4, kl = k & 15, kq = kl >> 2, b0 = (kl & 3) << 4, b1 = b0 + 16;
-      const double rkd = A[tp][tp][kq];
-      const double ka = readlane_f64(rkd, b0 | kl), kb = readlane_f64(rkd, b0 | (kl + 1)), ke = readlane_f64(rkd, b1 | (kl + 1));
-      const double det = ka * ke - kb * kb;
-      bad |= !(ka > 0.0) | !(det > 0.0);
-      const double x0 = __builtin_amdgcn_rcp(det);
-      const double e1 = fma(-det, x0, 1.0);
-      const double dinv = fma(x0 * e1, 1.0 + e1, x0);       // 1 / det: v_rcp_f64 and one cubic step
-      const double kp = ke * dinv, kq2 = -kb * dinv, ks = ka * dinv;       // Ki = [[kp, kq2], [kq2, ks]]
-      const bool in_piv = (lk >> 1) == ((kl >> 1) & 1);     // the lanes that hold the two pivot rows
-      const bool is_u = (lk & 1) == 0;                      // ... row k (else row k + 1)
-      const double cu = is_u ? kp : kq2, cw = is_u ? kq2 : ks;
-      double aop[NT], bop[NT], sv[NT];
-      bool piv[NT];
-#pragma unroll
-      for (int tj = 0; tj < NT; ++tj) {
-        const double rk = A[tp][tj][kq];
-        const unsigned lo = __double2loint(rk), hi = __double2hiint(rk);
-        const auto l2 = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-        const auto h2 = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-        const double uj = __hiloint2double(h2[0], l2[0]), wj = __hiloint2double(h2[1], l2[1]);
-        const bool c0 = (tj == tp) && (lr == kl), c1 = (tj == tp) && (lr == kl + 1);
-        piv[tj] = c0 | c1;
-        const double u1 = c0 ? 1.0 : (c1 ? 0.0 : uj), w1 = c0 ? 0.0 : (c1 ? 1.0 : wj);
-        sv[tj] = cu * u1 + cw * w1;                         // t1_j / t2_j; at the pivot columns the entries of Ki
-        aop[tj] = in_piv ? rk : 0.0;
-        bop[tj] = in_piv ? (piv[tj] ? sv[tj] : -sv[tj]) : 0.0;
-      }
-#pragma unroll
-      for (int ti = 0; ti < NT; ++ti)
-#pragma unroll
-        for (int tj = 0; tj < NT; ++tj) {
-          f64x4 acc = {A[ti][tj][0], A[ti][tj][1], A[ti][tj][2], A[ti][tj][3]};
-          if (tj == tp) {                  // (compile time) the pivot columns lie in tile column tp: their C input is zeroed
-            const double keep = piv[tj] ? 0.0 : 1.0;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) acc[q] *= keep;
-          }
-          acc = __builtin_amdgcn_mfma_f64_16x16x4f64(aop[ti], bop[tj], acc, 0, 0, 0);
-#pragma unroll
-          for (int q = 0; q < 4; ++q) A[ti][tj][q] = acc[q];
-        }
-#pragma unroll
-      for (int tj = 0; tj < NT; ++tj) A[tp][tj][kq] = in_piv ? (piv[tj] ? -sv[tj] : sv[tj]) : A[tp][tj][kq];   // pivot rows: t1, t2; pivot block: -Ki
-    }
-  }
-}
 
 // Per-lane constants of wave_sweep16m as numbers (lane: column lr = l & 15, rows lk + 4 q, lk = l >> 4); round j pivots on
 // rows / columns 2 j, 2 j + 1, which are register A[j >> 1] of the lane rows lk = 2 (j & 1), 2 (j & 1) + 1.
@@ -191,9 +139,9 @@ __device__ __forceinline__ void sw16k_init(Sw16K& c, const int lk, const int lr)
   c.fw = 1.0 - c.fu;
 }
 
-// wave_sweep_tiles with the lane predicates as multipliers (the form of wave_sweep16m, psmf_wave16.hip): a select of a double is two
+// The tile sweep with the lane predicates as multipliers (the form of wave_sweep16m, psmf_wave16.hip): a select of a double is two
 // v_cndmask and -- in kernels that have run out of SGPRs -- the reload of its lane mask from a spilled pair; a multiply by 0.0 / 1.0 is one
-// instruction.  The select form spent 24 v_cndmask and 8 mask reloads of the 89 instructions of a round (NT = 2, ISA of
+// instruction.  The select form it replaced spent 24 v_cndmask and 8 mask reloads of the 89 instructions of a round (NT = 2, ISA of
 // psmf_blk_filter7); c: sw16k_init(lk, lr), tile-local (the pivot columns of a round lie in tile column tp only).
 template <int NT>
 __device__ __forceinline__ void wave_sweep_tiles_m(double (&A)[NT][NT][4], const int r2, const Sw16K& c, bool& bad) {
@@ -258,11 +206,6 @@ __device__ __forceinline__ void wave_sweep_tiles_m(double (&A)[NT][NT][4], const
 // round of the 3 x 3 sweep costs ~1 700 cycles of one wave's instruction stream, of the 2 x 2 one ~850, of the single tile ~500.
 // Identity padding beyond r2 (as wave_sweep_tiles_m expects it) stays padding: the padded rows / columns of B are zero.
 // ------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void tile_xty(const double (&X)[4], const double (&Y)[4], f64x4& acc) {      // acc += X^T Y  (16 x 16 tiles, K = 16)
-#pragma unroll
-  for (int q = 0; q < 4; ++q) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(X[q], Y[q], acc, 0, 0, 0);
-}
-
 __device__ __forceinline__ void wave_inverse_blocked2(double (&A)[2][2][4], const int r2, const Sw16K& c, bool& bad);
 __device__ __forceinline__ void wave_inverse_blocked3(double (&A)[3][3][4], const int r2, const Sw16K& c, bool& bad) {
   double T[2][2][4];

@@ -1,7 +1,7 @@
 // Owning types of the host code: every device buffer, pinned host buffer, event and stream of libpsmf_hip.so belongs to one object
 // of a type below, and the object's destructor is what releases it.  This header is the only place that names the HIP functions
 // which create or destroy one; a create call with flags stays at its use site and writes through put().  (The one exception is the
-// process-lifetime event chain of launch_pstep in psmf_capi.hip.)
+// process-lifetime event chain of launch_pstep in psmf_step.hip.)
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -10,13 +10,13 @@
 // registers per wave on offer, puts them in AGPRs: 16 copies and a 16-cycle stall per pivot round).
 #pragma once
 #include "psmf_wave.h"        // readlane_f64, DPP sums, f64x4
-#include "psmf_ns.hip"        // Sw16K, wave_sweep_tiles
+#include "psmf_ns.hip"        // Sw16K, wave_sweep_tiles_m
 
 namespace psmf {
 
 // (Sw16K / sw16k_init, the per-lane constants of the multiplier-form sweeps: psmf_ns.hip)
 
-// wave_sweep16 (psmf_impute.hip) with the lane predicates as multipliers: A <- -A^-1 of the leading r2 x r2 block by 2 x 2
+// Symmetric sweep of a 16 x 16 matrix held by ONE wave, the lane predicates as multipliers: A <- -A^-1 of the leading r2 x r2 block by 2 x 2
 // SPD block pivots, the rank-2 update of a round on the matrix cores, the pivot block by v_readlane.
 //   Ki = K^-1 of the pivot block;  t_j = Ki [u_j; w_j] (u, w = rows 2 j, 2 j + 1);  the MFMA's B operand holds -t in the
 //   pivot rows' lanes (+Ki at the pivot columns, whose C input is zeroed), its A operand the pivot rows as they stand
@@ -55,7 +55,7 @@ __device__ __forceinline__ void wave_sweep16m(double (&A)[4], const int r2, cons
   }
 }
 
-// (wave_sweep_tiles<NT>, the same sweep for NT x NT tiles in one wave's registers, lives in psmf_ns.hip: the block filters use it too)
+// (wave_sweep_tiles_m<NT>, the same sweep for NT x NT tiles in one wave's registers, lives in psmf_ns.hip: the block filters use it too)
 
 // ------------------------------------------------------------------------------------------------------------
 // Solve block of the per-step engine for r <= 32 (declared in psmf_kernels.hip, which psmf_sweep_solve's block 0 calls): the two

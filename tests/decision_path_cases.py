@@ -38,7 +38,7 @@ QUIET = dict(rho=1e6, q=1e-3)
 SWEEP_ENV = {"PSMF_NS_FAR": "1e-2", "PSMF_NS_SKIP": str(SKIP_N)}
 
 # (robust, storage, path) -> (problem, environment, the pass whose counters show the path).  float64 storage accepts at 3e-7 by
-# default, float32 at 3e-4 (psmf_capi.hip).
+# default, float32 at 3e-4 (fill_step_params, psmf_capi.hip).
 SETTINGS = {
     (False, "f32", "one"): (QUIET, {"PSMF_NS_TOL": "1e-2"}, 1),
     (False, "f32", "two"): (QUIET, {}, 1),

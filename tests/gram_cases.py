@@ -28,13 +28,13 @@ from netlib import f32_round, relerr, spd  # noqa: F401  (the device tests take 
 from oracle import psmf_oracle as O
 from oracle.impute_oracle import impute_filter, mle_smf_filter, tmf_filter
 
-# ---- the geometry (psmf_masked.hip, psmf_capi.hip)
-N_WG = 256                 # kMGramWG, psmf_capi.hip: "constexpr int kMGramWG = 256"
+# ---- the geometry (psmf_masked.hip, psmf_step.hip)
+N_WG = 256                 # kMGramWG, psmf_step.hip: "constexpr int kMGramWG = 256"
 SLAB = 16                  # mgram_body: "const int nslab = (dl + 15) / 16"
-WGRAM_NW = 8               # wgram_inst, psmf_capi.hip: "psmf::psmf_wgram_mfma<T, NT, 8>"
-# serial_mgram_for, psmf_capi.hip: class -> (NT, NW); class = the padded rank, 64 split at r = 48 ("r <= 48 ? <64, T, 3, 4> : <64, T, 4, 4>")
+WGRAM_NW = 8               # wgram_inst, psmf_step.hip: "psmf::psmf_wgram_mfma<T, NT, 8>"
+# serial_mgram_for, psmf_step.hip: class -> (NT, NW); class = the padded rank, 64 split at r = 48 ("r <= 48 ? <64, T, 3, 4> : <64, T, 4, 4>")
 MGRAM = {8: (1, 16), 16: (1, 16), 32: (2, 8), 48: (3, 4), 64: (4, 4)}
-# wgram_for, psmf_capi.hip: "rpad <= 16 -> NT 1; rpad == 32 -> 2; r <= 48 ? 3 : 4"
+# wgram_for, psmf_step.hip: "rpad <= 16 -> NT 1; rpad == 32 -> 2; r <= 48 ? 3 : 4"
 WGRAM_NT = {8: 1, 16: 1, 32: 2, 48: 3, 64: 4}
 CLASSES = (8, 16, 32, 48, 64)
 BIG_D = 16_000             # rows beyond which a case runs 3 .. 6 steps and one pass
@@ -217,7 +217,7 @@ def shorten(cs):
 
 def reached(cs):
     """what a configuration lands on, restated from the dispatch: the masked handle's (class, storage, reason for the launched
-    form) -- pstep_usable, psmf_capi.hip: masked = 2 / 3 never, r > 32 never, a communicator never, PSMF_STEP_PERSISTENT=0 never --
+    form) -- pstep_usable, psmf_step.hip: masked = 2 / 3 never, r > 32 never, a communicator never, PSMF_STEP_PERSISTENT=0 never --
     or the weighted Gram's (NT, storage, unit: enqueue_weighted_gram)"""
     if not cs["masked"]:
         return ("w", WGRAM_NT[class_of(cs["r"])], cs["storage"], "valu" if cs["env"].get("PSMF_WGRAM_MFMA") == "0" else "mfma")

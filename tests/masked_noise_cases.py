@@ -19,7 +19,7 @@ import numpy as np
 from netlib import f32_round, relerr  # noqa: F401  (the tests take relerr from here)
 from oracle.impute_oracle import impute_filter, mle_smf_filter
 
-N_WG, SLAB, WGRAM_NW = 256, 16, 8           # kMGramWG and wgram_inst (psmf_capi.hip), mgram_body's slab (psmf_masked.hip)
+N_WG, SLAB, WGRAM_NW = 256, 16, 8           # kMGramWG and wgram_inst (psmf_step.hip), mgram_body's slab (psmf_masked.hip)
 BOUND = SLAB * N_WG * WGRAM_NW              # rows up to which every wave of the weighted Gram takes one slab
 SECOND_TRIP_COLUMN = 7
 SIG, LAMBDA0 = 2.0, 1.8

@@ -13,7 +13,7 @@
 #include <numeric>
 #include <vector>
 
-thread_local std::string g_create_error;      // (the library's lives in psmf_capi.hip)
+thread_local std::string g_create_error;      // (the library's lives in psmf_capi.hip, the C ABI unit)
 
 static int g_live = 0, g_failed = 0;
 static size_t g_alloc_bytes = 0, g_copy_bytes = 0;     // of the last allocation / copy

@@ -105,7 +105,7 @@ def np_list(rpad):
     return (4, 8, 12) + ((16,) if rpad == 64 else ())
 
 
-# ---- which handles take the persistent kernel (init_pstep, pstep_usable: psmf_capi.hip)
+# ---- which handles take the persistent kernel (init_pstep, pstep_usable: psmf_step.hip)
 def _on(cs, name):
     return cs["env"].get(name) != "0"
 

@@ -76,6 +76,15 @@ def test_a_file_with_a_plain_global_kernel_belongs_to_exactly_one_unit():
     assert n_checked >= 7      # psmf_kernels, psmf_block, psmf_masked, psmf_blk16, psmf_blk32, psmf_blk34, psmf_impute2
 
 
+def test_the_c_abi_unit_reaches_no_engine_kernels():
+    """psmf_capi.hip is the glue: the per-step engine, the blocked engine and the rotation are launched by their own units"""
+    deps = {os.path.basename(d) for _obj, src, ds, _extra in _units() if os.path.basename(src) == "psmf_capi.hip" for d in ds}
+    assert "psmf_capi.hip" in deps and "psmf_host.h" in deps, deps
+    engine_files = {"psmf_kernels.hip", "psmf_masked.hip", "psmf_wave16.hip", "psmf_ns.hip", "psmf_rotate.hip", "psmf_block.hip", "psmf_blk3.hip"}
+    assert all(os.path.isfile(os.path.join(CSRC, f)) for f in engine_files)      # (a renamed file would pass the next line unseen)
+    assert deps & engine_files == set(), f"psmf_capi.hip reaches {sorted(deps & engine_files)}"
+
+
 def test_includes_stand_at_the_top_of_a_file():
     for p in _csrc_files():
         code_seen = None

@@ -74,7 +74,7 @@ def test_only_psmf_own_h_names_the_functions_that_create_or_release():
                 continue
             through_put = [m.group(1) for m in THROUGH_PUT.finditer(line)]
             assert names == through_put, f"{f}:{n}: {sorted(set(names))} outside psmf_own.h and not a create call through put(): {line.strip()}"
-    assert ps_event_lines == 1, "the event chain of launch_pstep (psmf_capi.hip) is the one exception, on one line"
+    assert ps_event_lines == 1, "the event chain of launch_pstep (psmf_step.hip) is the one exception, on one line"
 
 
 def test_psmf_destroy_releases_nothing_by_hand():
