@@ -331,9 +331,10 @@ def lowrank_step(st: State, y, k, mode: Mode, dyn: Dynamics, Qk=None, rhok=None,
 # --------------------------------------------------------------------------
 # one step, reference-shaped dense algebra (O(d^2 r))
 # --------------------------------------------------------------------------
-def literal_step(st: State, y, k, mode: Mode, dyn: Dynamics, Qk=None, rhok=None):
+def literal_step(st: State, y, k, mode: Mode, dyn: Dynamics, Qk=None, rhok=None, want_grad=True):
     """Same step with the d x d matrices formed explicitly, unmasked only.  st.rho (or rhok) may be a d x d matrix: a
     non-diagonal R, which only this function takes (dense inverse of the innovation covariance, psmf.py:150-152).
+    The theta gradient is accumulated as lowrank_step accumulates it (want_grad).
 
     This is what the reference costs: dense R, kron(s, I_d), d x d inverse-innovation
     matrix, d x d trace argument (psmf.py:121-125,140-165).  Used for the
@@ -396,8 +397,23 @@ def literal_step(st: State, y, k, mode: Mode, dyn: Dynamics, Qk=None, rhok=None)
         rho_new = omega * (st.rho if rhok is None else rhok)
         lam_new = lam if mode.fixed_lambda else lam + d
 
+    # the theta gradient (psmf.py:48-66,167-177, rpsmf.py:53-73,173-184): the same g_f lines as lowrank_step -- R enters through N alone
+    gradsum = st.gradsum
+    if want_grad and dyn.n_theta > 0:
+        Jt = dyn.jac_theta(theta, mu, k)
+        w = (V @ xb).reshape(-1)
+        h = (C.T @ resid).reshape(-1)
+        ee = (resid.T @ resid).item()
+        if mode.robust:
+            D = st.lam * N
+            gf = d * w / N + 0.5 * (d + st.lam) * (-2.0 * h / D - 2.0 * st.lam * ee * w / D**2) / (1.0 + ee / D)
+        else:
+            gf = d * w / N - h / N - ee * w / N**2
+        g = Jt.T @ gf
+        gradsum = g if gradsum is None else gradsum + g
+
     new = State(C=C_new, V=V_new, mu=mu_new.reshape(-1), P=P_new, Q=Q_new, rho=rho_new,
-                lam=lam_new, theta=st.theta, gradsum=st.gradsum)
+                lam=lam_new, theta=st.theta, gradsum=gradsum)
     info = StepInfo(y_pred=yp.reshape(-1), eta=float(eta), N=float(N), s=float(sv), phi=phi, omega=omega)
     return new, info
 
@@ -421,10 +437,7 @@ def run_epoch(st: State, Y, mode: Mode, dyn: Dynamics, Qs=None, rhos=None, k0=0,
         k = k0 + j + 1
         Qk = None if Qs is None else Qs(k)
         rk = None if rhos is None else rhos(k)
-        if step is lowrank_step:
-            st, info = step(st, Y[j], k, mode, dyn, Qk=Qk, rhok=rk, want_grad=want_grad)
-        else:
-            st, info = step(st, Y[j], k, mode, dyn, Qk=Qk, rhok=rk)
+        st, info = step(st, Y[j], k, mode, dyn, Qk=Qk, rhok=rk, want_grad=want_grad)
         Y_pred[j] = info.y_pred
         if k in keep:
             trace[k] = (st.copy(), info)

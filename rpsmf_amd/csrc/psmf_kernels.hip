@@ -689,7 +689,12 @@ __device__ __forceinline__ void serial_body(const StepParams& p, const int first
   // =============== everything the NEXT sweep / solve needs (step index knext + 1) ===========
   // PSMFIter reads Q[k], R[k] of the step itself (psmf.py:115,123,141): scalar schedules (never with rPSMF's running Q, R)
   const double qs = p.q_sched ? p.q_sched[knext + 1 - p.series_t0] : 1.0;
-  if (p.rho_sched) rho = p.rho_sched[knext + 1 - p.series_t0];
+  if (p.rho_sched) {
+    rho = p.rho_sched[knext + 1 - p.series_t0];
+    // non-uniform diagonal R: the row weights 1 / (rho rho_i + s) of the next sweep and of its weighted Gram read st->rho, so the
+    // scalar in front of diag(rho_rows) is the scheduled one there too (eta and kappa below take it from the register)
+    if (p.rho_rows && tid == 0) st->rho = rho;
+  }
   const double* qm = p.q_mat ? p.q_mat + (size_t)(knext + 1 - p.series_t0) * r * r : nullptr;     // Q_k as a matrix of its own
   double* sF = &s_part[0][0];          // dense F = df/dx, row stride RPAD + 1 (s_part is free since the reduction)
   constexpr int FS = RPAD + 1;
